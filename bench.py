@@ -14,6 +14,8 @@ batch every step.  Weak scaling: every rank owns a full batch (the small CSR rep
 the encoder of leg 2 either node-row sharded with one RCCL all-gather per layer or replicated, whichever is faster);
 `strong_scaling` beside it cuts ONE list (the 504 514 non-edges within hop distance) into cost-balanced shards.
 `--gpus N` without a launcher starts its own N ranks (torch.distributed.run, before any GPU call).  Rank 0 prints ONE JSON line.
+`--dump-outputs DIR`: rank 0 also writes what the timed region's LAST step computed as DIR/<name>.npy (see dump_outputs); the
+inputs are seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -356,6 +358,20 @@ def rotated_batches(wl, count, seed=4321):
     return out
 
 
+DUMP_CAP_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays):
+    """Write each array as path/<name>.npy (float32 / float64 only, 64 MB in all at most)."""
+    assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_CAP_BYTES:
+        raise SystemExit("--dump-outputs: %d bytes exceed the %d-byte cap" % (total, DUMP_CAP_BYTES))
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -381,7 +397,12 @@ def main():
                     help="do not run the two rocprofv3 --pmc child passes that measure roofline.traffic (it is then read from profiles/)")
     ap.add_argument("--no-kernel-events", action="store_true",
                     help="development: no per-kernel HIP events in the timed region (the roofline block is then meaningless)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed (rank 0) as DIR/<name>.npy: pi_images [E, 25] "
+                         "float64, pi_status [E] (status bytes as float32), lp_prob [2E] float32")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(_self_launch(args.gpus, sys.argv[1:]))
@@ -662,6 +683,8 @@ def main():
     t_lp = ev_pi[K].elapsed_time(ev_lp[K - 1]) * 1e-3
     pi_steps = [ev_pi[s].elapsed_time(ev_pi[s + 1]) for s in range(K)] if args.sync_batches else [t_pi * 1e3 / K]
     lp_steps = [(ev_pi[K] if s == 0 else ev_lp[s - 1]).elapsed_time(ev_lp[s]) for s in range(K)]
+    # the probabilities of the last timed forward, before anything below runs the leg again (--dump-outputs)
+    lp_snapshot = prob.clone() if args.dump_outputs else None
     ktimes_timed = [] if args.no_kernel_events else g.timing_history(dom_warm, cap=min((K + 3) // 4, 64))
     if world > 1:
         import torch.distributed as dist
@@ -1201,6 +1224,11 @@ def main():
             out["cpu_baseline"]["max_rel_diff_vs_gpu"] = float((np.abs(got[nz] - ref[nz]) / np.abs(ref[nz])).max()) if nz.any() else 0.0
             out["cpu_baseline"]["status_equal_vs_gpu"] = bool(np.array_equal(snap_s[: len(sample)].cpu().numpy(), rst))
             out["cpu_baseline"]["checked"] = "rows written by the last step of the timed region (pipelined submission)"
+        if args.dump_outputs:
+            snap_o, snap_s, _ = timed_snapshot
+            dump_outputs(args.dump_outputs, {"pi_images": snap_o.cpu().numpy(),
+                                             "pi_status": snap_s.cpu().numpy().astype(np.float32),
+                                             "lp_prob": lp_snapshot.cpu().numpy()})
         print(json.dumps(out))
     if world > 1:
         import torch.distributed as dist

@@ -126,7 +126,9 @@ def _worker(rank, world, port, q):
         lo_r, hi_r = tdist.shard_bounds(n, world, r_)
         assert padded[lo_r:hi_r].equal(torch.arange(hi_r - lo_r) + r_ * pr_rows.blk)
     q.put((rank, float((emb - full).abs().max()), float((prob - prob_full[lo:hi]).abs().max()), tuple(emb.shape)))
-    dist.barrier()
+    # the closing barrier as a CPU all-reduce: dist.barrier() probes for an accelerator, which on a GPU machine has every rank
+    # open the device (8 ranks here)
+    dist.all_reduce(torch.zeros(1))
     dist.destroy_process_group()
 
 
