@@ -162,8 +162,8 @@ int tlc_pd_pi_algorithmic_bytes(int32_t n_nodes, const int32_t* h_rowptr, const 
  * phase_profile(): per-phase cycle counters of the tier kernels in a library built with `make PHASE_DEBUG=1` (all zero
  * otherwise): rows of 32 u64, one per tier and one for the early pass; at most cap_u64 values are written to h_out (may be
  * null), *n_rows (may be null) = rows kept.  enable != 0 starts counting, 0 stops and frees the counters.
- * set_option(): the fourteen switches of one handle, each exercised by a test that checks that results do not depend on it
- * (tests/test_gpu_extract.py, tests/test_gpu_tiers.py, tests/test_gpu_pd_parity.py); 1 = on is the default of the first eight:
+ * set_option(): the seventeen switches of one handle, each exercised by a test that checks that results do not depend on it
+ * (tests/test_gpu_extract.py, tests/test_gpu_tiers.py, tests/test_gpu_pd_parity.py, tests/test_gpu_pipelined.py); 1 = on is the default of the first eight:
  *   "extract"      ball-list extraction of the vicinities (any hop since round 5; 0: the breadth-first kernels; TLC_EXTRACT=0 at creation)
  *   "heavy"        its hub-row skipping (TLC_HEAVY=0)
  *   "tiny"         lane-per-subgraph kernel for vicinities of at most 16 nodes / 24 edges (TLC_TINY=0)
@@ -180,9 +180,21 @@ int tlc_pd_pi_algorithmic_bytes(int32_t n_nodes, const int32_t* h_rowptr, const 
  *   "tier_mask"    bit t: tier t's kernels are launched at all (cost tables under profiles/)
  *   "n_ws"         workspaces taken in turn by pipelined chunks (2..4, default 3)
  *   "timing_every" kernel events on every n-th chunk only
+ *   "mh_front_pos" pipelined plain chunks: compact MEDIUM vicinities with at least this many Pos edges go in front of their list
+ *                  (default TLC_MH_FRONT_POS = 64; 0: no front list)
+ *   "main_beside_early" pipelined chunks: the general extraction waits for the classification only and runs beside the early pass
+ *                  (default 1 = TLC_MAIN_BESIDE_EARLY; 0: it waits for the whole early pass, as a chunk on its own does)
+ *   "poison"       test hook: each chunk fills its workspace's float64 payload scratch with 7.25 before its first kernel (default 0)
  * An unknown name is TLC_ERR_INVALID_ARG. */
 int tlc_debug_set_option(tlc_graph* g, const char* name, int value);
 int tlc_debug_dc_stats(tlc_graph* g, long long* h_out, void* stream);
+/* Counters for tests, h_out[0 .. min(n, 12)): [0] front-list vicinities (option mh_front_pos) of the last tlc_pd_pi_batch call; since the
+ * handle was created: [1] front-list vicinities, [2] pipelined chunks, [3] chunks with the early pass, [4] speculative list positions
+ * beyond their reserved slots, [5] poisoned chunks, [6] bytes poisoned; [7..9] bytes the last poisoned chunk filled in the arena's,
+ * the early arena's and the SMALL slots' weights; [10] second halves submitted behind the next chunk's first half (not by a join or a
+ * drain), [11] the most workspaces with a chunk not yet waited for on the host at a chunk's submission.  Submits a deferred second
+ * half and synchronises `stream`. */
+int tlc_debug_chunk_counters(tlc_graph* g, long long* h_out, int32_t n, void* stream);
 /* The tier lists of the last tlc_pd_pi_batch call as the device cut them, h_out[8]: small, medium (the compact kernel configuration,
  * <= 384 nodes / 512 edges), large, huge, mid, tiny, medium with many Pos edges, medium beyond the compact configuration (<= 512 /
  * 1024).  tlc_pd_pi_batch_stats reports tiny with small and the three medium lists as one. */

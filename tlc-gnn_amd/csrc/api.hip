@@ -63,6 +63,16 @@ struct HostSync {
     volatile unsigned pub_seq;
 };
 
+// defaults of options mh_front_pos / main_beside_early (front_main_scan / front_join_early say what they do and what was measured)
+#ifndef TLC_MH_FRONT_POS
+#define TLC_MH_FRONT_POS 64      /* (96: -0.9 %, 64: -1.2 ... -1.9 %, 48: about the same, 32 and 128: less; two libraries or four in turn) */
+#endif
+#ifndef TLC_MAIN_BESIDE_EARLY
+#define TLC_MAIN_BESIDE_EARLY 1
+#endif
+// option poison: the sentinel a chunk's payload scratch is filled with (finite, outside [0, 1], where every filtration value lies)
+#define TLC_POISON 7.25
+
 #define TLC_N_WS 4                /* workspaces of a handle: chunks (and asynchronous batches) take them in turn */
 
 // Everything one chunk of pairs writes while it is in flight.  A handle has TLC_N_WS of them, taken in turn, each with its own
@@ -215,6 +225,17 @@ struct tlc_graph {
     unsigned timing_seq;
     int opt_tier_mask;                  // development: which tier kernels are launched at all (timing a tier alone; rows of the others are garbage)
     int opt_x_region, opt_x_bump_min;   // arena entries per workgroup region / minimum bump area of the extraction (tests shrink them)
+    int opt_mh_front_pos;               // pipelined plain chunks: Pos edges from which a compact MEDIUM vicinity stands in front of its list (0: no front list)
+    int opt_main_beside_early;          // pipelined chunks: the general extraction waits for the classification only, not for the early pass
+    int opt_poison;                     // tests: every chunk's payload scratch is filled with TLC_POISON before its first kernel (poison_chunk)
+    // tests (tlc_debug_chunk_counters): front-list vicinities of the last call; since the handle was created: front-list vicinities,
+    // pipelined chunks, chunks with the early pass, speculative list positions beyond their reserved slots, poisoned chunks, bytes
+    // poisoned; the bytes of each region the last poisoned chunk filled (A_lw, E_lw, S_lw)
+    long long last_n_hi;
+    long long cnt_n_hi, cnt_pipelined, cnt_early, cnt_beyond_spec, cnt_poisoned, cnt_poison_bytes;
+    long long cnt_deferred;             // second halves submitted behind the NEXT chunk's first half (not by a join, quiesce or debug call)
+    long long max_busy;                 // most workspaces with a chunk not yet waited for on the host, the new chunk's included
+    long long poison_region[3];
 };
 
 static int finish_pending(tlc_graph* g);
@@ -542,6 +563,7 @@ extern "C" int tlc_graph_create(int32_t n_nodes, const int32_t* h_rowptr, const 
     g->opt_plain_kernels = env_on("TLC_PLAIN_KERNELS") ? 1 : 0;
     g->opt_n_ws = 3;
     g->opt_x_region = TLC_X_REGION; g->opt_x_bump_min = 1 << 20; g->opt_tier_mask = (1 << TLC_N_TIERS) - 1; g->opt_timing_every = 1;
+    g->opt_mh_front_pos = TLC_MH_FRONT_POS; g->opt_main_beside_early = TLC_MAIN_BESIDE_EARLY;
     int rc = TLC_OK;
     auto fail = [&](int code) { tlc_graph_destroy(g); return code; };
 #define CK(e) do { if ((e) != hipSuccess) { tlc_set_error("%s failed: %s", #e, hipGetErrorString(hipGetLastError())); return fail(TLC_ERR_HIP); } } while (0)
@@ -865,6 +887,35 @@ static int front_prepare(tlc_graph* g, Workspace* ws, const int32_t* d_pairs, in
     return TLC_OK;
 }
 
+__global__ void tlc_fill_f64(double* p, long long n, double v) {
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) p[i] = v;
+}
+
+// Option poison (tests): the float64 payload of the workspace's scratch -- the weights of the arena, of the early arena and of the
+// SMALL tier's slots -- is filled with TLC_POISON on the chunk's own stream, ahead of every fork of its side streams, so a kernel that
+// reads an entry this chunk did not write sees 7.25 instead of a previous chunk's (possibly equal) value.  The previous chunk on this
+// workspace was waited for on the host (acquire_workspace).  Nothing that becomes an address, a loop bound or a count is touched:
+// headers, tier lists, directories, control block and hand-off slots keep whatever they held ("Who owns what").
+static int poison_chunk(tlc_graph* g, Workspace* ws, hipStream_t s) {
+    const struct { double* p; size_t n; } reg[3] = {
+        {ws->A_lw, ws->cap_entries},
+        {ws->E_lw, ws->E_lw ? (size_t)TLC_EARLY_SLOTS * 2 * TLC_L_MMAX : 0},
+        {ws->S_lw, ws->cap_small * (2 * TLC_S_MMAX)}};
+    long long bytes = 0;
+    for (int r = 0; r < 3; ++r) {
+        const long long n = reg[r].p ? (long long)reg[r].n : 0;
+        g->poison_region[r] = n * (long long)sizeof(double);
+        if (n == 0) continue;
+        const int grid = (int)std::min<long long>((n + 255) / 256, 4096);
+        hipLaunchKernelGGL(tlc_fill_f64, dim3(grid), dim3(256), 0, s, reg[r].p, n, (double)TLC_POISON);
+        TLC_HIP_CHECK(hipGetLastError());
+        bytes += n * (long long)sizeof(double);
+    }
+    g->cnt_poisoned += 1;
+    g->cnt_poison_bytes += bytes;
+    return TLC_OK;
+}
+
 // the fork of the early chain and the launch of the subgraph-list pairs
 static int front_fast(tlc_graph* g, Workspace* ws) {
     int rc;
@@ -873,9 +924,13 @@ static int front_fast(tlc_graph* g, Workspace* ws) {
     hipStream_t s = c.s;
     const int hop = c.hop, xgrid = c.xgrid, xfgrid = c.xfgrid;
     const bool early = c.early, use_x = c.use_x, fsplit = c.fsplit;
+    // (the one-off ball bounds and the early arena first: the poison covers the early arena, and the fork below follows both)
+    if (early && (rc = ensure_early(g, ws, hop, s)) != TLC_OK) return rc;
+    if (g->opt_poison && (rc = poison_chunk(g, ws, s)) != TLC_OK) return rc;
+    g->cnt_pipelined += c.pipelined ? 1 : 0;
+    g->cnt_early += early ? 1 : 0;
     if (early) {
-        // (the fork of the early chain: ahead of the FAST launch, which runs beside it; the one-off ball bounds go in front of it)
-        if ((rc = ensure_early(g, ws, hop, s)) != TLC_OK) return rc;
+        // (the fork of the early chain: ahead of the FAST launch, which runs beside it)
         TLC_HIP_CHECK(hipEventRecord(ws->ev_fork, s));                  // after the memsets (and the one-off bounds)
         TLC_HIP_CHECK(hipStreamWaitEvent(ws->side[4], ws->ev_fork, 0));
     }
@@ -985,14 +1040,11 @@ static int front_join_early(tlc_graph* g, Workspace* ws) {
         // the early COUNT is done and the early tier kernel's workgroups are resident (bounded: 50 us after the former).
         // (Measured and dropped, pipelined chunks: the main COUNT beside the early pass instead of behind it, and bounds of the gate
         // from none to 200 us: all within noise -- the machine is full of the previous chunk's tier kernels either way.)
-#ifndef TLC_MAIN_BESIDE_EARLY
-#define TLC_MAIN_BESIDE_EARLY 1
-#endif
         // (Round 6, pipelined chunks: the general launch waits for the classification only -- its bins and the candidates' count are all it
         // needs from the early stream; a pair has one owner, so the two launches write disjoint headers, regions and slots -- and runs
         // BESIDE the early pass; the scan still waits for the early list.  Two libraries in turn, three rounds: 0.4957 -> 0.4847 ms per
         // pipelined batch (-2.2 %), rotating batches -2.9 %.  A chunk on its own keeps the order that gets its LARGE workgroups placed first.)
-        if (TLC_MAIN_BESIDE_EARLY && c.pipelined && use_x) { TLC_HIP_CHECK(hipStreamWaitEvent(s, ws->ev_cls, 0)); }
+        if (g->opt_main_beside_early && c.pipelined && use_x) { TLC_HIP_CHECK(hipStreamWaitEvent(s, ws->ev_cls, 0)); }
         else TLC_HIP_CHECK(hipStreamWaitEvent(s, ws->ev_early, 0));
         // (Round 6: no gate for a pipelined chunk.  With other chunks' tier kernels on every CU the LARGE workgroups are never resident
         // within the bound, so the gate was a 50 us wait -- and a kernel of its own -- in the middle of every first half: in-region timeline
@@ -1068,11 +1120,9 @@ static int front_main_scan(tlc_graph* g, Workspace* ws) {
     // but to stand in FRONT of the compact MEDIUM launch (TlcPdParams::tier_list_hi): the swap kernel ends most batches and lasts as long as
     // its longest walk plus the time that walk's wavefront waited to be placed.  tools/order_probe.py: the MEDIUM list with its most-Pos
     // vicinities first, -2 % per pipelined batch.)
-#ifndef TLC_MH_FRONT_POS
-#define TLC_MH_FRONT_POS 64      /* (96: -0.9 %, 64: -1.2 ... -1.9 %, 48: about the same, 32 and 128: less; two libraries or four in turn) */
-#endif
-    c.mh_front = !mh_split && plain && TLC_MH_FRONT_POS > 0;
-    if (c.mh_front) { sp.mh_min_pos = TLC_MH_FRONT_POS; sp.mh_compact_only = 1; }
+    // (the cut: TLC_MH_FRONT_POS, option mh_front_pos)
+    c.mh_front = !mh_split && plain && g->opt_mh_front_pos > 0;
+    if (c.mh_front) { sp.mh_min_pos = g->opt_mh_front_pos; sp.mh_compact_only = 1; }
     sp.tiny_ok = (g->opt_tiny && plain && vp.flags == 0u && vp.res == 5) ? 1 : 0;      // (plain: images and none of the filtration outputs)
     sp.dcm_count = ws->d_ctl + 44; sp.h_dcm = const_cast<int*>(&ws->h_sync_dev->pub_dcm);
     // (the TINY list by size class as well: d_ctl[48..63] count, zeroed with the control block; the scan's flags start at 64)
@@ -1254,6 +1304,7 @@ static int run_chunk_back(tlc_graph* g, Workspace* ws) {
     // (the many-Pos part of a pipelined chunk's compact MEDIUM list: one launch with the rest, in front of it)
     int n_hi = 0;
     if (c.mh_front) { n_hi = tc[TLC_TIER_MEDHI]; tc[TLC_TIER_MEDIUM] += n_hi; tc[TLC_TIER_MEDHI] = 0; }
+    g->cnt_n_hi += n_hi;
     // (COUNT's writes stand unless the chunk overflowed the arena: then everything is laid out by the scan and written by FILL)
     const bool bumped = bump && ws->h_sync->pub_overflow == 0;
     if (use_x) ws->x_entries_hint = std::max(ws->x_entries_hint, (size_t)std::max<long long>(total - (bumped ? bump_base : 0), 0));
@@ -1270,6 +1321,8 @@ static int run_chunk_back(tlc_graph* g, Workspace* ws) {
         todo = 0;
     }
     const bool spec_done = spec && bumped;          // the MID / MEDIUM tiers are already running
+    if (spec_done)
+        for (int t : {TLC_TIER_MID, TLC_TIER_MEDIUM, TLC_TIER_MEDHI}) g->cnt_beyond_spec += std::max(tc[t] - spec_cap[t], 0);
     ws->prev_tc[TLC_TIER_MID] = tc[TLC_TIER_MID]; ws->prev_tc[TLC_TIER_MEDIUM] = tc[TLC_TIER_MEDIUM]; ws->prev_tc[TLC_TIER_MEDHI] = tc[TLC_TIER_MEDHI];
     ws->prev_tc[TLC_TIER_MEDWIDE] = tc[TLC_TIER_MEDWIDE];
     if (todo > 0) {
@@ -1313,6 +1366,7 @@ static int run_chunk_back(tlc_graph* g, Workspace* ws) {
             pp.wi_base = spec_cap[t]; pp.grid = tc[t] - spec_cap[t]; pp.handoff_cap = spec_cap[t]; pp.phase = 1;
             pp.handoff = ws->handoff + spec_base[t]; pp.handoff_stride = (long long)tlc_handoff_slot_bytes(t);
             pp.abort_flag = nullptr; pp.dc_count = nullptr; pp.dc_list = nullptr;
+            pp.tier_list_hi = nullptr; pp.n_hi = 0;                 // (a chunk on its own has no front list; not left to the order of the launches)
             pp.phase_cycles = g->d_phase ? g->d_phase + 32 * t : nullptr;
             if (((g->opt_tier_mask >> t) & 1) && (rc = tlc_launch_pd_tier(t, pp, s)) != TLC_OK) return rc;
             pp.wi_base = 0; pp.grid = 0; pp.phase = 0; pp.handoff = nullptr; pp.handoff_cap = 0;
@@ -1430,6 +1484,7 @@ static int run_chunk_back(tlc_graph* g, Workspace* ws) {
                 pp.handoff = nullptr; pp.handoff_stride = 0; pp.handoff_cap = 0; pp.grid = 0; pp.phase = 0;
                 pp.tier_count_dev = nullptr; pp.abort_flag = nullptr;
                 pp.dc_count = nullptr; pp.dc_list = nullptr;
+                pp.tier_list_hi = nullptr; pp.n_hi = 0;             // (the MEDIUM launch's front list, if it went first: not the TINY list's)
                 pp.phase_cycles = g->d_phase ? g->d_phase + 32 * TLC_TIER_TINY : nullptr;
                 int r = ((g->opt_tier_mask >> TLC_TIER_TINY) & 1) ? tlc_launch_pd_tiny(pp, ws->side[5]) : TLC_OK;
                 if (r != TLC_OK) return r;
@@ -1481,7 +1536,7 @@ static int run_chunk_back(tlc_graph* g, Workspace* ws) {
         if (used[k]) TLC_HIP_CHECK(hipStreamWaitEvent(s, ws->ev_join[k], 0));
 #undef T0
 #undef T1
-    if (c.call_seq == g->call_seq) account_chunk(g, tc, n_early);      // (a deferred second half submitted by a LATER call does not count into that call's statistics)
+    if (c.call_seq == g->call_seq) { account_chunk(g, tc, n_early); g->last_n_hi += n_hi; }      // (a deferred second half submitted by a LATER call does not count into that call's statistics)
     if (host_trace) {
         static std::chrono::steady_clock::time_point last_end;
         const double gap = (double)std::chrono::duration_cast<std::chrono::nanoseconds>(ht0 - last_end).count() * 1e-3;
@@ -1583,6 +1638,7 @@ static int run_batch(tlc_graph* g, const int32_t* d_pairs, int64_t n_pairs, int 
     TLC_ON_DEVICE(g->device);
     memset(g->last_stats, 0, sizeof(g->last_stats));
     memset(g->last_tc, 0, sizeof(g->last_tc));
+    g->last_n_hi = 0;
     g->acc_tie = 0; g->acc_entries = 0;
     ++g->call_seq;
     for (int k = 0; k < TLC_N_WS; ++k) g->ws[k].in_call = 0;
@@ -1626,6 +1682,12 @@ static int run_batch(tlc_graph* g, const int32_t* d_pairs, int64_t n_pairs, int 
         if (rc != TLC_OK) return fail_batch(g, rc);
         ws->busy = 1; ws->in_call = 1; ws->n_pairs = cnt;
         g->last_ws = ws;
+        {   // (diagnostics: how far chunks overlapped -- host-side bookkeeping only)
+            long long busy = 0;
+            for (int k = 0; k < TLC_N_WS; ++k) busy += g->ws[k].busy ? 1 : 0;
+            g->max_busy = std::max(g->max_busy, busy);
+            g->cnt_deferred += g->pending ? 1 : 0;
+        }
         if ((rc = finish_pending(g)) != TLC_OK) return fail_batch(g, rc);      // the previous chunk's second half (none unless deferred)
         g->pending = ws;
         if (!defer && (rc = finish_pending(g)) != TLC_OK) return fail_batch(g, rc);
@@ -1831,7 +1893,8 @@ extern "C" int tlc_debug_pair_times(tlc_graph* g, unsigned long long* h_out, int
 }
 
 // development / test switches of one handle: "extract" (ball-list extraction, extract.hip), "heavy" (its heavy-row skipping),
-// "tiny" (lane-per-subgraph kernel, pd_tiny.hip); 1 = on (default), 0 = off.  "x_region" / "x_bump_min": arena entries of a
+// "tiny" (lane-per-subgraph kernel, pd_tiny.hip); 1 = on (default), 0 = off.  "mh_front_pos" / "main_beside_early": the runtime
+// form of TLC_MH_FRONT_POS / TLC_MAIN_BESIDE_EARLY (defaults: those constants); "poison": see poison_chunk.  "x_region" / "x_bump_min": arena entries of a
 // workgroup's region / of the bump area behind the regions (tests shrink them to reach the overflow path).  Results must not
 // depend on any of them.
 extern "C" int tlc_debug_set_option(tlc_graph* g, const char* name, int value) {
@@ -1850,6 +1913,9 @@ extern "C" int tlc_debug_set_option(tlc_graph* g, const char* name, int value) {
     else if (!strcmp(name, "timing_every")) { g->opt_timing_every = std::max(value, 1); g->timing_seq = 0; }
     else if (!strcmp(name, "dc_force_fail")) g->opt_dc_force_fail = value != 0;
     else if (!strcmp(name, "x_arena")) { g->opt_x_region = value > 0 ? value : TLC_X_REGION; g->opt_x_bump_min = value > 0 ? value : (1 << 20); }
+    else if (!strcmp(name, "mh_front_pos")) g->opt_mh_front_pos = std::max(value, 0);
+    else if (!strcmp(name, "main_beside_early")) g->opt_main_beside_early = value != 0;
+    else if (!strcmp(name, "poison")) g->opt_poison = value != 0;
     else { tlc_set_error("tlc_debug_set_option: unknown option '%s'", name); return TLC_ERR_INVALID_ARG; }
     return TLC_OK;
 }
@@ -1868,6 +1934,22 @@ extern "C" int tlc_debug_dc_stats(tlc_graph* g, long long* h_out, void* stream) 
     }
     h_out[0] = (long long)v[1];
     h_out[1] = (long long)v[3];
+    return TLC_OK;
+}
+
+// diagnostics (tests): h_out[0 .. min(n, 12)) = front-list vicinities of the last call; since the handle was created: front-list
+// vicinities, pipelined chunks, chunks with the early pass, speculative list positions beyond their reserved slots, poisoned chunks,
+// bytes poisoned; then the bytes the last poisoned chunk filled in the arena's, the early arena's and the SMALL slots' weights; then
+// second halves submitted behind the next chunk's first half, and the most workspaces busy at once (see run_batch)
+extern "C" int tlc_debug_chunk_counters(tlc_graph* g, long long* h_out, int32_t n, void* stream) {
+    TLC_REQUIRE(g && h_out && n >= 0, "null argument");
+    TLC_ON_DEVICE(g->device);
+    { int rc_p = finish_pending(g); if (rc_p != TLC_OK) return rc_p; }
+    TLC_HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
+    const long long v[12] = {g->last_n_hi, g->cnt_n_hi, g->cnt_pipelined, g->cnt_early, g->cnt_beyond_spec, g->cnt_poisoned,
+                             g->cnt_poison_bytes, g->poison_region[0], g->poison_region[1], g->poison_region[2], g->cnt_deferred,
+                             g->max_busy};
+    for (int k = 0; k < n && k < 12; ++k) h_out[k] = v[k];
     return TLC_OK;
 }
 

@@ -100,6 +100,24 @@ class DeviceGraph:
         _lib.check(_lib.lib().tlc_debug_tier_counts(self._h, C.cast(out, C.c_void_p), _lib.stream_ptr(self.device)), "tlc_debug_tier_counts")
         return dict(zip(("small", "medium", "large", "huge", "mid", "tiny", "medium_many_pos", "medium_wide"), (int(v) for v in out)))
 
+    CHUNK_COUNTERS = ("front_list_last_call", "front_list", "pipelined_chunks", "early_chunks", "beyond_spec_slots", "poisoned_chunks",
+                      "poison_bytes", "poison_arena_bytes", "poison_early_bytes", "poison_small_bytes", "deferred_second_halves",
+                      "max_busy_workspaces")
+
+    def chunk_counters(self):
+        """Scheduling counters of the handle (tlc_debug_chunk_counters): the front-list vicinities of the last pd_pi_batch call
+        ('front_list_last_call'), then totals since the handle was created, and the bytes of each region the last poisoned chunk filled
+        (option 'poison'); 'deferred_second_halves' / 'max_busy_workspaces' show how far chunks overlapped (a hop change drains
+        every workspace)."""
+        out = (C.c_longlong * len(self.CHUNK_COUNTERS))()
+        _lib.check(_lib.lib().tlc_debug_chunk_counters(self._h, C.cast(out, C.c_void_p), C.c_int32(len(out)), _lib.stream_ptr(self.device)),
+                   "tlc_debug_chunk_counters")
+        return dict(zip(self.CHUNK_COUNTERS, (int(v) for v in out)))
+
+    def front_list_count(self):
+        """MEDIUM vicinities the last pd_pi_batch call's pipelined chunks put in front of their list (option mh_front_pos)."""
+        return self.chunk_counters()["front_list_last_call"]
+
     # ---- measurement helpers (bench.py) -----------------------------------------------------------------------
     KERNELS = ["vicinity_count", "scan_bin", "vicinity_fill", "pd_tier_small", "pd_tier_medium", "pd_tier_large", "pd_tier_huge",
                "pd_tier_mid"]
