@@ -301,6 +301,34 @@ int tlc_lp_decode_fused_f32(int64_t n_pairs, const int32_t* d_pairs, const float
                             const float* d_pi, int32_t pi_dim, const float* d_W1, const float* d_b1,
                             const float* d_W2, const float* d_b2, float* d_prob, void* stream);
 
+/* ---- The backward of the LP training step (pipelines.py:10-18, loss.backward()) -------------------------------------------
+ * Deterministic like the forward: no atomics, every sum in an order fixed by the shapes, the same inputs give bit-identical
+ * gradients. */
+
+/* A^T of the normalised adjacency of tlc_gcn_norm_csr, as a CSR whose rows are the forward's sources (d(XW) = A^T G runs on
+ * tlc_spmm_csr_f32): the structure of the flipped edge list under the same self-loop rule, targets ascending inside a row, the
+ * forward's values (degrees = the forward rows' in-degrees; edge_index need not be symmetric).  d_rowptr: the forward operator's
+ * row pointers.  d_rowptr_t int32[n_nodes+1]; d_col_t int32[n_edges+n_nodes]; d_val_t f32[n_edges+n_nodes]; d_nnz int32[1].
+ * One-off (allocates, waits for the stream). */
+int tlc_gcn_norm_csr_t(int32_t n_nodes, int64_t n_edges, const int64_t* d_edge_index, const int32_t* d_rowptr,
+                       int32_t* d_rowptr_t, int32_t* d_col_t, float* d_val_t, int32_t* d_nnz, void* stream);
+
+/* C[M,N] = A[K,M]^T @ B[K,N], row-major, fp32 on the f32 MFMA: dW = X^T d(XW) of GCNConv.  Split-K (at most 32 splits) with
+ * the partials added in split order.  d_A NULL with M = 1: C = the column sums of B (bias gradients).  M, N >= 1, K >= 0 (K = 0:
+ * zeros).  d_work float32[32 * M * N] scratch. */
+int tlc_gemm_tn_f32(int32_t M, int32_t N, int64_t K, const float* d_A, const float* d_B, float* d_C, float* d_work, void* stream);
+
+/* Backward of tlc_lp_decode_fused_f32 and of the emb.renorm_(2, 0, 1) in front of it (TLCGNN.py:48-61), emb_dim 16 / pi_dim 25
+ * (else TLC_ERR_UNSUPPORTED).  d_emb_pre f32[n_nodes,16]: the rows before the renorm; d_emb: after it (what the forward read);
+ * d_pi f32[n_pairs,25]; d_gprob f32[n_pairs] = d loss / d prob.  The pair endpoints grouped by node, in the order their
+ * contributions are added: d_node_ptr int32[n_nodes+1], d_node_slots int32[2 n_pairs] (slot 2 i = pair i's first endpoint,
+ * 2 i + 1 its second).  Out: d_gemb f32[n_nodes,16] = d loss / d emb_pre; d_gw f32[1076] = dW1 [25][41] | db1 [25] | dW2 [25] |
+ * db2 [1].  d_work float32[16 n_pairs + 1076 * 512] scratch (16-byte aligned, like d_emb). */
+int tlc_lp_decode_bwd_f32(int64_t n_pairs, const int32_t* d_pairs, const float* d_emb_pre, const float* d_emb, int32_t n_nodes,
+                          int32_t emb_dim, const float* d_pi, int32_t pi_dim, const float* d_W1, const float* d_b1,
+                          const float* d_W2, const float* d_b2, const float* d_gprob, const int32_t* d_node_ptr,
+                          const int32_t* d_node_slots, float* d_gemb, float* d_gw, float* d_work, void* stream);
+
 /* ---- M4-M6: PDGNN layer forward (Knowledge_Distillation/gat_conv.py:113-216) ----------------------
  * One GATConv(heads=1, new_node_feat, use_edge_attn) layer on a block-diagonal batch of graphs whose
  * edges are given as CSR BY TARGET (self loops already added, gat_conv.py:146-160):

@@ -1,8 +1,11 @@
 """Autograd glue for PDGNN training: `loss.backward()` of the reference's training loop
-(Knowledge_Distillation/train_Teacher_Model.py:55-62) through the HIP kernels.
+(Knowledge_Distillation/train_Teacher_Model.py:55-62) through the HIP kernels; and for the TLCGNN link-prediction step
+(pipelines.py:10-18): GcnLayer and LpDecode, used by pipelines.train through Net's private training forward.
 
 torch.autograd only carries the graph: every forward and every backward below is one C-ABI call (`tlc_gat_layer_fwd/_bwd`,
-`tlc_edge_head_fwd/_bwd`, `tlc_w2_partial_matching`, `tlc_pi_raster` / `tlc_pi_raster_wgrad`); nothing is recomputed with torch ops and there is no CPU path.
+`tlc_edge_head_fwd/_bwd`, `tlc_w2_partial_matching`, `tlc_pi_raster` / `tlc_pi_raster_wgrad`) or a few (`tlc_gemm_f32` /
+`tlc_spmm_csr_f32` / `tlc_gemm_tn_f32`, `tlc_lp_decode_fused_f32` / `tlc_lp_decode_bwd_f32`); nothing is recomputed with torch ops
+and there is no CPU path.
 """
 import torch
 
@@ -122,3 +125,63 @@ def diagram_loss(pd_hat, target, order=2, xoff=None, yoff=None, infer=False):
     if yoff is None:
         yoff = torch.tensor([0, target.shape[0]], dtype=torch.int64, device=dev)
     return DiagramLoss.apply(pd_hat, xoff, target, yoff, int(order), bool(infer))
+
+
+class GcnLayer(torch.autograd.Function):
+    """GCNConv.forward of the training path (PD_conv.py:179-188): act(A (X W) + b) with tlc_gemm_f32 / tlc_spmm_csr_f32, the
+    same calls as baselines/TLCGNN.GCNConv.forward.  Backward, G = d loss / d(pre-activation):
+    db = colsum(G), d(XW) = A^T G (tlc_spmm_csr_f32 on the transposed operator), dW = X^T d(XW) (tlc_gemm_tn_f32),
+    dX = d(XW) W^T (tlc_gemm_f32) only when X needs it."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, op, op_t, relu):
+        rowptr, col, val = op
+        xd = x.detach()
+        xw = ops.gemm(xd, weight.detach())
+        out = ops.spmm(rowptr, col, val, xw, bias=bias.detach(), relu=relu)
+        ctx.save_for_backward(xd, weight, out if relu else None)
+        ctx.op_t, ctx.relu = op_t, relu
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        x, weight, out = ctx.saved_tensors
+        g = gout.contiguous()
+        if ctx.relu:
+            g = g.masked_fill(out <= 0, 0.0)                          # ReLU's backward (threshold on the result)
+        rowptr_t, col_t, val_t = ctx.op_t
+        gb = ops.colsum(g)
+        gxw = ops.spmm(rowptr_t, col_t, val_t, g)
+        gw = ops.gemm_tn(x, gxw)
+        gx = ops.gemm(gxw, weight.detach().t().contiguous()) if ctx.needs_input_grad[0] else None
+        return gx, gw, gb, None, None, None
+
+
+class LpDecode(torch.autograd.Function):
+    """Net.decode after the pair selection (TLCGNN.py:48-61) on the PRE-renorm embedding: emb.renorm_(2, 0, 1) (on a copy: the
+    caller's tensor is left alone, autograd saw it) and the fused decode -- the same two calls as Net.decode, so the same
+    probabilities.  Backward: tlc_lp_decode_bwd_f32 -> d emb (through the renorm), dW1, db1, dW, db."""
+
+    @staticmethod
+    def forward(ctx, emb, pairs, pi, w1, b1, w2, b2):
+        pre = emb.detach().contiguous()
+        post = ops.renorm_rows_(pre.clone())
+        prob = ops.lp_decode(pairs, post, pi, w1.detach(), b1.detach(), w2.detach(), b2.detach())
+        ctx.save_for_backward(pre, post, pairs, pi, w1, b1, w2, b2)
+        return prob
+
+    @staticmethod
+    def backward(ctx, gprob):
+        pre, post, pairs, pi, w1, b1, w2, b2 = ctx.saved_tensors
+        pi32 = pi if pi.dtype == torch.float32 else pi.to(torch.float32)   # (the forward's cast on load: same rounding)
+        gemb, gw1, gb1, gw2, gb2 = ops.lp_decode_bwd(pairs, pre, post, pi32, w1.detach(), b1.detach(), w2.detach(), b2.detach(),
+                                                     gprob.contiguous())
+        return gemb, None, None, gw1, gb1, gw2, gb2
+
+
+def gcn_layer(x, weight, bias, op, op_t, relu=False):
+    return GcnLayer.apply(x, weight, bias, op, op_t, bool(relu))
+
+
+def lp_decode(emb, pairs, pi, w1, b1, w2, b2):
+    return LpDecode.apply(emb, pairs, pi, w1, b1, w2, b2)

@@ -7,7 +7,9 @@ GCNConv is third-party in the reference (torch-geometric==1.6.1); its in-tree sp
 Knowledge_Distillation/PD_conv.py:35-70 (gcn_norm) and :146-148,179-188 (weight [in,out] glorot, bias zeros,
 x @ W, add-aggregate at the target, + bias).
 
-Forward only: encode/decode produce the link probabilities; the optimiser loop of pipelines.py is out of scope.
+encode/decode are the forward (eval mode, or train mode under torch.no_grad()); the training step of pipelines.py:10-18 is
+pipelines.train, which runs the same forward through Net's private _encode_train / _decode_train: autograd Functions over the
+same kernels, with the backward in HIP as well (autograd.GcnLayer / autograd.LpDecode, lp_backward.hip).
 """
 import math
 
@@ -39,10 +41,19 @@ class GCNConv(torch.nn.Module):
             self.bias.zero_()
         self._cache = None
 
+    # _cache = (rowptr, col, val, transposed): the forward operator and -- built on the first training step -- its transpose
+    # (rowptr_t, col_t, val_t) for the backward; one entry, so that the two are always dropped together
     def norm_csr(self, edge_index, num_nodes):
         if self._cache is None or not self.cached:
-            self._cache = ops.gcn_norm_csr(edge_index, num_nodes)
-        return self._cache
+            self._cache = ops.gcn_norm_csr(edge_index, num_nodes) + (None,)
+        return self._cache[:3]
+
+    def norm_csr_t(self, edge_index, num_nodes):
+        """(forward operator, transposed operator) for the training step."""
+        op = self.norm_csr(edge_index, num_nodes)
+        if self._cache[3] is None:
+            self._cache = op + (ops.gcn_norm_csr_t(edge_index, num_nodes, op[0]),)
+        return op, self._cache[3]
 
     def forward(self, x, edge_index, relu=False, x_sparse=None):
         """x_sparse: ops.SparseRows of x (the caller keeps it for as long as x does not change): the projection then runs over
@@ -123,9 +134,10 @@ class Net(torch.nn.Module):
         autograd recording; loss.backward()) would fail late, inside backward, with torch's generic "does not require grad".
         Refuse at the first call instead.  train mode under torch.no_grad() (pipelines.train_forward) is fine."""
         if self.training and torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
-            raise RuntimeError("TLCGNN.Net (HIP) is forward only: Net.%s in train mode with autograd enabled would build no graph and "
-                               "loss.backward() would fail -- wrap the forward in torch.no_grad() (pipelines.train_forward) or call "
-                               "model.eval(); the optimiser loop of pipelines.py:10-18 is out of scope (SURVEY.md 8f)" % what)
+            raise RuntimeError("TLCGNN.Net (HIP): Net.%s is forward only -- in train mode with autograd enabled it would build no graph "
+                               "and loss.backward() would fail.  Train with pipelines.train(model, data, optimizer) (the step of "
+                               "pipelines.py:10-18); for the forward alone wrap it in torch.no_grad() (pipelines.train_forward) or "
+                               "call model.eval()" % what)
 
     def encode(self, data):
         # can set p = 0.8 for Cora and Citeseer, the results can be higher   (reference comment, TLCGNN.py:20)
@@ -149,7 +161,16 @@ class Net(torch.nn.Module):
 
     def decode(self, data, emb, type="train"):
         self._forward_only("decode")
-        device = emb.device
+        total_edges, edges_y, PI = self._select(data, emb.device, type)
+        # linear to gather edge features
+        emb = ops.renorm_rows_(emb)                                    # emb.renorm_(2,0,1), in place (:48)
+        prob = ops.lp_decode(total_edges, emb, PI, self.linear_1.weight.detach(), self.linear_1.bias.detach(),
+                             self.linear.weight.detach(), self.linear.bias.detach())
+        return prob, edges_y.float()
+
+    def _select(self, data, device, type):
+        """The pairs, labels and image rows of one split (:29-53) -> (pairs int32 [E,2], labels, PI [E,25] f32 or f64); 'train'
+        draws its negatives with np.random.randint like the reference (:31)."""
         pi_all, pairs_all = self._tables(data, device)
         tp, tn, vp, vn = data.train_pos, data.train_neg, data.val_pos, data.val_neg
         n_all = len(pairs_all) if not isinstance(pairs_all, torch.Tensor) else pairs_all.shape[0]
@@ -170,10 +191,26 @@ class Net(torch.nn.Module):
             total_edges = torch.from_numpy(pairs_all.gather(idx_h).astype(np.int32)).to(device)
             edges_y = torch.from_numpy(pairs_all.labels(idx_h)).to(device)
         PI = pi_all[idx].contiguous() if isinstance(pi_all, torch.Tensor) else pi_all.gather_device(idx)
-        # linear to gather edge features
-        emb = ops.renorm_rows_(emb)                                    # emb.renorm_(2,0,1), in place (:48)
-        prob = ops.lp_decode(total_edges, emb, PI, self.linear_1.weight.detach(), self.linear_1.bias.detach(),
-                             self.linear.weight.detach(), self.linear.bias.detach())
+        return total_edges, edges_y, PI
+
+    # ---- the training forward (pipelines.train only): the train-mode forward of encode / decode('train') as autograd Functions
+    # over the same kernel calls -- the same dropout draws, negatives and probabilities as under torch.no_grad() -- whose backward
+    # runs in HIP too
+    def _encode_train(self, data):
+        from .. import autograd as ag
+        x, edge_index = data.x, data.edge_index
+        op1, op1_t = self.conv1.norm_csr_t(edge_index, x.shape[0])
+        self.conv2._cache = self.conv2._cache or self.conv1._cache            # (one graph: conv2 would build the same operators)
+        op2, op2_t = self.conv2.norm_csr_t(edge_index, x.shape[0])
+        x = F.dropout(x, p=0.5, training=self.training)
+        x = ag.gcn_layer(x, self.conv1.weight, self.conv1.bias, op1, op1_t, relu=False)
+        x = F.dropout(F.relu(x), p=0.5, training=self.training)
+        return ag.gcn_layer(x, self.conv2.weight, self.conv2.bias, op2, op2_t, relu=True)
+
+    def _decode_train(self, data, emb):
+        from .. import autograd as ag
+        total_edges, edges_y, PI = self._select(data, emb.device, "train")
+        prob = ag.lp_decode(emb, total_edges, PI, self.linear_1.weight, self.linear_1.bias, self.linear.weight, self.linear.bias)
         return prob, edges_y.float()
 
 

@@ -4,6 +4,7 @@
 //   tlc_gemm_f32         x @ W on the f32 MFMA (v_mfma_f32_16x16x4_f32), bias/ReLU fused   (PD_conv.py:179-181)
 //   tlc_spmm_csr_f32     propagate = normalised scatter-add at the target, as a row-owned CSR SpMM,
 //                        bias + ReLU fused (PD_conv.py:183-188; message_passing.py:275-293 aggr='add')
+//   tlc_gcn_norm_csr_t   the transposed operator A^T of the backward (lp_backward.hip), same values
 //   tlc_renorm_rows_f32  emb.renorm_(2, 0, 1)                      (TLCGNN.py:48)
 //   tlc_lp_decode_fused  gather, (a-b)^2 || PI, Linear(41->25), LeakyReLU, Linear(25->1), |.|, clamp, Fermi-Dirac
 //                        in one pass per pair                      (TLCGNN.py:52-61)
@@ -1256,6 +1257,53 @@ extern "C" int tlc_csr_by_target(int32_t n_nodes, int64_t n_edges, const int64_t
     TLC_REQUIRE(d_rowptr && d_col && d_nnz && d_work && (n_edges == 0 || d_edge_index), "null pointer");
     const int rc = gcn_csr_launch(n_nodes, n_edges, d_edge_index, d_rowptr, d_col, nullptr, d_nnz, d_work, (hipStream_t)stream);
     if (rc != TLC_OK) tlc_set_error("tlc_csr_by_target: HIP failure");
+    return rc;
+}
+
+// The transposed operator of the backward (d(XW) = A^T G): A^T as a CSR with its own rows = the forward's sources.  A^T's structure
+// is the CSR by target of the flipped edge list -- the same self-loop rule, duplicates kept, sources ascending inside a row -- and
+// its values are the forward's, deg^-1/2[source] * deg^-1/2[target] with the degrees of the FORWARD rows (in-degrees: the two
+// differ when edge_index is not symmetric).
+namespace {
+__global__ void flip_edges_kernel(long long n_edges, const long long* __restrict__ ei, long long* __restrict__ out) {
+    const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= n_edges) return;
+    out[e] = ei[n_edges + e];
+    out[n_edges + e] = ei[e];
+}
+__global__ void gcn_val_t_kernel(int n_nodes, const int* __restrict__ rowptr, const int* __restrict__ rowptr_t, const int* __restrict__ col_t,
+                                 float* __restrict__ val_t) {
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= n_nodes) return;
+    const float dr = 1.0f / sqrtf((float)(rowptr[r + 1] - rowptr[r]));          // r: the source of the forward's entries
+    for (int j = rowptr_t[r]; j < rowptr_t[r + 1]; ++j) {
+        const int c = col_t[j];
+        const float dc = 1.0f / sqrtf((float)(rowptr[c + 1] - rowptr[c]));
+        val_t[j] = dr * 1.0f * dc;                                               // the product gcn_val_kernel forms, same order
+    }
+}
+}  // namespace
+
+extern "C" int tlc_gcn_norm_csr_t(int32_t n_nodes, int64_t n_edges, const int64_t* d_edge_index, const int32_t* d_rowptr,
+                                  int32_t* d_rowptr_t, int32_t* d_col_t, float* d_val_t, int32_t* d_nnz, void* stream) {
+    TLC_REQUIRE(n_nodes > 0 && n_edges >= 0, "bad sizes");
+    TLC_REQUIRE(d_rowptr && d_rowptr_t && d_col_t && d_val_t && d_nnz && (n_edges == 0 || d_edge_index), "null pointer");
+    hipStream_t s = (hipStream_t)stream;
+    int* tmp = nullptr;
+    const size_t tmp_ints = 3 * (size_t)n_nodes + (size_t)n_edges, flip_ints = 4 * (size_t)n_edges;      // (int64 pairs: 4 ints per edge)
+    TLC_HIP_CHECK(hipMalloc(&tmp, (tmp_ints + flip_ints + 2) * sizeof(int)));
+    long long* flip = reinterpret_cast<long long*>(tmp + ((tmp_ints + 1) & ~(size_t)1));
+    if (n_edges) hipLaunchKernelGGL(flip_edges_kernel, dim3((unsigned)((n_edges + 255) / 256)), dim3(256), 0, s, (long long)n_edges,
+                                    (const long long*)d_edge_index, flip);
+    int rc = gcn_csr_launch(n_nodes, n_edges, (const int64_t*)flip, d_rowptr_t, d_col_t, nullptr, d_nnz, tmp, s);
+    if (rc == TLC_OK) {
+        hipLaunchKernelGGL(gcn_val_t_kernel, dim3((n_nodes + 255) / 256), dim3(256), 0, s, n_nodes, (const int*)d_rowptr,
+                           (const int*)d_rowptr_t, (const int*)d_col_t, d_val_t);
+        if (hipGetLastError() != hipSuccess) rc = TLC_ERR_HIP;
+    }
+    hipStreamSynchronize(s);      // one-off, like tlc_gcn_norm_csr: the temporaries must outlive the kernels
+    hipFree(tmp);
+    if (rc != TLC_OK) tlc_set_error("tlc_gcn_norm_csr_t: HIP failure");
     return rc;
 }
 

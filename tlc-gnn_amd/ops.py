@@ -1,7 +1,7 @@
 """Typed wrappers over the LP-forward / PDGNN entry points of the C ABI (include/tlcgnn.h).
 
 torch tensors in, torch tensors out; every call enqueues hand-written HIP kernels on the current stream.
-Forward only (no autograd): the path in scope is the link-prediction FORWARD.
+No autograd here: autograd.py connects the backward entry points (gcn_norm_csr_t, gemm_tn, lp_decode_bwd) to loss.backward().
 """
 import ctypes as C
 
@@ -245,6 +245,95 @@ def lp_decode(pairs, emb, pi, w1, b1, w2, b2, out=None):
             _lib.ptr(_f32(w2).reshape(-1)), _lib.ptr(_f32(b2)), _lib.ptr(out), _lib.stream_ptr())
     _lib.check(rc, "tlc_lp_decode_fused")
     return out
+
+
+# ---- backward of the LP training step (lp_backward.hip; autograd.GcnLayer / autograd.LpDecode) ---------------------------------
+@_lib.on_device_of
+def gcn_norm_csr_t(edge_index, num_nodes, rowptr):
+    """A^T of gcn_norm_csr's operator (rowptr: its row pointers) as CSR by source: (rowptr_t, col_t, val_t) -- what
+    d(XW) = A^T G of the GCN backward runs on with spmm.  Holds for a non-symmetric edge_index too."""
+    torch = _lib.require_gpu()
+    assert edge_index.is_cuda and edge_index.dtype == torch.int64 and edge_index.shape[0] == 2
+    ei = edge_index.contiguous()
+    E, dev = ei.shape[1], ei.device
+    rowptr_t = torch.empty(num_nodes + 1, dtype=torch.int32, device=dev)
+    col_t = torch.empty(E + num_nodes, dtype=torch.int32, device=dev)
+    val_t = torch.empty(E + num_nodes, dtype=torch.float32, device=dev)
+    nnz = torch.zeros(1, dtype=torch.int32, device=dev)
+    rc = _lib.lib().tlc_gcn_norm_csr_t(C.c_int32(num_nodes), C.c_int64(E), _lib.ptr(ei), _lib.ptr(rowptr.contiguous()), _lib.ptr(rowptr_t),
+                                       _lib.ptr(col_t), _lib.ptr(val_t), _lib.ptr(nnz), _lib.stream_ptr())
+    _lib.check(rc, "tlc_gcn_norm_csr_t")
+    k = int(nnz.item())
+    return rowptr_t, col_t[:k].contiguous(), val_t[:k].contiguous()
+
+
+GEMM_TN_MAX_SPLITS = 32          # include/tlcgnn.h: tlc_gemm_tn_f32's scratch is 32 * M * N floats
+
+
+@_lib.on_device_of
+def gemm_tn(a, b, out=None):
+    """C = A^T @ B for A [K,M], B [K,N] float32 CUDA (tlc_gemm_tn_f32: split-K on the f32 MFMA, partials added in a fixed order).
+    a None: the column sums of b as [1,N]."""
+    torch = _lib.require_gpu()
+    b = _f32(b)
+    K, N = b.shape
+    if a is not None:
+        a = _f32(a)
+        assert a.shape[0] == K
+        M = a.shape[1]
+    else:
+        M = 1
+    if out is None:
+        out = torch.empty((M, N), dtype=torch.float32, device=b.device)
+    work = torch.empty(GEMM_TN_MAX_SPLITS * M * N, dtype=torch.float32, device=b.device)
+    rc = _lib.lib().tlc_gemm_tn_f32(C.c_int32(M), C.c_int32(N), C.c_int64(K), _lib.ptr(a), _lib.ptr(b), _lib.ptr(out), _lib.ptr(work),
+                                    _lib.stream_ptr())
+    _lib.check(rc, "tlc_gemm_tn_f32")
+    return out
+
+
+def colsum(b):
+    """Column sums of b [K,N] -> [N] (the bias gradient of a layer), tlc_gemm_tn_f32 with a column of ones."""
+    return gemm_tn(None, b).reshape(-1)
+
+
+LP_DECODE_BWD_WG = 512           # include/tlcgnn.h: tlc_lp_decode_bwd_f32's scratch is 16 n_pairs + 1076 * 512 floats
+
+
+def endpoint_groups(pairs, num_nodes):
+    """The endpoints of `pairs` [E,2] grouped by node, in slot order (slot 2 i / 2 i + 1 = pair i's first / second endpoint):
+    (node_ptr int32[N+1], slots int32[2E]).  A sort on unique keys (node * 2E + slot): the order is fixed by the pairs alone."""
+    import torch
+    flat = pairs.reshape(-1).to(torch.int64)
+    n2 = flat.numel()
+    keys = flat * max(n2, 1) + torch.arange(n2, device=flat.device)
+    sk, _ = torch.sort(keys)
+    nodes = torch.div(sk, max(n2, 1), rounding_mode="floor")
+    slots = (sk - nodes * max(n2, 1)).to(torch.int32)
+    node_ptr = torch.searchsorted(nodes, torch.arange(num_nodes + 1, device=flat.device)).to(torch.int32)
+    return node_ptr, slots.contiguous()
+
+
+@_lib.on_device_of
+def lp_decode_bwd(pairs, emb_pre, emb, pi, w1, b1, w2, b2, gprob, groups=None):
+    """Backward of renorm_rows_ + lp_decode (tlc_lp_decode_bwd_f32).  pairs int32 [E,2]; emb_pre f32 [N,16] (before the renorm), emb
+    (after it); pi f32 [E,25]; gprob f32 [E] -> (d emb_pre [N,16], dW1 [25,41], db1 [25], dW2 [1,25], db2 [1])."""
+    torch = _lib.require_gpu()
+    assert pairs.dtype == torch.int32 and pi.dtype == torch.float32
+    E, n = pairs.shape[0], emb_pre.shape[0]
+    dev = emb_pre.device
+    node_ptr, slots = endpoint_groups(pairs, n) if groups is None else groups
+    gemb = torch.empty((n, emb_pre.shape[1]), dtype=torch.float32, device=dev)
+    gw = torch.empty(1076, dtype=torch.float32, device=dev)
+    work = torch.empty(16 * E + 1076 * LP_DECODE_BWD_WG, dtype=torch.float32, device=dev)
+    pairs_c = pairs.contiguous()
+    rc = _lib.lib().tlc_lp_decode_bwd_f32(C.c_int64(E), _lib.ptr(pairs_c), _lib.ptr(_f32(emb_pre)), _lib.ptr(_f32(emb)), C.c_int32(n),
+                                          C.c_int32(emb_pre.shape[1]), _lib.ptr(pi.contiguous()), C.c_int32(pi.shape[1]),
+                                          _lib.ptr(_f32(w1)), _lib.ptr(_f32(b1)), _lib.ptr(_f32(w2).reshape(-1)), _lib.ptr(_f32(b2)),
+                                          _lib.ptr(_f32(gprob)), _lib.ptr(node_ptr), _lib.ptr(slots), _lib.ptr(gemb), _lib.ptr(gw),
+                                          _lib.ptr(work), _lib.stream_ptr())
+    _lib.check(rc, "tlc_lp_decode_bwd_f32")
+    return gemb, gw[:1025].view(25, 41), gw[1025:1050], gw[1050:1075].view(1, 25), gw[1075:1076]
 
 
 @_lib.on_device_of
