@@ -329,6 +329,35 @@ int tlc_lp_decode_bwd_f32(int64_t n_pairs, const int32_t* d_pairs, const float* 
                           const float* d_W2, const float* d_b2, const float* d_gprob, const int32_t* d_node_ptr,
                           const int32_t* d_node_slots, float* d_gemb, float* d_gw, float* d_work, void* stream);
 
+/* ---- Link-prediction scoring (pipelines.py:20-40: roc_auc_score / average_precision_score) ----------------------------------
+ * Binary ranking metrics per segment, with sklearn's binary semantics (pos_label 1): scores in descending order, equal scores one
+ * threshold, -0.0 == +0.0.  AUC = U2 / (2 P N) with one rounding, U2 = sum over tie groups g of p_g (2 N_below,g + n_g) exact in
+ * int64; AP = sum_g (p_g / P) tp_g / (tp_g + fp_g) in f64 (tp / fp cumulative through g).  Deterministic: no floating-point
+ * atomics; a segment gives the same bits alone or among others.
+ *   d_scores: TLC_SCORE_F32 / TLC_SCORE_F64; d_labels: TLC_LABEL_U8 (also bool) / TLC_LABEL_I64 / TLC_LABEL_F32, each 0 or 1.
+ *   h_seg_ptr int64[n_segs + 1] (HOST): segment s = [h_seg_ptr[s], h_seg_ptr[s+1]) of both arrays; n_segs >= 1, h_seg_ptr[0] >= 0,
+ *   non-decreasing (else TLC_ERR_INVALID_ARG); a segment of 2^31 scores or more: TLC_ERR_UNSUPPORTED.
+ *   Out, per segment (device): d_auc / d_ap f64, d_n_pos / d_n_neg int64, d_status int32 (TLC_RANK_* bits, 0 = valid).  One class
+ *   only: AUC NaN, AP 0.0 without positives / 1.0 without negatives (sklearn 1.7).  An empty segment: NaN / NaN, TLC_RANK_EMPTY.
+ *   Segments of at most TLC_RANK_LDS_CAP scores are sorted in LDS, one workgroup each, all in one launch (per 64); longer ones by
+ *   a multi-workgroup radix sort, one after the other in d_work: tlc_binary_rank_metrics_work_bytes() bytes (0 if no segment
+ *   takes the radix tier, -1 for invalid arguments), 16-byte aligned.  TLC_RANK_FORCE_RADIX (tests): every non-empty segment
+ *   through the radix tier.  Asynchronous on `stream`, no host synchronisation. */
+#define TLC_SCORE_F32          0
+#define TLC_SCORE_F64          1
+#define TLC_LABEL_U8           0
+#define TLC_LABEL_I64          1
+#define TLC_LABEL_F32          2
+#define TLC_RANK_FORCE_RADIX   0x1u
+#define TLC_RANK_NONFINITE     0x1   /* a NaN or +-inf score      */
+#define TLC_RANK_BAD_LABEL     0x2   /* a label other than 0 / 1  */
+#define TLC_RANK_EMPTY         0x4   /* the segment has no scores */
+#define TLC_RANK_LDS_CAP       16384 /* 9 B per score (u64 key + label) in the 160 KiB of LDS of one gfx950 workgroup, a power of 2 */
+int64_t tlc_binary_rank_metrics_work_bytes(const int64_t* h_seg_ptr, int32_t n_segs, int score_dtype, uint32_t flags);
+int tlc_binary_rank_metrics(const void* d_scores, int score_dtype, const void* d_labels, int label_dtype, const int64_t* h_seg_ptr,
+                            int32_t n_segs, uint32_t flags, double* d_auc, double* d_ap, int64_t* d_n_pos, int64_t* d_n_neg,
+                            int32_t* d_status, void* d_work, int64_t work_bytes, void* stream);
+
 /* ---- M4-M6: PDGNN layer forward (Knowledge_Distillation/gat_conv.py:113-216) ----------------------
  * One GATConv(heads=1, new_node_feat, use_edge_attn) layer on a block-diagonal batch of graphs whose
  * edges are given as CSR BY TARGET (self loops already added, gat_conv.py:146-160):

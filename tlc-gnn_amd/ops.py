@@ -336,6 +336,71 @@ def lp_decode_bwd(pairs, emb_pre, emb, pi, w1, b1, w2, b2, gprob, groups=None):
     return gemb, gw[:1025].view(25, 41), gw[1025:1050], gw[1050:1075].view(1, 25), gw[1075:1076]
 
 
+# ---- link-prediction scoring (lp_metrics.hip; metrics.py, pipelines.test(metrics="device")) -----------------------------------
+RANK_LDS_CAP = 16384             # include/tlcgnn.h TLC_RANK_LDS_CAP: longer segments take the radix tier
+RANK_FORCE_RADIX = 0x1
+RANK_NONFINITE, RANK_BAD_LABEL, RANK_EMPTY = 0x1, 0x2, 0x4
+
+
+def _rank_dtypes(scores, labels):
+    import torch
+    sdt = {torch.float32: 0, torch.float64: 1}.get(scores.dtype)
+    if sdt is None:
+        raise TypeError("binary_rank_metrics: scores must be float32 or float64, not %s" % scores.dtype)
+    if labels.dtype == torch.bool:
+        labels = labels.view(torch.uint8)
+    ldt = {torch.uint8: 0, torch.int64: 1, torch.float32: 2}.get(labels.dtype)
+    if ldt is None:
+        raise TypeError("binary_rank_metrics: labels must be bool, uint8, int64 or float32, not %s" % labels.dtype)
+    return sdt, labels, ldt
+
+
+@_lib.on_device_of
+def binary_rank_metrics(scores, labels, seg_ptr=None, force_radix=False):
+    """ROC-AUC and average precision per segment (tlc_binary_rank_metrics, sklearn's binary semantics with pos_label 1).
+
+    scores: 1-D float32 / float64 CUDA; labels: 1-D bool / uint8 / int64 / float32 CUDA of the same length, 0 or 1.
+    seg_ptr: host offsets [S+1] (a list, numpy array or CPU tensor; None: one segment of everything).  Enqueued on the current
+    stream, workspace from torch's allocator, no host synchronisation: returns device tensors (auc f64 [S], ap f64 [S],
+    n_pos int64 [S], n_neg int64 [S], status int32 [S]) -- status bits RANK_NONFINITE / RANK_BAD_LABEL / RANK_EMPTY, 0 = valid.
+    force_radix: every non-empty segment through the multi-workgroup radix tier (tests compare the two tiers)."""
+    import numpy as np
+    torch = _lib.require_gpu()
+    assert scores.is_cuda and labels.is_cuda and scores.device == labels.device, "scores and labels must be on one CUDA device"
+    scores, labels = scores.reshape(-1).contiguous(), labels.reshape(-1).contiguous()
+    if scores.numel() != labels.numel():
+        raise ValueError("binary_rank_metrics: %d scores but %d labels" % (scores.numel(), labels.numel()))
+    sdt, labels, ldt = _rank_dtypes(scores, labels)
+    if seg_ptr is None:
+        seg_ptr = [0, scores.numel()]
+    if isinstance(seg_ptr, torch.Tensor):
+        if seg_ptr.is_cuda:
+            raise TypeError("binary_rank_metrics: seg_ptr is read on the host; pass it as a list or CPU tensor")
+        seg_ptr = seg_ptr.numpy()
+    sp = np.ascontiguousarray(np.asarray(seg_ptr, dtype=np.int64))
+    if sp.ndim != 1 or sp.size < 2:
+        raise ValueError("binary_rank_metrics: seg_ptr needs S + 1 >= 2 offsets")
+    if sp[-1] > scores.numel():
+        raise ValueError("binary_rank_metrics: seg_ptr ends at %d, past the %d scores" % (sp[-1], scores.numel()))
+    S = sp.size - 1
+    flags = RANK_FORCE_RADIX if force_radix else 0
+    L = _lib.lib()
+    hp = sp.ctypes.data_as(C.c_void_p)
+    nbytes = int(L.tlc_binary_rank_metrics_work_bytes(hp, C.c_int32(S), C.c_int(sdt), C.c_uint32(flags)))
+    if nbytes < 0:
+        raise ValueError("binary_rank_metrics: malformed seg_ptr (must start at >= 0 and be non-decreasing)")
+    dev = scores.device
+    work = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+    f64 = torch.empty(2 * S, dtype=torch.float64, device=dev)
+    i64 = torch.empty(2 * S, dtype=torch.int64, device=dev)
+    status = torch.empty(S, dtype=torch.int32, device=dev)
+    rc = L.tlc_binary_rank_metrics(_lib.ptr(scores), C.c_int(sdt), _lib.ptr(labels), C.c_int(ldt), hp, C.c_int32(S), C.c_uint32(flags),
+                                   _lib.ptr(f64), _lib.ptr(f64[S:]), _lib.ptr(i64), _lib.ptr(i64[S:]), _lib.ptr(status), _lib.ptr(work),
+                                   C.c_int64(nbytes), _lib.stream_ptr())
+    _lib.check(rc, "tlc_binary_rank_metrics")
+    return f64[:S], f64[S:], i64[:S], i64[S:], status
+
+
 @_lib.on_device_of
 def gat_layer(rowptr, src, x, wl, att, wij, bias, prelu_slope=-1.0, out=None):
     """One PDGNN layer (Knowledge_Distillation/gat_conv.py:113-216) on a CSR-by-target batch."""

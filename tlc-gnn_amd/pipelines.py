@@ -6,7 +6,8 @@
 The reference's `train()` / `test()` are closures over the module-level `model`, `data`, `optimizer`; here they take them as
 arguments.  Everything between the arguments and the returned numbers is the reference's: encode once, decode per split,
 binary cross-entropy, roc_auc_score / average_precision_score on the host.  The forward itself runs on the HIP kernels behind
-baselines/TLCGNN.py (Net.encode / Net.decode)."""
+baselines/TLCGNN.py (Net.encode / Net.decode).  test(..., metrics="device") / fit(..., metrics="device") score the splits on the
+device instead (metrics.py, csrc/lp_metrics.hip); the default stays the reference's sklearn path."""
 import numpy as np
 import torch
 import torch.nn.functional as F
@@ -53,17 +54,17 @@ def train(model, data, optimizer):
     return x
 
 
-def fit(model, data, optimizer, total_epochs=2000, wait_total=200):
+def fit(model, data, optimizer, total_epochs=2000, wait_total=200, metrics="sklearn"):
     """The epoch loop of :111-126: train, then test; the test numbers of the best validation ROC-AUC (>=) are kept, and the loop
     stops after `wait_total` epochs without a better one -> (test_acc, test_roc, best_val_acc, best_val_roc, best_val_loss)
-    (acc = average precision, as the reference names it)."""
+    (acc = average precision, as the reference names it).  metrics: passed to test()."""
     best_val_acc = test_acc = 0.0
     best_val_roc = test_roc = 0.0
     best_val_loss = np.inf
     wait_step = 0
     for epoch in range(1, total_epochs + 1):
         train(model, data, optimizer)
-        val_loss, val_roc, val_acc, tmp_test_roc, tmp_test_acc = test(model, data)
+        val_loss, val_roc, val_acc, tmp_test_roc, tmp_test_acc = test(model, data, metrics=metrics)
         if val_roc >= best_val_roc:
             test_acc, test_roc = tmp_test_acc, tmp_test_roc
             best_val_acc, best_val_roc, best_val_loss = val_acc, val_roc, val_loss
@@ -75,8 +76,16 @@ def fit(model, data, optimizer, total_epochs=2000, wait_total=200):
     return test_acc, test_roc, best_val_acc, best_val_roc, best_val_loss
 
 
-def test(model, data):
-    """:20-40 -> [val BCE, val ROC-AUC, val AP, test ROC-AUC, test AP]."""
+def test(model, data, metrics="sklearn"):
+    """:20-40 -> [val BCE, val ROC-AUC, val AP, test ROC-AUC, test AP].
+
+    metrics="sklearn" (default): the reference's path, predictions copied to the host, BCE on the CPU, sklearn's scores.
+    metrics="device": both splits scored by one tlc_binary_rank_metrics call (two segments), the val BCE on the device, then one
+    copy of the five numbers to the host.  Same list, order and types (a 0-dim float32 CPU tensor, then four floats)."""
+    if metrics == "device":
+        return _test_device(model, data)
+    if metrics != "sklearn":
+        raise ValueError("metrics must be 'sklearn' or 'device', not %r" % (metrics,))
     from sklearn.metrics import roc_auc_score, average_precision_score
     model.eval()
     accs = []
@@ -91,3 +100,23 @@ def test(model, data):
             accs.append(roc_auc_score(y, pred))
             accs.append(average_precision_score(y, pred))
     return accs
+
+
+def _test_device(model, data):
+    from . import metrics, ops
+    model.eval()
+    with torch.no_grad():
+        emb = model.encode(data)
+        pv, yv = model.decode(data, emb, type="val")
+        pt, yt = model.decode(data, emb, type="test")
+        yv, yt = yv.to(pv.device), yt.to(pt.device)
+        nv, nt = pv.numel(), pt.numel()
+        auc, ap, n_pos, n_neg, status = ops.binary_rank_metrics(torch.cat([pv, pt]), torch.cat([yv, yt]), [0, nv, nv + nt])
+        bce = F.binary_cross_entropy(pv, yv)
+        # one copy to the host; the f32 BCE, the counts (< 2^31) and the status words are exact in float64
+        v = torch.cat([bce.double().reshape(1), auc, ap, n_pos.double(), n_neg.double(), status.double()]).cpu()
+    h = v.tolist()            # [bce, auc val, auc test, ap val, ap test, n_pos val, test, n_neg val, test, status val, test]
+    for s, what in enumerate(["val", "test"]):
+        metrics.check_status(int(h[9 + s]), "pipelines.test: %s split" % what)
+        metrics.warn_single_class(int(h[5 + s]), int(h[7 + s]))
+    return [v[0].float(), h[1], h[3], h[2], h[4]]
