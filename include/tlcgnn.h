@@ -181,9 +181,9 @@ int tlc_pd_pi_algorithmic_bytes(int32_t n_nodes, const int32_t* h_rowptr, const 
  *   "n_ws"         workspaces taken in turn by pipelined chunks (2..4, default 3)
  *   "timing_every" kernel events on every n-th chunk only
  *   "mh_front_pos" pipelined plain chunks: compact MEDIUM vicinities with at least this many Pos edges go in front of their list
- *                  (default TLC_MH_FRONT_POS = 64; 0: no front list)
+ *                  (default 64; 0: no front list)
  *   "main_beside_early" pipelined chunks: the general extraction waits for the classification only and runs beside the early pass
- *                  (default 1 = TLC_MAIN_BESIDE_EARLY; 0: it waits for the whole early pass, as a chunk on its own does)
+ *                  (default 1; 0: it waits for the whole early pass, as a chunk on its own does)
  *   "poison"       test hook: each chunk fills its workspace's float64 payload scratch with 7.25 before its first kernel (default 0)
  * An unknown name is TLC_ERR_INVALID_ARG. */
 int tlc_debug_set_option(tlc_graph* g, const char* name, int value);

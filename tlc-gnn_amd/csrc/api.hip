@@ -63,13 +63,6 @@ struct HostSync {
     volatile unsigned pub_seq;
 };
 
-// defaults of options mh_front_pos / main_beside_early (front_main_scan / front_join_early say what they do and what was measured)
-#ifndef TLC_MH_FRONT_POS
-#define TLC_MH_FRONT_POS 64      /* (96: -0.9 %, 64: -1.2 ... -1.9 %, 48: about the same, 32 and 128: less; two libraries or four in turn) */
-#endif
-#ifndef TLC_MAIN_BESIDE_EARLY
-#define TLC_MAIN_BESIDE_EARLY 1
-#endif
 // option poison: the sentinel a chunk's payload scratch is filled with (finite, outside [0, 1], where every filtration value lies)
 #define TLC_POISON 7.25
 
@@ -563,7 +556,9 @@ extern "C" int tlc_graph_create(int32_t n_nodes, const int32_t* h_rowptr, const 
     g->opt_plain_kernels = env_on("TLC_PLAIN_KERNELS") ? 1 : 0;
     g->opt_n_ws = 3;
     g->opt_x_region = TLC_X_REGION; g->opt_x_bump_min = 1 << 20; g->opt_tier_mask = (1 << TLC_N_TIERS) - 1; g->opt_timing_every = 1;
-    g->opt_mh_front_pos = TLC_MH_FRONT_POS; g->opt_main_beside_early = TLC_MAIN_BESIDE_EARLY;
+    // (front_main_scan / front_join_early say what these two do; front list cut measured at 96: -0.9 %, 64: -1.2 ... -1.9 %,
+    // 48: about the same, 32 and 128: less)
+    g->opt_mh_front_pos = 64; g->opt_main_beside_early = 1;
     int rc = TLC_OK;
     auto fail = [&](int code) { tlc_graph_destroy(g); return code; };
 #define CK(e) do { if ((e) != hipSuccess) { tlc_set_error("%s failed: %s", #e, hipGetErrorString(hipGetLastError())); return fail(TLC_ERR_HIP); } } while (0)
@@ -586,9 +581,9 @@ extern "C" int tlc_graph_create(int32_t n_nodes, const int32_t* h_rowptr, const 
     //                  side[2], side[7] MEDWIDE (normal), side[1] the heavy tiers the early pass did not take (high).
     // (MEDWIDE, pipelined chunks only: on MEDIUM's stream the few hundred largest MEDIUM-sized vicinities of a batch, 0.38 ms of
     // tier + swap kernel, ran in front of the MEDIUM chain instead of beside it.  A fifth stream of normal priority shares a
-    // queue with another one; in-process A/B, tools/gpu_env_ab3.sh TLC_MEDWIDE_PRIO=0|1|2: 0.683 / 0.651 / 0.703 ms per pipelined
+    // queue with another one; measured with MEDWIDE in the low / normal / high pool: 0.683 / 0.651 / 0.703 ms per pipelined
     // batch -- as the fourth stream of the low pool it starts too late, in the high pool it delays the early chains.
-    // TINY or SMALL in the normal pool (TLC_TINY_PRIO / TLC_SMALL_PRIO = 1): 0.81 / 0.75 ms.  More hardware queues for the runtime
+    // TINY or SMALL in the normal pool: 0.81 / 0.75 ms.  More hardware queues for the runtime
     // (GPU_MAX_HW_QUEUES=6 / 8, its environment variable; 4 is the default this layout was tuned for): 0.69 ms; 2: 0.95 ms.)
     // Normal priority then holds the caller's stream, the two main streams and MEDIUM: four.  With MID there as well (round 2)
     // the second workspace's main stream shared a hardware queue with the MID chain, and the lead-in of every other pipelined
@@ -637,10 +632,7 @@ extern "C" int tlc_graph_create(int32_t n_nodes, const int32_t* h_rowptr, const 
             }
             else if (k == 2) ws->side[k] = nullptr;                      // (= side[6], set below)
             else {
-                int pr = k == 1 ? prio_hi : ((k == 6 || k == 7) ? prio_mid : prio_lo);
-                // (development A/B, tools/gpu_prio_ab.sh: 0 low, 1 normal, 2 high)
-                const char* ev = k == 3 ? getenv("TLC_MID_PRIO") : (k == 6 ? getenv("TLC_MEDIUM_PRIO") : (k == 7 ? getenv("TLC_MEDWIDE_PRIO") : (k == 5 ? getenv("TLC_TINY_PRIO") : (k == 0 ? getenv("TLC_SMALL_PRIO") : nullptr))));
-                if (ev) pr = atoi(ev) == 0 ? prio_lo : (atoi(ev) == 1 ? prio_mid : prio_hi);
+                const int pr = k == 1 ? prio_hi : ((k == 6 || k == 7) ? prio_mid : prio_lo);
                 CK(hipStreamCreateWithPriority(&ws->side[k], hipStreamNonBlocking, pr));
             }
             CK(hipEventCreateWithFlags(&ws->ev_join[k], hipEventDisableTiming));
@@ -1048,15 +1040,10 @@ static int front_join_early(tlc_graph* g, Workspace* ws) {
         else TLC_HIP_CHECK(hipStreamWaitEvent(s, ws->ev_early, 0));
         // (Round 6: no gate for a pipelined chunk.  With other chunks' tier kernels on every CU the LARGE workgroups are never resident
         // within the bound, so the gate was a 50 us wait -- and a kernel of its own -- in the middle of every first half: in-region timeline
-        // profiles/r06_queue_occupancy.txt.  Two libraries in turn, three rounds: 0.5048 -> 0.4930 ms per pipelined batch (-2.3 %).
-        // -DTLC_GATE_PIPELINED=5000: as before.)
-#ifndef TLC_GATE_PIPELINED
-#define TLC_GATE_PIPELINED 0
-#endif
-        const long long gate = c.pipelined ? (long long)TLC_GATE_PIPELINED : 5000ll;   // 10 ns ticks
-        if (gate > 0)
+        // profiles/r06_queue_occupancy.txt.  Two libraries in turn, three rounds: 0.5048 -> 0.4930 ms per pipelined batch (-2.3 %).)
+        if (!c.pipelined)
             hipLaunchKernelGGL(tlc_wait_started_dev, dim3(1), dim3(TLC_WAVE), 0, s, (const int*)d_early_started, (const int*)d_early_count,
-                               192, gate);
+                               192, 5000ll);                                // 10 ns ticks
         TLC_HIP_CHECK(hipGetLastError());
     }
     return TLC_OK;
@@ -1077,7 +1064,7 @@ static int front_main_scan(tlc_graph* g, Workspace* ws) {
     vp.work_counter = ws->d_ctl + 64 + TLC_SCAN_MAX_BLOCKS + 8;         // TLC_X_COUNTERS (8) counters, 64 ints apart, behind the statistics
     // (about one chunk per RESIDENT extraction wavefront -- 16 per CU, 4 096 -- when batches are pipelined: the machine is full of
     // other chunks' kernels then and the extraction's own tail costs nothing; twice as many for a lone batch.  In-process A/B,
-    // tools/gpu_chunk_ab.sh, x_chunk_div 4096 against 8192 / 16384 / 32768: pipelined batch +0.4 / +2.2 / +2.7 %, latency of one
+    // x_chunk_div 4096 against 8192 / 16384 / 32768: pipelined batch +0.4 / +2.2 / +2.7 %, latency of one
     // batch -1.9 / -1.1 / -1.7 %.  Half as many leaves half of the machine without a first chunk: +6 %)
     vp.work_chunk = std::max(2, n_pairs / (pipelined ? 4096 : 8192));
     // (behind a FAST launch the work list is the two top bins only -- a few thousand pairs of 20 - 80 us: one pair per chunk)
@@ -1120,7 +1107,7 @@ static int front_main_scan(tlc_graph* g, Workspace* ws) {
     // but to stand in FRONT of the compact MEDIUM launch (TlcPdParams::tier_list_hi): the swap kernel ends most batches and lasts as long as
     // its longest walk plus the time that walk's wavefront waited to be placed.  tools/order_probe.py: the MEDIUM list with its most-Pos
     // vicinities first, -2 % per pipelined batch.)
-    // (the cut: TLC_MH_FRONT_POS, option mh_front_pos)
+    // (the cut: option mh_front_pos)
     c.mh_front = !mh_split && plain && g->opt_mh_front_pos > 0;
     if (c.mh_front) { sp.mh_min_pos = g->opt_mh_front_pos; sp.mh_compact_only = 1; }
     sp.tiny_ok = (g->opt_tiny && plain && vp.flags == 0u && vp.res == 5) ? 1 : 0;      // (plain: images and none of the filtration outputs)
@@ -1893,8 +1880,8 @@ extern "C" int tlc_debug_pair_times(tlc_graph* g, unsigned long long* h_out, int
 }
 
 // development / test switches of one handle: "extract" (ball-list extraction, extract.hip), "heavy" (its heavy-row skipping),
-// "tiny" (lane-per-subgraph kernel, pd_tiny.hip); 1 = on (default), 0 = off.  "mh_front_pos" / "main_beside_early": the runtime
-// form of TLC_MH_FRONT_POS / TLC_MAIN_BESIDE_EARLY (defaults: those constants); "poison": see poison_chunk.  "x_region" / "x_bump_min": arena entries of a
+// "tiny" (lane-per-subgraph kernel, pd_tiny.hip); 1 = on (default), 0 = off.  "mh_front_pos" / "main_beside_early": the front
+// list's cut and the general launch beside the early pass (defaults 64 and 1, tlc_graph_create); "poison": see poison_chunk.  "x_region" / "x_bump_min": arena entries of a
 // workgroup's region / of the bump area behind the regions (tests shrink them to reach the overflow path).  Results must not
 // depend on any of them.
 extern "C" int tlc_debug_set_option(tlc_graph* g, const char* name, int value) {

@@ -19,7 +19,7 @@
 // the last bits) some query ends without its edge: the stage reports failure and the caller runs the serial walk.
 #pragma once
 
-#ifndef TLC_DC_MIN_POS             /* (overridable for the threshold sweep: tools/gpu_threshold_sweep.sh) */
+#ifndef TLC_DC_MIN_POS             /* (overridable for a threshold sweep: make EXTRA=-DTLC_DC_MIN_POS=n) */
 #define TLC_DC_MIN_POS 160          /* below this many Pos edges the serial walk wins (a workgroup with a CU to itself) */
 #endif
 /* 256-thread tiers (MEDIUM): measured on the PubMed batch, a level costs ~30k cycles there as well (phases of two or three
@@ -28,9 +28,6 @@
  * longer, not shorter.  Only the sizes the tier cannot reach in this batch take it. */
 #ifndef TLC_DC_MIN_POS_SHARED
 #define TLC_DC_MIN_POS_SHARED 320
-#endif
-#ifndef TLC_DC_LARGE_MODE
-#define TLC_DC_LARGE_MODE 2          /* LARGE tier: 1 = in the tier kernel, 2 = hand the subgraph to tlc_pd_dc_kernel */
 #endif
 #define TLC_DC_MAX_TIE_RUN 64       /* longer runs of equal descending keys: no fix-up, serial walk */
 

@@ -40,9 +40,7 @@ struct XCfg {
 };
 
 #define TLC_X_UNITS (1024 + TLC_X_H_CAP * TLC_X_H_CAP / 64)    /* units of a sweep: 64-member batches + 64-pair heavy chunks */
-#ifndef TLC_X_STAGE
-#define TLC_X_STAGE 128       /* entries a wavefront stages in LDS before it writes them out in order (0: every lane stores its own) */
-#endif
+constexpr int X_STAGE = 128;          // entries a wavefront stages in LDS before it writes them out in order
 struct XLayout {
     size_t o_pref, o_sid, o_hvy, o_hl, o_ctl, o_ucnt, o_stage, o_mt, total;
 };
@@ -69,7 +67,7 @@ __host__ __device__ __forceinline__ constexpr XLayout x_layout(int nw, int sid_c
     L.o_ctl = L.o_hl + (size_t)TLC_X_H_CAP * 4;
     L.o_ucnt = L.o_ctl + 64 + (size_t)(bw / 64) * 4 + 16;
     L.o_stage = (L.o_ucnt + (bw > 64 ? (size_t)TLC_X_UNITS * 4 : 0) + 15) & ~(size_t)15;
-    L.o_mt = L.o_stage + (size_t)(bw / 64) * TLC_X_STAGE * 12;       // per wavefront: [TLC_X_STAGE doubles | TLC_X_STAGE words]
+    L.o_mt = L.o_stage + (size_t)(bw / 64) * X_STAGE * 12;       // per wavefront: [X_STAGE doubles | X_STAGE words]
     L.total = L.o_mt + TLC_X_MT_BYTES;
     return L;
 }
@@ -133,13 +131,9 @@ __device__ __forceinline__ void x_sync() {
 // arena entries: ordinary stores.  (Nontemporal stores -- the entries are written once and read once, by another kernel, and
 // 37 MB of them per batch pass through a 4 MB L2 beside the graph's 6 MB of lists and rows -- were measured: same kernel time,
 // but WRITE_SIZE 142 MB instead of 51 MB per batch: the partial lines a wavefront's few entries make are not merged on the way
-// out.  make X_NT=1 brings them back for an A/B.)
+// out.)
 template <typename T>
-#ifdef TLC_X_NT_STORE
-__device__ __forceinline__ void x_store(T* p, T v) { __builtin_nontemporal_store(v, p); }
-#else
 __device__ __forceinline__ void x_store(T* p, T v) { *p = v; }
-#endif
 __device__ __forceinline__ bool x_heavy(const XState& X, int ly) { return (X.hvy[ly >> 5] >> (ly & 31)) & 1u; }
 
 // One sweep over the rows of the members ids[0..n): every directed entry of the induced subgraph exactly once, as
@@ -172,11 +166,11 @@ __device__ __forceinline__ int x_sweep_wave(const PB& p, const int* ids, int n, 
     // entries of the short-row rounds go to an LDS buffer at their entry number and leave it in order, 64 consecutive entries per
     // store.  [st_fb, st_fb + st_fill) are the entry numbers the buffer holds; the dense paths (long rows, heavy pairs) number
     // their entries by ballot already and store directly.
-    double* const st_w = reinterpret_cast<double*>(X.stage + (size_t)wv * TLC_X_STAGE * 12);
-    unsigned* const st_d = reinterpret_cast<unsigned*>(st_w + TLC_X_STAGE);
+    double* const st_w = reinterpret_cast<double*>(X.stage + (size_t)wv * X_STAGE * 12);
+    unsigned* const st_d = reinterpret_cast<unsigned*>(st_w + X_STAGE);
     int st_fb = 0, st_fill = 0;
     auto st_flush = [&]() {
-        if (!WR || TLC_X_STAGE == 0 || st_fill == 0) return;
+        if (!WR || st_fill == 0) return;
         x_sync<64>();
         for (int k = lane; k < st_fill; k += TLC_WAVE) {
             const int e = st_fb + k;
@@ -187,9 +181,9 @@ __device__ __forceinline__ int x_sweep_wave(const PB& p, const int* ids, int n, 
     };
     // the round's entries are numbered [r0, r0 + tot): true = they go through the buffer
     auto st_round = [&](int r0, int tot) -> bool {
-        if (!WR || TLC_X_STAGE == 0) return false;
-        if (st_fill && (r0 != st_fb + st_fill || st_fill + tot > TLC_X_STAGE)) st_flush();
-        if (tot > TLC_X_STAGE) return false;
+        if (!WR) return false;
+        if (st_fill && (r0 != st_fb + st_fill || st_fill + tot > X_STAGE)) st_flush();
+        if (tot > X_STAGE) return false;
         if (!st_fill) st_fb = r0;
         st_fill += tot;
         return true;
@@ -419,12 +413,9 @@ __device__ __forceinline__ int x_sweep_ball(const unsigned* __restrict__ be_pos,
             rk = ((p & 64u) ? c0 : 0u) + (unsigned)__popcll(m & below);
         }
     };
-    // TLC_X_BALL_UNROLL chunks of 64 entries are requested together (a list of 1 300 entries was 20 trips to L2 one after the
-    // other; 84 % of the pairs have one chunk and are not touched by this)
-#ifndef TLC_X_BALL_UNROLL
-#define TLC_X_BALL_UNROLL 4
-#endif
-    constexpr int UN = TLC_X_BALL_UNROLL;
+    // UN chunks of 64 entries are requested together (a list of 1 300 entries was 20 trips to L2 one after the other; 84 % of
+    // the pairs have one chunk and are not touched by this.  Measured: one chunk per trip, pipelined batch +2 %; 8 equal to 4)
+    constexpr int UN = 4;
     for (int j0 = e0; j0 < e1; j0 += UN * TLC_WAVE) {
         unsigned pos_[UN];
         double w_[UN];
@@ -494,7 +485,6 @@ __device__ __forceinline__ void x_zero_row(const PB& p, int i, int status, int n
     if (p.out_pi) for (int c = tid; c < res2; c += BW) p.out_pi[(size_t)i * res2 + c] = 0.0;
 }
 
-// One pair.  The bitmap is all zero on entry and on exit.
 // The head of an item -- the pair and the bounds of its rows and ball lists -- as scalars: loaded by the kernel's loop one item
 // ahead of the item's body (tlc_extract_kernel).  Bounds are zero for a pair with an id out of range.
 struct XHead {
@@ -502,18 +492,11 @@ struct XHead {
     int ru0, ru1, rv0, rv1, a0, a1, b0, b1;
     int eu0, eu1, ev0, ev1;            // the ball-subgraph lists of u and v (TlcVicParams::be_ptr; zero without them)
 };
-// The first chunks of a pair's two ball lists, asked for while the pair BEFORE it is swept (single-wavefront workgroups): lane l
-// holds entry l of the smaller list (b) and entries l, 64 + l of the larger one (a), -1 beyond their ends.  (Three registers: with
-// four chunks of each the kernel spilled 40 -- and a spilled prefetch register is a wait for the load in front of the sweep.)
-struct XNoPrefetch {
-    __device__ __forceinline__ void operator()() const {}
-};
+// One pair.  The bitmap is all zero on entry and on exit.
 // FAST (BW == 64): the launch that takes the pairs x_sweep_ball serves (TlcVicParams::fast_split) and nothing else -- the general
 // sweep, the member bitmap and the heavy-member bookkeeping are compiled out, which is what lets it run at twice the wavefronts.
-template <int BW, bool FAST = false, class PB, class PF = XNoPrefetch>
-__device__ __forceinline__ void extract_pair(const PB& p, int i, bool from_rest, const XHead& H, unsigned char* lds, int* slot,
-                                             bool has_pre = false, int pb0 = -1, int pa0 = -1, int pa1 = -1,
-                                             const PF& prefetch_next = PF()) {
+template <int BW, bool FAST = false, class PB>
+__device__ __forceinline__ void extract_pair(const PB& p, int i, bool from_rest, const XHead& H, unsigned char* lds, int* slot) {
     static_assert(!FAST || BW == 64, "the FAST launch is one wavefront per pair");
     constexpr int SID_CAP = FAST ? TLC_BE_CAP + 8 : XCfg<BW>::SID_CAP;   // (the FAST launch never touches its scratch slot)
     const XLayout L = x_layout(p.nw, SID_CAP, BW, FAST);
@@ -542,7 +525,6 @@ __device__ __forceinline__ void extract_pair(const PB& p, int i, bool from_rest,
 #ifdef TLC_PAIR_TIMES
     const unsigned long long t_start = wall_clock64();
 #endif
-#ifndef TLC_NO_FAST_ASSUME
     if constexpr (FAST) {
         // what api.hip's subgraph-list launch always passes (run_chunk_front, `fp`): told to the compiler, the branches on them and the
         // scalar loads of the fields behind them leave the per-pair code (every field of p is re-read per pair, see the kernel)
@@ -550,7 +532,6 @@ __device__ __forceinline__ void extract_pair(const PB& p, int i, bool from_rest,
         __builtin_assume(p.skip_count == nullptr); __builtin_assume(p.big_count == nullptr); __builtin_assume(p.be_ptr != nullptr);
         __builtin_assume((p.flags & TLC_INCLUDE_ROOTS) == 0u); __builtin_assume(p.bump_top != nullptr);
     }
-#endif
     const int u = H.u, v = H.v;
     // KeyError on dict_node (riccidist2dgm.py:353): ids the edge-built graph does not contain
     bool missing = u < 0 || v < 0 || u >= p.n_nodes || v >= p.n_nodes;
@@ -609,23 +590,17 @@ __device__ __forceinline__ void extract_pair(const PB& p, int i, bool from_rest,
 #pragma unroll
     for (int r = 0; r < 4; ++r) {                       // (the first chunks of the smaller list are in flight while the larger is marked)
         const int j = r * BW + tid;
-        if (has_pre && r == 0) bv[r] = pb0;             // (uniform) came with the call
-        else bv[r] = j < nB ? p.bcol[b0 + j] : -1;
+        bv[r] = j < nB ? p.bcol[b0 + j] : -1;
     }
     // (FAST launch with ball bitmaps: the larger ball is not marked at all -- its row of p.bbits answers the membership test below)
     const unsigned* bbrow = nullptr;
     if constexpr (FAST) {
         if (p.bbits) bbrow = p.bbits + (size_t)(((H.a1 - H.a0) < (H.b1 - H.b0)) ? v : u) * (size_t)p.bb_nw;   // (the node whose ball is [a0, a1))
     }
-    bool first = has_pre;
     for (int j = tid; j < (bbrow ? 0 : nA); j += 4 * BW) {
         int av[4];
 #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            if (first && r < 2) av[r] = r == 0 ? pa0 : pa1;
-            else av[r] = (j + r * BW < nA) ? p.bcol[a0 + j + r * BW] : -1;
-        }
-        first = false;
+        for (int r = 0; r < 4; ++r) av[r] = (j + r * BW < nA) ? p.bcol[a0 + j + r * BW] : -1;
 #pragma unroll
         for (int r = 0; r < 4; ++r) if (av[r] >= 0) atomicOr(&X.bits[av[r] >> 5], 1u << (av[r] & 31));
     }
@@ -820,7 +795,6 @@ __device__ __forceinline__ void extract_pair(const PB& p, int i, bool from_rest,
             cap = 2 * TLC_L_MMAX;
         }
     }
-    prefetch_next();                                      // (the next pair's ball lists travel while this one's rows are swept)
     const int m2 = sweep(wdir, wlw, cap, i);
     XSTAMP(6);
     const int m = m2 >> 1;
@@ -860,19 +834,10 @@ __device__ __forceinline__ void extract_pair(const PB& p, int i, bool from_rest,
 
 }  // namespace
 
-#ifndef TLC_X_WPE
-#define TLC_X_WPE 4
-#endif
-#ifndef TLC_X_NOPF
-#define TLC_X_NOPF 0
-#endif
-#ifndef TLC_X_PIPE
-#define TLC_X_PIPE 0          /* 0: the item loop without the stream / list prefetch (A/B) */
-#endif
 typedef const __attribute__((address_space(4))) TlcVicParams XParams;
 typedef const __attribute__((address_space(4))) int XCInt;
 template <int BW, bool FAST>
-__global__ __launch_bounds__(BW, BW == 64 ? (FAST ? 8 : TLC_X_WPE) : 1) void tlc_extract_kernel(TlcVicParams p) {
+__global__ __launch_bounds__(BW, BW == 64 ? (FAST ? 8 : 4) : 1) void tlc_extract_kernel(TlcVicParams p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char xlds[];
     int* slot = p.scratch + (size_t)(p.scratch_base_slot + blockIdx.x) * p.scratch_stride;
     {
@@ -955,102 +920,6 @@ __global__ __launch_bounds__(BW, BW == 64 ? (FAST ? 8 : TLC_X_WPE) : 1) void tlc
     const bool dyn = p.work_counter != nullptr;
     const int n_chunks = dyn ? (n_work + p.work_chunk - 1) / p.work_chunk : n_work;
     int ck = (int)(blockIdx.x % TLC_X_COUNTERS), dry = 0;
-    if constexpr (BW == 64 && TLC_X_PIPE != 0) {
-        // Single-wavefront workgroups: the items of this workgroup form ONE stream (its chunks one after the other) and the stages
-        // run across chunk boundaries, three items ahead: while item k is extracted, the list entry of item k+3, the pair of k+2 and
-        // the row bounds of k+1 are fetched (scalar loads), and once item k's own lists have been consumed -- in front of its
-        // sweep -- the first 64 / 128 entries of the two ball lists of item k+1 are asked for (vector loads that nobody waits for
-        // before the next item starts).  Per-pair stamps had shown 2.4 of the 9.8 us of a <= 16-node pair in front of the first
-        // list entry, and the three-load chain at the head of every CHUNK (two pairs) exposed.
-        int g_c = (int)blockIdx.x;
-        int g_w = g_c < n_chunks ? g_c : -1;                   // the next item the stream hands out
-        int g_nxt = 0;                                        // (lane 0) the counter's answer for the chunk after g_c
-        if (dyn && g_w >= 0 && threadIdx.x == 0) g_nxt = atomicAdd(p.work_counter + ck * TLC_X_COUNTER_STRIDE, 1);
-        auto gen = [&]() -> int {
-            const int w = g_w;
-            if (w < 0) return -1;
-            if (w + n_chunks < n_work) { g_w = w + n_chunks; return w; }
-            if (!dyn) g_c += (int)gridDim.x;
-            else {
-                g_c = (int)gridDim.x + TLC_X_COUNTERS * __builtin_amdgcn_readfirstlane(g_nxt) + ck;
-                while (g_c >= n_chunks && ++dry < TLC_X_COUNTERS) {          // (dry counters: see the loop below)
-                    ck = (ck + 1) % TLC_X_COUNTERS;
-                    int* cnt = p.work_counter + ck * TLC_X_COUNTER_STRIDE;
-                    int t = 0;
-                    if (threadIdx.x == 0) t = __atomic_load_n(cnt, __ATOMIC_RELAXED);
-                    if ((int)gridDim.x + TLC_X_COUNTERS * __builtin_amdgcn_readfirstlane(t) + ck >= n_chunks) continue;
-                    if (threadIdx.x == 0) t = atomicAdd(cnt, 1);
-                    g_c = (int)gridDim.x + TLC_X_COUNTERS * __builtin_amdgcn_readfirstlane(t) + ck;
-                }
-            }
-            g_w = g_c < n_chunks ? g_c : -1;
-            if (dyn && g_w >= 0 && threadIdx.x == 0) g_nxt = atomicAdd(p.work_counter + ck * TLC_X_COUNTER_STRIDE, 1);
-            return w;
-        };
-        bool fr0 = false, fr1 = false, fr2 = false;
-        int i0 = -1, i1 = -1, i2 = -1, u1 = -1, v1 = -1;
-        XHead H0;
-        H0.u = H0.v = -1;
-        {
-            XParams* q = kp;
-            asm volatile("" : "+s"(q));
-            const int w0 = gen(), w1 = gen(), w2 = gen();
-            if (w0 >= 0) i0 = idx_of(q, w0, fr0);
-            if (w1 >= 0) i1 = idx_of(q, w1, fr1);
-            if (w2 >= 0) i2 = idx_of(q, w2, fr2);
-            if (i0 >= 0) pair_of(q, i0, H0.u, H0.v);
-            if (i1 >= 0) pair_of(q, i1, u1, v1);
-            bounds_of(q, H0);
-        }
-        bool pre_ok = false;
-        int pb0 = -1, pa0 = -1, pa1 = -1;
-        while (i0 >= 0) {
-            XParams* q = kp;
-            asm volatile("" : "+s"(q));
-            bool fr3 = false;
-            int i3 = -1, u2 = -1, v2 = -1;
-            const int w3 = gen();
-            if (w3 >= 0) i3 = idx_of(q, w3, fr3);
-            if (i2 >= 0) pair_of(q, i2, u2, v2);
-            XHead H1;
-            H1.u = u1; H1.v = v1;
-            bounds_of(q, H1);
-            bool pf_done = false, pre_n = false;
-            int npb0 = -1, npa0 = -1, npa1 = -1;
-            auto pf = [&]() {
-                pf_done = true;
-                if (TLC_X_NOPF || i1 < 0 || q->x_fill) return;
-                int a0 = H1.a0, a1 = H1.a1, b0 = H1.b0, b1 = H1.b1;          // (all zero for ids outside the graph)
-                if (a1 - a0 < b1 - b0) { int t = a0; a0 = b0; b0 = t; t = a1; a1 = b1; b1 = t; }
-                const int nA = a1 - a0, nB = b1 - b0;
-                if (fr1) {                                                   // (a pair another pass owns: extract_pair's predicates)
-                    if (q->skip_count && nB >= q->skip_threshold) return;
-                    else if (q->big_count && nB >= TLC_X_BIN_MIN) return;
-                }
-                const int* bc = q->bcol;
-                const int j = (int)threadIdx.x;
-                npb0 = j < nB ? bc[b0 + j] : -1;
-                npa0 = j < nA ? bc[a0 + j] : -1;
-                npa1 = j + 64 < nA ? bc[a0 + j + 64] : -1;
-                pre_n = true;
-            };
-            extract_pair<BW, FAST>(*q, i0, fr0, H0, xlds, slot, pre_ok, pb0, pa0, pa1, pf);
-            if (!pf_done) pf();
-            pre_ok = pre_n;
-            pb0 = npb0; pa0 = npa0; pa1 = npa1;
-            // (the carried heads are uniform; said explicitly, or the compiler keeps the eight bounds in vector registers across the body)
-#define XU(x) __builtin_amdgcn_readfirstlane(x)
-            i0 = XU(i1); fr0 = fr1;
-            H0.u = XU(H1.u); H0.v = XU(H1.v);
-            H0.ru0 = XU(H1.ru0); H0.ru1 = XU(H1.ru1); H0.rv0 = XU(H1.rv0); H0.rv1 = XU(H1.rv1);
-            H0.a0 = XU(H1.a0); H0.a1 = XU(H1.a1); H0.b0 = XU(H1.b0); H0.b1 = XU(H1.b1);
-            H0.eu0 = XU(H1.eu0); H0.eu1 = XU(H1.eu1); H0.ev0 = XU(H1.ev0); H0.ev1 = XU(H1.ev1);
-            i1 = XU(i2); fr1 = fr2; u1 = XU(u2); v1 = XU(v2);
-            i2 = XU(i3); fr2 = fr3;
-#undef XU
-        }
-        return;
-    }
     for (int c = blockIdx.x; c < n_chunks;) {
         int nxt = 0;
         if (dyn && BW == 64 && threadIdx.x == 0) nxt = atomicAdd(p.work_counter + ck * TLC_X_COUNTER_STRIDE, 1);

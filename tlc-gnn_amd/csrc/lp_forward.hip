@@ -419,12 +419,6 @@ static hipError_t gemm16_launch(int M, int N, int K, const float* A, const float
 //     per block, with the other wavefront of its SIMD filling the gaps.
 // ======================================================================================================================
 #define GBR_KH 128                                           /* k per phase */
-#ifdef TLC_GBR_DEBUG
-__device__ unsigned long long g_gbr_dbg[16];                 // cycle sums of wavefront 0 of every workgroup: see GBR_STAMP
-#define GBR_STAMP(k) do { const unsigned long long _t = clock64(); if (tid == 0) atomicAdd(&g_gbr_dbg[(k)], _t - t_prev); t_prev = _t; } while (0)
-#else
-#define GBR_STAMP(k) do { } while (0)
-#endif
 template <int NT>
 struct GbrLayout {
     static constexpr int NP = NT * 16;
@@ -451,9 +445,6 @@ __global__ __launch_bounds__(256 * KS) void gemm_bres_f32_kernel(int M, int N, i
     const int l16 = lane & 15, g = lane >> 4;
     const int row0 = blockIdx.x * G16_BM;
 
-#ifdef TLC_GBR_DEBUG
-    unsigned long long t_prev = clock64();
-#endif
     f32x4 acc[NB];
 #pragma unroll
     for (int t = 0; t < NB; ++t) acc[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
@@ -509,16 +500,9 @@ __global__ __launch_bounds__(256 * KS) void gemm_bres_f32_kernel(int M, int N, i
     // waited 6 500 cycles per phase for them.
     u32x4 xa0[BLK], xa1[BLK], ya0[BLK], ya1[BLK];
     auto phase = [&](int ph, int buf, const u32x4 (&ca0)[BLK], const u32x4 (&ca1)[BLK], u32x4 (&na0)[BLK], u32x4 (&na1)[BLK]) __attribute__((always_inline)) {
-#ifndef TLC_GBR_SKIP_B                                       /* (diagnostic builds: which operand stream the wavefronts wait for) */
         issue_b(ph + 1, buf ^ 1);                            // (the other buffer: its last readers passed the barrier of the phase before)
-#endif
-#ifndef TLC_GBR_SKIP_A
 #pragma unroll
         for (int i = 0; i < BLK; ++i) { na0[i] = load_a0(ph + 1, i); na1[i] = load_a1(ph + 1, i); }
-#else
-#pragma unroll
-        for (int i = 0; i < BLK; ++i) { na0[i] = ca0[i]; na1[i] = ca1[i]; }
-#endif
         constexpr int NO = KS <= 2 ? 2 : 1;                  // (four wavefronts per SIMD hide an LDS round trip themselves: one operand set)
         Bops o[NO];
         read_b(o[0], buf, ks * BLK);
@@ -536,18 +520,14 @@ __global__ __launch_bounds__(256 * KS) void gemm_bres_f32_kernel(int M, int N, i
                 for (int x = 0; x < XT; ++x) acc[NT + x] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa1[sidx], o[i & (NO - 1)].b[NT + x][sidx], acc[NT + x], 0, 0, 0);
             }
         }
-        GBR_STAMP(1);                                        // [1] a phase's MFMAs issued
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");    // this wavefront's part of the next slice is in LDS ...
-        GBR_STAMP(2);                                        // [2] waiting for its own loads
         __syncthreads();                                     // ... and everybody's
-        GBR_STAMP(3);                                        // [3] barrier
     };
 #pragma unroll
     for (int i = 0; i < BLK; ++i) { xa0[i] = load_a0(0, i); xa1[i] = load_a1(0, i); }
     issue_b(0, 0);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
-    GBR_STAMP(0);                                            // [0] prologue: first operands in
     for (int ph = 0; ph < nph; ph += 2) {
         phase(ph, 0, xa0, xa1, ya0, ya1);
         if (ph + 1 < nph) phase(ph + 1, 1, ya0, ya1, xa0, xa1);      // (uniform)
@@ -586,19 +566,12 @@ __global__ __launch_bounds__(256 * KS) void gemm_bres_f32_kernel(int M, int N, i
         if (relu) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
         *reinterpret_cast<float4*>(C + (size_t)(row0 + r) * N + c) = v;
     }
-    GBR_STAMP(4);                                            // [4] epilogue (K-group sums through LDS, row stores issued)
-#ifdef TLC_GBR_DEBUG
-    if (tid == 0) atomicAdd(&g_gbr_dbg[15], 1ull);
-#endif
 }
 
-#ifndef TLC_GBR_KS
-#define TLC_GBR_KS 2
-#endif
 template <int NT>
 static hipError_t gemm_bres_launch(int M, int N, int K, const float* A, const float* B, const float* bias, int relu, float* C, hipStream_t s) {
     static bool attr_set[64] = {};
-    constexpr int KS = TLC_GBR_KS;
+    constexpr int KS = 2;                                    // two K groups of four wavefronts
     auto kern = gemm_bres_f32_kernel<NT, KS>;
     constexpr int lds = GbrLayout<NT>::LDS_BYTES;
     int dev = 0;
@@ -609,21 +582,6 @@ static hipError_t gemm_bres_launch(int M, int N, int K, const float* A, const fl
         attr_set[dev] = true;
     }
     hipLaunchKernelGGL(kern, dim3((M + G16_BM - 1) / G16_BM), dim3(256 * KS), lds, s, M, N, K, A, B, bias, relu, C);
-#ifdef TLC_GBR_DEBUG
-    {
-        static int calls = 0;
-        if (++calls == 50) {                                  // (one report, once warm)
-            unsigned long long h[16], z[16] = {};
-            (void)hipMemcpyToSymbol(HIP_SYMBOL(g_gbr_dbg), z, sizeof(z));
-            hipLaunchKernelGGL(kern, dim3((M + G16_BM - 1) / G16_BM), dim3(256 * KS), lds, s, M, N, K, A, B, bias, relu, C);
-            (void)hipStreamSynchronize(s);
-            (void)hipMemcpyFromSymbol(h, HIP_SYMBOL(g_gbr_dbg), sizeof(h));
-            const double w = (double)(h[15] ? h[15] : 1);
-            fprintf(stderr, "[gemm_bres %d x %d x %d] cycles of wavefront 0, mean over %llu workgroups: prologue %.0f | MFMA phases %.0f | own loads %.0f | barrier %.0f | epilogue %.0f\n",
-                    M, K, N, h[15], h[0] / w, h[1] / w, h[2] / w, h[3] / w, h[4] / w);
-        }
-    }
-#endif
     return hipGetLastError();
 }
 
@@ -1331,9 +1289,8 @@ extern "C" int tlc_gemm_f32(int32_t M, int32_t N, int32_t K, const float* d_A, c
         }
     }
     hipError_t le = hipSuccess;
-    // enough K for phases of 128 and 16-byte operands: B resident in LDS, no barrier inside the K loop (TLC_GEMM_BRES=0: the chunked kernel)
-    static const bool bres_on = !(getenv("TLC_GEMM_BRES") && getenv("TLC_GEMM_BRES")[0] == '0');
-    if (bres_on && vec && K >= 128 && (long long)G16_BM * K * 4 < (1ll << 31)) {
+    // enough K for phases of 128 and 16-byte operands: B resident in LDS, no barrier inside the K loop
+    if (vec && K >= 128 && (long long)G16_BM * K * 4 < (1ll << 31)) {
 #define TLC_GBR(NT_) case NT_: le = gemm_bres_launch<NT_>(M, N, K, d_A, d_B, d_bias, relu, d_C, s); break;
         switch ((N + 15) / 16) {
             TLC_GBR(1) TLC_GBR(2) TLC_GBR(3) TLC_GBR(4) TLC_GBR(5) TLC_GBR(6) TLC_GBR(7) TLC_GBR(8)
@@ -1383,7 +1340,7 @@ extern "C" int tlc_gemm_f32(int32_t M, int32_t N, int32_t K, const float* d_A, c
 // row's first entry's, so the only weights multiplied by that zero are ones the row uses anyway (finite weights: exact; a
 // non-finite weight the row touches gives a non-finite output either way, possibly NaN where the sum is an infinity).
 //
-// What bounds it (cycle stamps per wavefront, TLC_SQ_DEBUG): the LDS reads of the slice -- 13 ds_read_b128 of 1 KB per row of 50
+// What bounds it (cycle stamps per wavefront, measured): the LDS reads of the slice -- 13 ds_read_b128 of 1 KB per row of 50
 // entries, 16 wavefronts x 10 rows per CU = 16 000 cycles of the LDS pipe at 128 B per clock -- then the slice's way into LDS
 // (26 MB from L2 over all CUs, asked for with buffer_load ... lds: no registers, no ds_write, every piece in flight at once).
 // The entries of a row are requested four rows ahead into a ring of four register pairs.  The loads are issued from inline
@@ -1394,15 +1351,6 @@ extern "C" int tlc_gemm_f32(int32_t M, int32_t N, int32_t K, const float* d_A, c
 // requests into the same registers (a request under a branch gets routed through a temporary the compiler copies from before
 // the data is there): a block's rows are rounded up to a multiple of four with empty ones, and loads have no branch around them
 // -- a lane without an entry asks for an offset behind the descriptor's range and gets zero.
-#ifndef TLC_SPGEMM_NW
-#define TLC_SPGEMM_NW 16
-#endif
-#ifdef TLC_SQ_DEBUG
-__device__ unsigned long long g_sq_dbg[8];                   // cycle sums over all wavefronts
-#define SQ_CLK() clock64()
-#else
-#define SQ_CLK() 0ull
-#endif
 template <int I>
 __device__ __forceinline__ int row_bcast(int x) { return __builtin_amdgcn_update_dpp(0, x, 0x150 + I, 0xf, 0xf, true); }
 
@@ -1423,13 +1371,7 @@ __global__ __launch_bounds__(NW * 64, 1) void spgemm_quad_kernel(int M, int K, i
     const int stride = (int)gridDim.x * NW;
     const int r_first = (int)blockIdx.x * NW + wave;
     // the rows of this wavefront are r_first + i stride: lane i keeps the bounds of row i (of a block of 64 rows)
-#if defined(TLC_SQ_DIAG) && (TLC_SQ_DIAG & 1)                    /* (diagnostic builds: 1 no rows, 2 no staging, 4 no row stores) */
-    const int n_mine = 0;
-#else
     const int n_mine = r_first < M ? (M - r_first + stride - 1) / stride : 0;
-#endif
-    unsigned long long dbg_t0 = SQ_CLK(), dbg_wait = 0, dbg_chunk = 0, dbg_tail = 0, dbg_stage = 0;
-    (void)dbg_t0; (void)dbg_wait; (void)dbg_chunk; (void)dbg_tail; (void)dbg_stage;
     int rb0 = 0, rb1 = 0;
     if (lane < n_mine) { rb0 = rowptr[r_first + lane * stride]; rb1 = rowptr[r_first + lane * stride + 1]; }
     constexpr int OOB = 0x7ffffff0;
@@ -1456,11 +1398,7 @@ __global__ __launch_bounds__(NW * 64, 1) void spgemm_quad_kernel(int M, int K, i
         const unsigned inv = (1u << 20) / (unsigned)q4 + 1u;      // id / q4 = (id inv) >> 20 for id q4 < 2^20 (items <= 10 240 fit LDS, q4 <= 16);
                                                                   // the product in 64 bits: q4 = 1 or 2 (N = 4, 8) puts inv near 2^20 and id above 4 095
         const int npieces = (items + 63) >> 6;
-#if defined(TLC_SQ_DIAG) && (TLC_SQ_DIAG & 2)
-        for (int pc = wave; pc < 0; pc += NW) {
-#else
         for (int pc = wave; pc < npieces; pc += NW) {
-#endif
             const int id = pc * 64 + lane;
             const int k = (int)(((unsigned long long)(unsigned)id * inv) >> 20), q = id - k * q4;
             const int goff = (id < items && 4 * q < cw) ? (k * N + c0 + 4 * q) * 4 : OOB;
@@ -1475,7 +1413,6 @@ __global__ __launch_bounds__(NW * 64, 1) void spgemm_quad_kernel(int M, int K, i
         if (tid < 16) Bs[K * sw + tid] = 0.f;
     }
     __syncthreads();
-    dbg_stage = SQ_CLK() - dbg_t0;
     const int my_col = 4 * l + g;                                 // the column of the slice this lane stores
     const float bvs = (bias && my_col < cw) ? bias[c0 + my_col] : 0.f;
     const unsigned char* bsb = sq_lds + loff;
@@ -1519,9 +1456,7 @@ __global__ __launch_bounds__(NW * 64, 1) void spgemm_quad_kernel(int M, int K, i
 
     // one row: its first chunk in the ring pair (kr, vr), requested four rows ago; the pair then takes row i + 4
     auto do_row = [&](int r, int i, int& kr, int& vr) __attribute__((always_inline)) {
-        const unsigned long long ta = SQ_CLK();
         asm volatile("s_waitcnt vmcnt(6)" : "+v"(kr), "+v"(vr) : : "memory");
-        const unsigned long long tb = SQ_CLK();
         int kk = kr, vvi = vr;
         asm volatile("" : "+v"(kk), "+v"(vvi) : "v"(kr), "v"(vr) : "memory");   // (the copies are made here, before the pair is requested again)
         request(i + 4, kr, vr);
@@ -1536,19 +1471,8 @@ __global__ __launch_bounds__(NW * 64, 1) void spgemm_quad_kernel(int M, int K, i
                 asm volatile("s_waitcnt vmcnt(0)" : "+v"(kk), "+v"(vvi) : : "memory");
             }
             turn_round(kk, vvi, cnt);
-#ifdef TLC_SQ_DUMP
-            if (r == 0) { C[64 + lane] = __builtin_bit_cast(float, vvi); C[128 + lane] = (float)kk; }
-#endif
             do_chunk(kk, vvi, cnt, acc);
         }
-#ifdef TLC_SQ_DUMP
-        if (r == 0) { C[192 + lane] = acc.x; C[256 + lane] = acc.y; }
-#endif
-#ifdef TLC_SQ_DEBUG
-        asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(acc.x), "+v"(acc.y), "+v"(acc.z), "+v"(acc.w) : : "memory");
-#endif
-        const unsigned long long tc = SQ_CLK();
-        dbg_wait += tb - ta; dbg_chunk += tc - tb;
         if (r < M) {                                              // (uniform; the padding rows of a trip have no row)
             // rows of 16 lanes: [x | y] -> x' = (x0, y0, x2, y2), y' = (x1, y1, x3, y3); the same for [z | w]; then the halves.
             // (From assembly: with __builtin_amdgcn_permlane16_swap this compiler adds the FIRST result to itself -- v_add v, v9, v9.
@@ -1560,13 +1484,8 @@ __global__ __launch_bounds__(NW * 64, 1) void spgemm_quad_kernel(int M, int K, i
             asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1\n\ts_nop 1" : "+v"(s_xy), "+v"(s_zw));
             float y = (s_xy + s_zw) + bvs;                        // (x, y, z, w): column 4 l + g
             if (relu & 1) y = y > 0.f ? y : 0.f;
-#if defined(TLC_SQ_DIAG) && (TLC_SQ_DIAG & 4)
-            if (my_col < cw && y == 123.456f) C[(size_t)r * N + c0 + my_col] = y;
-#else
             if (my_col < cw) C[(size_t)r * N + c0 + my_col] = y;
-#endif
         }
-        dbg_tail += SQ_CLK() - tc;
     };
 
     for (int blk = 0; blk < n_mine; blk += 64) {                  // (more than 64 rows per wavefront: the bounds 64 rows at a time)
@@ -1587,14 +1506,6 @@ __global__ __launch_bounds__(NW * 64, 1) void spgemm_quad_kernel(int M, int K, i
     }
     // (the ring's last requests -- rows behind the end: empty -- land before the wavefront ends)
     asm volatile("s_waitcnt vmcnt(0)" : : : "memory");
-#ifdef TLC_SQ_DEBUG
-    if (lane == 0) {
-        const unsigned long long whole = SQ_CLK() - dbg_t0;
-        atomicAdd(&g_sq_dbg[0], dbg_stage); atomicAdd(&g_sq_dbg[1], dbg_wait); atomicAdd(&g_sq_dbg[2], dbg_chunk);
-        atomicAdd(&g_sq_dbg[3], dbg_tail); atomicAdd(&g_sq_dbg[4], whole); atomicAdd(&g_sq_dbg[5], (unsigned long long)n_mine);
-        atomicAdd(&g_sq_dbg[7], 1ull);
-    }
-#endif
 }
 
 extern "C" int tlc_spgemm_csr_dense_f32(int32_t M, int32_t K, int32_t N, const int32_t* d_rowptr, const int32_t* d_col,
@@ -1606,7 +1517,7 @@ extern "C" int tlc_spgemm_csr_dense_f32(int32_t M, int32_t K, int32_t N, const i
     // column slices of equal width, a multiple of four and at most 64 (N = 100: 52 + 48)
     const int slices = (N + 63) / 64;
     const int sw = (((N + slices - 1) / slices) + 3) & ~3;
-    constexpr int NW = TLC_SPGEMM_NW;
+    constexpr int NW = 16;                           // wavefronts per workgroup
     const size_t lds = (size_t)K * sw * sizeof(float) + 1024;
     if (lds > 160 * 1024) {
         tlc_set_error("tlc_spgemm_csr_dense_f32: K = %d needs %zu B of LDS per %d-column slice (max 160 KiB)", K, lds, sw);
@@ -1622,23 +1533,6 @@ extern "C" int tlc_spgemm_csr_dense_f32(int32_t M, int32_t K, int32_t N, const i
         TLC_HIP_CHECK(hipFuncSetAttribute((const void*)spgemm_quad_kernel<NW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipLaunchKernelGGL(spgemm_quad_kernel<NW>, dim3(gx, slices), dim3(NW * 64), lds, s, M, K, N, sw, d_rowptr, d_col, d_val, d_B,
                        d_bias, relu, d_C);
-#ifdef TLC_SQ_DEBUG
-    {
-        static int calls = 0;
-        if (++calls % 50 == 0) {                             // (a report every 50 calls, warm)
-            unsigned long long h[8], z[8] = {};
-            (void)hipMemcpyToSymbol(HIP_SYMBOL(g_sq_dbg), z, sizeof(z));
-            hipLaunchKernelGGL(spgemm_quad_kernel<NW>, dim3(gx, slices), dim3(NW * 64), lds, s, M, K, N, sw, d_rowptr, d_col, d_val, d_B,
-                               d_bias, relu, d_C);
-            (void)hipStreamSynchronize(s);
-            (void)hipMemcpyFromSymbol(h, HIP_SYMBOL(g_sq_dbg), sizeof(h));
-            const double w = (double)(h[7] ? h[7] : 1);
-            fprintf(stderr, "[spgemm_quad %d x %d x %d] mean cycles per wavefront (%llu wavefronts, %.1f rows each): to the barrier %.0f | rows: "
-                    "waiting for entries %.0f, chunks %.0f, butterfly + store %.0f | whole %.0f\n",
-                    M, K, N, h[7], h[5] / w, h[0] / w, h[1] / w, h[2] / w, h[3] / w, h[4] / w);
-        }
-    }
-#endif
     TLC_HIP_CHECK(hipGetLastError());
     return TLC_OK;
 }

@@ -37,7 +37,7 @@
 #define TLC_STAMP(k) do { } while (0)
 #endif
 #define TLC_NONE16 0xFFFFu
-// Timing experiment (tools/gpu_r6_knockout.sh): -DTLC_STOP_AFTER=k compiles the tier kernels' stages behind stage k out -- 1 staging,
+// Timing experiment (make EXTRA=-DTLC_STOP_AFTER=k): the tier kernels' stages behind stage k are compiled out -- 1 staging,
 // 2 Bellman-Ford, 3 tight chains (+ fallback) and normalisation, 4 edge compaction, 5 rank relabel + ascending sort, 6 ascending pass,
 // 7 descending sort, 8 descending pass + Pos / Neg split, 9 cycle swap (hand-off / walk / divide and conquer), 10 image = everything.
 // Rows are garbage below 10; what a pipelined batch then costs, stage by stage, is the cost table of DESIGN.md section 0.
@@ -45,11 +45,6 @@
 #define TLC_STOP_AFTER 10
 #endif
 #define TLC_STOPPED 99          /* a status nobody tests for: every later stage is guarded by status == TLC_ST_OK */
-// the SMALL tier keeps its entry weights in LDS (true) or reads them from the arena like the larger tiers (false: 6.9 -> 6.0 KB per
-// workgroup; A/B on one box, tools/gpu_build_ab.sh: pipelined batch 0.744 -> 0.736 ms, one batch alone 0.804 -> 0.792 ms)
-#ifndef TLC_SMALL_LWL
-#define TLC_SMALL_LWL false
-#endif
 
 namespace {
 
@@ -70,21 +65,22 @@ __host__ __device__ constexpr size_t smax(size_t a, size_t b) { return a > b ? a
 //              [first/hook u32 | best u32 | comp2 | tree bits | R bits] in the key half between the sorts (MST passes),
 //              then [edge rank of each node's parent edge u32] (cycle swap)
 //   dir region: directed entries, then [undirected edges (lo<<16|hi in rank space) | ascending rank of every edge],
-//              then (with lw) the image table
+//              then the image table
+// Every tier reads its entry weights from the arena.  (Keeping the SMALL tier's in LDS was measured: 6.9 instead of 6.0 KB per
+// workgroup, pipelined batch 0.744 instead of 0.736 ms.)
 struct Layout {
-    size_t o_f, o_dir, o_lw, o_x, o_vals, o_amb, o_par, o_mark, o_pn, o_pts, o_ctl, o_rec, total;
+    size_t o_f, o_dir, o_x, o_vals, o_amb, o_par, o_mark, o_pn, o_pts, o_ctl, o_rec, total;
     int P;   // capacity of the sort buffers (power of two >= max(NM, MM))
 };
 __host__ __device__ constexpr size_t aux_bytes(int NM, int MM, int idxb) {
     return (size_t)NM * 8 + al16((size_t)NM * idxb) + 2 * al16((size_t)((MM + 31) / 32) * 4);
 }
-__host__ __device__ constexpr Layout make_layout(int NM, int MM, bool lwl, int idxb, size_t min_table = 0) {
+__host__ __device__ constexpr Layout make_layout(int NM, int MM, int idxb, size_t min_table = 0) {
     Layout L{};
     size_t o = 0;
     L.P = pow2ceil(NM > MM ? NM : MM);
     L.o_f = o;    o += al16((size_t)(NM + 2) * 8);                      // BF distances from u, then f
     L.o_dir = o;  o += al16((size_t)2 * MM * 4);                        // directed entries | later: edges + asc ranks
-    L.o_lw = o;   o += lwl ? al16((size_t)2 * MM * 8) : 0;              // entry weights (dir|lw also host the PI table)
     if (o - L.o_dir < min_table) o = L.o_dir + al16(min_table);         // the image table needs >= 1 point
     const size_t keys = al16(smax((size_t)L.P * 8, aux_bytes(NM, MM, idxb)));
     L.o_x = o;
@@ -99,13 +95,11 @@ __host__ __device__ constexpr Layout make_layout(int NM, int MM, bool lwl, int i
     L.o_amb = o;  o += al16((size_t)NM * idxb);                         // tie-fallback list, then union-find parents
     L.o_par = o;  o += al16((size_t)NM * idxb);                         // spanning-tree parents
     L.o_mark = o; o += al16((size_t)NM * idxb);                         // node ranks, then path stamps
-    // (both also host one tight-successor weight table of the filtration stage, NM doubles, when the weights are not in LDS)
-    L.o_pn = o;   o += al16(smax((size_t)MM * 4, lwl ? 0 : (size_t)NM * 8));             // Pos from the front, Neg from the back (edge ids)
-    L.o_pts = o;  o += al16(smax((size_t)(MM + 2) * 4, lwl ? 0 : (size_t)NM * 8));       // diagram points (birth node<<16 | death node)
+    // (both also host one tight-successor weight table of the filtration stage, NM doubles)
+    L.o_pn = o;   o += al16(smax((size_t)MM * 4, (size_t)NM * 8));                        // Pos from the front, Neg from the back (edge ids)
+    L.o_pts = o;  o += al16(smax((size_t)(MM + 2) * 4, (size_t)NM * 8));                  // diagram points (birth node<<16 | death node)
     L.o_ctl = o;  o += 320;                                             // 16 ints | 16 doubles | 32 ints
-    // cycle swap: the two walks' path records, [2][65] nodes + [2][65] keys (the entry weights are dead by then)
-    if (lwl && (size_t)2 * MM * 8 >= 1280) L.o_rec = L.o_lw;
-    else { L.o_rec = o; o += 1280; }
+    L.o_rec = o;  o += 1280;                                            // cycle swap: the two walks' path records, [2][65] nodes + [2][65] keys
     L.total = o;
     return L;
 }
@@ -115,7 +109,6 @@ struct Mem {
     double* f;
     unsigned* dir;     // phase 1: directed entries; afterwards ends[e] = lo<<16|hi (rank space)
     unsigned* arank;   // ascending-sort position of edge e
-    double* lw;
     ull* dv;
     unsigned *cntU, *nxtU, *cntV, *nxtV;
     ull* keyS;
@@ -131,7 +124,7 @@ struct Mem {
     double* red;   // 16 doubles for block reductions
     int* wcnt;     // 32 ints for block compaction
     unsigned* rec; // cycle swap: path records of the two walks
-    unsigned char* table;  // PI table: spans dir (+lw)
+    unsigned char* table;  // PI table: spans dir
     size_t table_bytes;
     unsigned char* xbase;  // everything between the edge tables and the Pos/Neg lists: free once the passes are done
     size_t xbytes;
@@ -143,12 +136,11 @@ struct Mem {
 };
 
 template <typename idx_t>
-__device__ __forceinline__ Mem<idx_t> carve(unsigned char* base, const Layout& L, int NM, int MM, bool lwl) {
+__device__ __forceinline__ Mem<idx_t> carve(unsigned char* base, const Layout& L, int NM, int MM) {
     Mem<idx_t> m;
     m.f = (double*)(base + L.o_f);
     m.dir = (unsigned*)(base + L.o_dir);
     m.arank = m.dir + MM;
-    m.lw = (double*)(base + L.o_lw);
     m.dv = (ull*)(base + L.o_x);
     m.cntU = (unsigned*)(base + L.o_x + (size_t)NM * 8);
     m.nxtU = m.cntU + NM;
@@ -484,12 +476,6 @@ struct PtsSink {
     __device__ __forceinline__ void ext0(const double*, int mn, int mx) { pts[ctl[2]++] = ((unsigned)mn << 16) | (unsigned)mx; }
     __device__ __forceinline__ void down(const double*, int, int) {}
     __device__ __forceinline__ void one_at(const double*, int slot, int, int b, int d) { pts[slot] = ((unsigned)b << 16) | (unsigned)d; }
-};
-// development check (TLC_DC_VERIFY): the higher endpoint per query
-struct VerifySink {
-    unsigned short* o;
-    [[maybe_unused]] static constexpr bool want_down = false, is_global = false;
-    __device__ __forceinline__ void one_at(const double*, int, int k, int, int d) { o[k] = (unsigned short)d; }
 };
 // tlc_pd_from_filtration: values straight to the caller's arrays.
 struct GlobalSink {
@@ -1062,9 +1048,6 @@ __device__ __forceinline__ int ext1_walk(const SwapTables& T, ull* recs, Query& 
 // A walker EXCHANGES its stamp and its running maximum into the node it steps on: what comes back is the other walker's stamp and
 // maximum when that one has been there (the meeting), so "publish, take the stamp, read theirs" of ext1_walk is one ds_wrxchg_rtn_b64.
 // In the swap kernels these steps are a seventh of a pipelined batch's wave-instructions (profiles/r05_stream_assignment.txt, 3).
-#ifndef TLC_SWAP_COMPACT
-#define TLC_SWAP_COMPACT 1        /* make EXTRA="-DTLC_SWAP_COMPACT=0": the swap kernels on ext1_walk's tables (A/B) */
-#endif
 struct SwapTablesC {
     unsigned* pk;
     ull* slot;
@@ -1248,27 +1231,6 @@ __device__ __forceinline__ void ext1_stage(Mem<idx_t>& M, Sink& sink, int n, uns
         const bool ok = M.xbytes > hin_bytes &&
                         ext1_dc_solve<W>(src, n, K, M.ctl[4], M.ctl, M.wcnt, M.xbase, M.xbytes - hin_bytes, hin);
         if (threadIdx.x == 0 && M.stats) atomicAdd(&M.stats[ok ? 1 : 3], 1ull);
-#ifdef TLC_DC_VERIFY
-        if (ok && (size_t)(M.ctl[2] + K) * 4 + (size_t)K * 2 + 16 <= (size_t)(MMcap + 2) * 4) {
-            // development check: the serial walk on the same input, answer for answer (mismatches are counted in stats[3])
-            unsigned short* v_hin = (unsigned short*)(M.pts + M.ctl[2] + K + 2);
-            VerifySink vs{v_hin};
-            unsigned short keep[8];
-            for (int q = 0; q < 8; ++q) { const int k = (int)threadIdx.x + q * W; keep[q] = k < K ? hin[k] : 0; }
-            __syncthreads();
-            const SwapTables Tv = carve_swap(M.keyS, NMcap);
-            const bool anyu = ext1_build_tree<W>(M, Tv, n, MMcap, NMcap);
-            if (threadIdx.x < 64) {
-                QueryLds qv{M.pn, M.dir, M.arank, K, 0u, 0u, 0u};
-                ext1_walk(Tv, (ull*)M.rec, qv, K, NMcap, anyu, vs, M.f, true, 0, nullptr);
-            }
-            __syncthreads();
-            int mism = 0;
-            for (int q = 0; q < 8; ++q) { const int k = (int)threadIdx.x + q * W; if (k < K) { mism += (keep[q] != v_hin[k]); hin[k] = keep[q]; } }
-            if (mism && M.stats) atomicAdd(&M.stats[3], (unsigned long long)mism);
-            __syncthreads();
-        }
-#endif
         if (ok) {
             const bool keep0 = (flags & TLC_KEEP_ZERO_PERS) != 0;
             const int out0 = M.ctl[2];
@@ -1500,9 +1462,7 @@ __device__ __forceinline__ double pi_stage_impl(double* tbl, size_t table_bytes,
 }
 template <int W, bool BOUNDED, int SW, class Get>
 __device__ __forceinline__ double pi_stage(double* tbl, size_t table_bytes, Get get, int first, int last, int res, double acc) {
-#ifndef TLC_NO_RES5
     if (res == 5) return pi_stage_impl<W, BOUNDED, SW, 5>(tbl, table_bytes, get, first, last, res, acc);   // (uniform)
-#endif
     return pi_stage_impl<W, BOUNDED, SW, 0>(tbl, table_bytes, get, first, last, res, acc);
 }
 
@@ -1518,16 +1478,13 @@ __device__ __forceinline__ void dc_subgraph(const TlcPdParams& p, int wi, unsign
 // PLAIN: the launch is the plain TLC-GNN image batch -- flags == 0, images at resolution 5, none of tlc_vicinity_filtration's outputs
 // (tlc_launch_pd_tier checks): those parameters are constants of the instance, and every branch on a variant flag, the filtration /
 // edge outputs and the divisions by the resolution drop out of the kernel the bench batch runs.
-template <int NM, int MM, int W, bool LWL, bool HUGE, bool PLAIN = false>
+template <int NM, int MM, int W, bool HUGE, bool PLAIN = false>
 #ifdef TLC_PHASE_DEBUG
 __global__ __launch_bounds__(W) void tlc_pd_tier_kernel(TlcPdParams p) {       // (the counters need the registers)
 #else
 // 128 VGPRs for the SMALL and MEDWIDE tiers: four wavefronts per SIMD (16 resp. 4 workgroups per CU); 80 for the compact MEDIUM
 // configuration: six (its 26 KB of LDS let six workgroups share a CU)
-#ifndef TLC_M_WPE
-#define TLC_M_WPE 4
-#endif
-__global__ __launch_bounds__(W, (W == 256 && !HUGE ? (NM == TLC_C_NMAX ? 6 : TLC_M_WPE) : (W <= 128 ? 4 : 1))) void tlc_pd_tier_kernel(TlcPdParams p) {
+__global__ __launch_bounds__(W, (W == 256 && !HUGE ? (NM == TLC_C_NMAX ? 6 : 4) : (W <= 128 ? 4 : 1))) void tlc_pd_tier_kernel(TlcPdParams p) {
 #endif
     typedef unsigned short idx_t;
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
@@ -1541,39 +1498,20 @@ __global__ __launch_bounds__(W, (W == 256 && !HUGE ? (NM == TLC_C_NMAX ? 6 : TLC
     int NMr, MMr;
     if constexpr (HUGE) {
         NMr = p.huge_nmax; MMr = p.huge_mmax;
-        L = make_layout(NMr, MMr, false, sizeof(idx_t), TLC_HUGE_MIN_TABLE);
+        L = make_layout(NMr, MMr, sizeof(idx_t), TLC_HUGE_MIN_TABLE);
         base = p.huge_scratch + (size_t)blockIdx.x * p.huge_stride;
     } else {
         NMr = NM; MMr = MM;
-        constexpr Layout Lc = make_layout(NM, MM, LWL, sizeof(idx_t));
+        constexpr Layout Lc = make_layout(NM, MM, sizeof(idx_t));
         L = Lc;
         base = lds_raw;
     }
-    Mem<idx_t> M = carve<idx_t>(base, L, NMr, MMr, LWL);
+    Mem<idx_t> M = carve<idx_t>(base, L, NMr, MMr);
     M.stats = p.stats;
     if constexpr (HUGE) { M.lds_swap = p.huge_lds > 0 ? lds_raw : nullptr; M.lds_swap_bytes = (size_t)p.huge_lds; }
     const int res = p.res, res2 = res * res;
 
-    // Issue priority by LDS per wavefront (development A/B, make EXTRA="-DTLC_PRIO_LARGE=3 ..."; default 0 = none): in a pipelined
-    // batch a tier costs LDS capacity x time, so a wavefront that holds much LDS should get through first.  Measured
-    // (tools/gpu_build_ab3.sh, TINY 3 / LARGE 3 / MEDIUM 2 / MID 1 / SMALL 1 and subsets, four builds in turn): 0.649 - 0.664 ms per
-    // pipelined batch whatever the setting -- the SIMDs are not contended enough for issue arbitration to matter
-#ifndef TLC_PRIO_LARGE
-#define TLC_PRIO_LARGE 0
-#endif
-#ifndef TLC_PRIO_MEDIUM
-#define TLC_PRIO_MEDIUM 0
-#endif
-#ifndef TLC_PRIO_MID
-#define TLC_PRIO_MID 0
-#endif
-#ifndef TLC_PRIO_SMALL
-#define TLC_PRIO_SMALL 0
-#endif
-    if constexpr (!HUGE) {
-        constexpr int prio = (NM == TLC_L_NMAX) ? TLC_PRIO_LARGE : ((NM == TLC_M_NMAX || NM == TLC_C_NMAX) ? TLC_PRIO_MEDIUM : (NM == TLC_D_NMAX ? TLC_PRIO_MID : TLC_PRIO_SMALL));
-        if constexpr (prio > 0) __builtin_amdgcn_s_setprio(prio);
-    }
+    // (no s_setprio: issue priorities by LDS per wavefront were measured, 0.649 - 0.664 ms per pipelined batch whatever the setting)
     // this workgroup is resident: tell the launcher's gate (api.hip, tlc_wait_started)
     if (p.abort_flag && *p.abort_flag) return;
     int tier_count = p.tier_count;
@@ -1594,11 +1532,9 @@ __global__ __launch_bounds__(W, (W == 256 && !HUGE ? (NM == TLC_C_NMAX ? 6 : TLC
         if (slot && tid == 0) *(int*)slot = 0;
         if (i < 0) continue;              // (a slot of the early arena whose vicinity turned out not to be of this tier: extract.hip)
         const int n = p.hdr_n[i], m2 = p.hdr_m2[i], lu = p.hdr_lu[i], lv = p.hdr_lv[i];
-#ifndef TLC_NO_SIZE_ASSUME
         // (the scan bins a vicinity by these sizes: told to the compiler, a `for (k = tid; k < n; k += W)` of a tier with NM <= W is
         // an `if`, and the entry loops have a known maximum trip count)
         if constexpr (!HUGE) { __builtin_assume(n >= 1 && n <= NM); __builtin_assume(m2 >= 0 && m2 <= 2 * MM); }
-#endif
         const long long eo = p.slot_entries ? (long long)wi * p.slot_entries : p.edge_off[i];
         const int m = m2 >> 1;
         const bool far = (lu < 0);        // u in S <=> v in S <=> d(u,v) <= hop  
@@ -1617,21 +1553,18 @@ __global__ __launch_bounds__(W, (W == 256 && !HUGE ? (NM == TLC_C_NMAX ? 6 : TLC
         const bool in_small = (NM == TLC_S_NMAX && !HUGE && p.small_dir != nullptr);
         const unsigned* adir = in_small ? p.small_dir + (size_t)i * (2 * TLC_S_MMAX) : p.A_dir + eo;
         const double* alw = in_small ? p.small_lw + (size_t)i * (2 * TLC_S_MMAX) : p.A_lw + eo;
-        for (int j = tid; j < m2; j += W) {
-            M.dir[j] = adir[j];
-            if (LWL) M.lw[j] = alw[j];
-        }
+        for (int j = tid; j < m2; j += W) M.dir[j] = adir[j];
         ull* du = (ull*)M.f;
         for (int k = tid; k < n; k += W) { du[k] = TLC_INF_BITS; M.dv[k] = TLC_INF_BITS; }
         if (tid == 0) M.ctl[1] = 0;
         __syncthreads();
         const double* glw = alw;
-        auto LW = [&](int j) -> double { return LWL ? M.lw[j] : glw[j]; };
+        auto LW = [&](int j) -> double { return glw[j]; };
         // tiers whose weights stay in HBM/L2: Bellman-Ford keeps a thread's entries in registers, and the weight of every
         // node's tight successor entry goes to LDS beside its index (the Pos/Neg and point lists are not live yet), so that
         // neither the rounds nor the chain walks wait for global memory
-        constexpr int BF_CE = (!LWL && !HUGE) ? (2 * MM + W - 1) / W : 0;
-        constexpr bool WTAB = !LWL && !HUGE;
+        constexpr int BF_CE = !HUGE ? (2 * MM + W - 1) / W : 0;
+        constexpr bool WTAB = !HUGE;
         // image slicing: the tiers that may hand a subgraph to tlc_pd_swap_kernel slice like that kernel does
         constexpr int PSW = (!HUGE && (NM == TLC_D_NMAX || NM == TLC_M_NMAX || NM == TLC_C_NMAX)) ? 64 : W;
         // (the tight-successor weight tables alias pn / pts: make_layout gives both NM doubles at least)
@@ -1840,8 +1773,7 @@ __global__ __launch_bounds__(W, (W == 256 && !HUGE ? (NM == TLC_C_NMAX ? 6 : TLC
             // (the compact LARGE kernels sort like the wide ones -- same run / merge decisions, so a vicinity's row does not depend on which of
             // the two took it)
             status = pd_all_stages<W, sort_hold(MM, W)>(M, sink, n, m, p.flags, MMr, NMr, pc, t_prev, ph, slot, deferred,
-                                      /*dc_mode=*/(!HUGE && (NM == TLC_L_NMAX)) ? TLC_DC_LARGE_MODE
-                                                  : ((!HUGE && NM == TLC_M_NMAX) ? 2 : 0),     // (whether or not the launch carries a
+                                      /*dc_mode=*/(!HUGE && (NM == TLC_L_NMAX || NM == TLC_M_NMAX)) ? 2 : 0,     // (whether or not the launch carries a
                                       // dc list: marking a subgraph for the divide and conquer fixes the order of its tied descending
                                       // keys, and a row must not depend on whether tlc_pd_dc_kernel or the serial walk then answers)
                                       /*handoff_all=*/NM != TLC_L_NMAX);
@@ -1907,7 +1839,7 @@ __host__ __device__ constexpr SwapLayout make_swap_layout(int NM, int MM) {
     SwapLayout L{};
     // [0, o_rec): the swap tables; afterwards f[NM] and the image table (64 points per round at res 5)
     // (capacities up to 1 024 edges: the compact tables of ext1_walk_c)
-    size_t o = al16(smax((MM <= 1024 && TLC_SWAP_COMPACT) ? swap_table_c_bytes(NM) : swap_table_bytes(NM), (size_t)8 * NM + (size_t)64 * 13 * 8));
+    size_t o = al16(smax(MM <= 1024 ? swap_table_c_bytes(NM) : swap_table_bytes(NM), (size_t)8 * NM + (size_t)64 * 13 * 8));
     L.table_bytes = o - (size_t)8 * NM;
     L.o_rec = o;  o += 1280;
     L.o_pts = o;  o += al16((size_t)(MM + 2) * 4);
@@ -1934,7 +1866,7 @@ __device__ __forceinline__ void swap_subgraph(const TlcPdParams& p, int wi, unsi
 #endif
     for (int k = tid; k < np0; k += W) pts[k] = H.pts[k];
     PtsSink sink{pts, ctl};
-    if constexpr (MM <= 1024 && TLC_SWAP_COMPACT) {
+    if constexpr (MM <= 1024) {
         // compact tables (ext1_walk_c): (rank + 1) << 16 | parent per node, "not in the tree" = 0xffff; slot NM = the spare node above the root
         const SwapTablesC T = carve_swap_c(lds_raw, NM);
         unsigned* recs = (unsigned*)(lds_raw + L.o_rec);
@@ -2130,15 +2062,15 @@ __global__ __launch_bounds__(W) void tlc_pdf_tier_kernel(TlcPdfParams p) {
     int NMr, MMr;
     if constexpr (HUGE) {
         NMr = p.huge_nmax; MMr = p.huge_mmax;
-        L = make_layout(NMr, MMr, false, sizeof(idx_t), TLC_HUGE_MIN_TABLE);
+        L = make_layout(NMr, MMr, sizeof(idx_t), TLC_HUGE_MIN_TABLE);
         base = p.huge_scratch + (size_t)blockIdx.x * p.huge_stride;
     } else {
         NMr = NM; MMr = MM;
-        constexpr Layout Lc = make_layout(NM, MM, false, sizeof(idx_t));
+        constexpr Layout Lc = make_layout(NM, MM, sizeof(idx_t));
         L = Lc;
         base = lds_raw;
     }
-    Mem<idx_t> M = carve<idx_t>(base, L, NMr, MMr, false);
+    Mem<idx_t> M = carve<idx_t>(base, L, NMr, MMr);
     // (no loop around the body for the LDS tiers, whose launches have one workgroup per graph: see tlc_pd_tier_kernel)
     int wi = blockIdx.x;
     if (wi >= p.count) return;
@@ -2338,14 +2270,11 @@ __device__ __forceinline__ void raster_fold(const double (&acc)[R2], double (*st
 }
 
 // (three workgroups per CU need <= 168 VGPRs: at resolution 5 that costs 18 spilled VGPRs and 176 B of scratch per lane.  Two per CU
-// and no scratch -- make EXTRA=-DTLC_RASTER_OCC3_MAXRES=4 -- was measured in round 4 (tools/time_raster.py, same box): uniform
+// and no scratch at resolutions up to 5 was measured in round 4 (tools/time_raster.py, same box): uniform
 // 48-point diagrams 39.1 vs 38.8 us, the batch-shaped mix 86.0 vs 81.1, the erfc range 334 vs 300: the spills sit outside the
 // series loops and the third workgroup hides more latency than they cost.  Three stay.)
-#ifndef TLC_RASTER_OCC3_MAXRES
-#define TLC_RASTER_OCC3_MAXRES 5
-#endif
 template <int RES>
-__global__ __launch_bounds__(256, (RES <= TLC_RASTER_OCC3_MAXRES ? 3 : 2)) void tlc_pi_raster_kernel(int n_dgms, int dpb, const long long* __restrict__ offs,
+__global__ __launch_bounds__(256, (RES <= 5 ? 3 : 2)) void tlc_pi_raster_kernel(int n_dgms, int dpb, const long long* __restrict__ offs,
                                                             const double* __restrict__ pts, double* __restrict__ out) {
     constexpr int R2 = RES * RES;
     __shared__ long long s_k[16], s_o[16];
@@ -2451,11 +2380,11 @@ size_t tlc_handoff_slot_bytes(int tier) {
         // (LARGE keeps the serial cycle swap of its subgraphs with few Pos edges: they are few and the batch waits for the
         // slowest of them, which runs fastest with a CU to itself -- measured 0.91 vs 1.07 ms with the swap in the shared
         // one-wavefront kernel; only the subgraphs meant for tlc_pd_dc_kernel are handed off, into a buffer of their own)
-        case TLC_TIER_LARGE: return TLC_DC_LARGE_MODE == 2 ? handoff_bytes(TLC_L_NMAX, TLC_L_MMAX) : 0;
+        case TLC_TIER_LARGE: return handoff_bytes(TLC_L_NMAX, TLC_L_MMAX);
         default: return 0;
     }
 }
-size_t tlc_huge_slot_bytes(int nmax, int mmax) { return al16(make_layout(nmax, mmax, false, 2, TLC_HUGE_MIN_TABLE).total); }
+size_t tlc_huge_slot_bytes(int nmax, int mmax) { return al16(make_layout(nmax, mmax, 2, TLC_HUGE_MIN_TABLE).total); }
 
 template <class K>
 static int set_lds_limit(K kernel, size_t bytes) {
@@ -2463,9 +2392,6 @@ static int set_lds_limit(K kernel, size_t bytes) {
     return TLC_OK;
 }
 
-#ifndef TLC_C_THREADS
-#define TLC_C_THREADS 256          /* threads of the compact MEDIUM tier kernel (128 measured: see DESIGN_HISTORY.md, round 6) */
-#endif
 int tlc_launch_pd_tier(int tier, const TlcPdParams& p, void* stream) {
     hipStream_t s = (hipStream_t)stream;
     if (p.tier_count <= 0) return TLC_OK;
@@ -2479,36 +2405,34 @@ int tlc_launch_pd_tier(int tier, const TlcPdParams& p, void* stream) {
         static int once = 0;
         if (!once++)
             fprintf(stderr, "[tlc] LDS per workgroup: SMALL %zu | MEDIUM tier %zu swap %zu | MEDWIDE tier %zu swap %zu | MID tier %zu swap %zu | LARGE tier %zu dc %zu\n",
-                    (size_t)make_layout(TLC_S_NMAX, TLC_S_MMAX, TLC_SMALL_LWL, 2).total, (size_t)make_layout(TLC_C_NMAX, TLC_C_MMAX, false, 2).total,
-                    (size_t)make_swap_layout(TLC_C_NMAX, TLC_C_MMAX).total, (size_t)make_layout(TLC_M_NMAX, TLC_M_MMAX, false, 2).total,
-                    (size_t)make_swap_layout(TLC_M_NMAX, TLC_M_MMAX).total, (size_t)make_layout(TLC_D_NMAX, TLC_D_MMAX, false, 2).total,
-                    (size_t)make_swap_layout(TLC_D_NMAX, TLC_D_MMAX).total, (size_t)make_layout(TLC_L_NMAX, TLC_L_MMAX, false, 2).total,
+                    (size_t)make_layout(TLC_S_NMAX, TLC_S_MMAX, 2).total, (size_t)make_layout(TLC_C_NMAX, TLC_C_MMAX, 2).total,
+                    (size_t)make_swap_layout(TLC_C_NMAX, TLC_C_MMAX).total, (size_t)make_layout(TLC_M_NMAX, TLC_M_MMAX, 2).total,
+                    (size_t)make_swap_layout(TLC_M_NMAX, TLC_M_MMAX).total, (size_t)make_layout(TLC_D_NMAX, TLC_D_MMAX, 2).total,
+                    (size_t)make_swap_layout(TLC_D_NMAX, TLC_D_MMAX).total, (size_t)make_layout(TLC_L_NMAX, TLC_L_MMAX, 2).total,
                     (size_t)dc_kernel_lds(TLC_L_NMAX, TLC_L_MMAX));
     }
     switch (tier) {
         case TLC_TIER_SMALL: {
-            constexpr Layout L = make_layout(TLC_S_NMAX, TLC_S_MMAX, TLC_SMALL_LWL, 2);
-            // (development: TLC_SMALL_LDS_PAD=bytes inflates this tier's footprint -- the experiment behind DESIGN.md's "the tier
-            // phase is bound by LDS capacity x time": +4 KB here costs the batch 2.5 %, +16 KB 20 %)
-            static const size_t pad = getenv("TLC_SMALL_LDS_PAD") ? (size_t)atoi(getenv("TLC_SMALL_LDS_PAD")) : 0;
+            constexpr Layout L = make_layout(TLC_S_NMAX, TLC_S_MMAX, 2);
+            // (this tier's footprint is what DESIGN.md's "the tier phase is bound by LDS capacity x time" measured: 4 KB more of it
+            // cost the batch 2.5 %, 16 KB more 20 %)
             if (plain)
-                hipLaunchKernelGGL((tlc_pd_tier_kernel<TLC_S_NMAX, TLC_S_MMAX, 64, TLC_SMALL_LWL, false, true>), dim3(p.tier_count), dim3(64),
-                                   L.total + pad, s, p);
+                hipLaunchKernelGGL((tlc_pd_tier_kernel<TLC_S_NMAX, TLC_S_MMAX, 64, false, true>), dim3(p.tier_count), dim3(64),
+                                   L.total, s, p);
             else
-                hipLaunchKernelGGL((tlc_pd_tier_kernel<TLC_S_NMAX, TLC_S_MMAX, 64, TLC_SMALL_LWL, false>), dim3(p.tier_count), dim3(64),
-                                   L.total + pad, s, p);
+                hipLaunchKernelGGL((tlc_pd_tier_kernel<TLC_S_NMAX, TLC_S_MMAX, 64, false>), dim3(p.tier_count), dim3(64),
+                                   L.total, s, p);
             break;
         }
         case TLC_TIER_MEDIUM: {
-            constexpr Layout L = make_layout(TLC_C_NMAX, TLC_C_MMAX, false, 2);
-            static const size_t mpad = getenv("TLC_MEDIUM_LDS_PAD") ? (size_t)atoi(getenv("TLC_MEDIUM_LDS_PAD")) : 0;
+            constexpr Layout L = make_layout(TLC_C_NMAX, TLC_C_MMAX, 2);   // (256 threads; 128 measured: DESIGN_HISTORY.md, round 6)
             if (p.phase != 2) {
                 if (plain)
-                    hipLaunchKernelGGL((tlc_pd_tier_kernel<TLC_C_NMAX, TLC_C_MMAX, TLC_C_THREADS, false, false, true>), dim3(grid),
-                                       dim3(TLC_C_THREADS), L.total + mpad, s, p);
+                    hipLaunchKernelGGL((tlc_pd_tier_kernel<TLC_C_NMAX, TLC_C_MMAX, 256, false, true>), dim3(grid),
+                                       dim3(256), L.total, s, p);
                 else
-                    hipLaunchKernelGGL((tlc_pd_tier_kernel<TLC_C_NMAX, TLC_C_MMAX, TLC_C_THREADS, false, false>), dim3(grid),
-                                       dim3(TLC_C_THREADS), L.total + mpad, s, p);
+                    hipLaunchKernelGGL((tlc_pd_tier_kernel<TLC_C_NMAX, TLC_C_MMAX, 256, false>), dim3(grid),
+                                       dim3(256), L.total, s, p);
             }
             if (deferring && p.phase != 1) {
                 constexpr SwapLayout SL = make_swap_layout(TLC_C_NMAX, TLC_C_MMAX);
@@ -2519,16 +2443,15 @@ int tlc_launch_pd_tier(int tier, const TlcPdParams& p, void* stream) {
         }
         case TLC_TIER_MEDHI:
         case TLC_TIER_MEDWIDE: {
-            constexpr Layout L = make_layout(TLC_M_NMAX, TLC_M_MMAX, false, 2);
-            // (development: TLC_MEDIUM_LDS_PAD=bytes -- how much does this tier's footprint cost?  37.5 KB = four workgroups per CU)
-            static const size_t mpad = getenv("TLC_MEDIUM_LDS_PAD") ? (size_t)atoi(getenv("TLC_MEDIUM_LDS_PAD")) : 0;
+            constexpr Layout L = make_layout(TLC_M_NMAX, TLC_M_MMAX, 2);
+            // (37.5 KB = four workgroups per CU)
             if (p.phase != 2) {
                 if (plain)
-                    hipLaunchKernelGGL((tlc_pd_tier_kernel<TLC_M_NMAX, TLC_M_MMAX, 256, false, false, true>), dim3(grid),
-                                       dim3(256), L.total + mpad, s, p);
+                    hipLaunchKernelGGL((tlc_pd_tier_kernel<TLC_M_NMAX, TLC_M_MMAX, 256, false, true>), dim3(grid),
+                                       dim3(256), L.total, s, p);
                 else
-                    hipLaunchKernelGGL((tlc_pd_tier_kernel<TLC_M_NMAX, TLC_M_MMAX, 256, false, false>), dim3(grid),
-                                       dim3(256), L.total + mpad, s, p);
+                    hipLaunchKernelGGL((tlc_pd_tier_kernel<TLC_M_NMAX, TLC_M_MMAX, 256, false>), dim3(grid),
+                                       dim3(256), L.total, s, p);
             }
             // (a dc list on the launch: the scan counted vicinities with Pos edges enough -- dense hop-1 vicinities of the Amazon
             // shapes, 600 Pos edges on 80 nodes -- and the tier kernel marked them; the rest stay for the swap kernel behind)
@@ -2544,42 +2467,37 @@ int tlc_launch_pd_tier(int tier, const TlcPdParams& p, void* stream) {
             break;
         }
         case TLC_TIER_MID: {
-            constexpr Layout L = make_layout(TLC_D_NMAX, TLC_D_MMAX, false, 2);
+            constexpr Layout L = make_layout(TLC_D_NMAX, TLC_D_MMAX, 2);
             if (p.phase != 2) {
                 if (plain)
-                    hipLaunchKernelGGL((tlc_pd_tier_kernel<TLC_D_NMAX, TLC_D_MMAX, TLC_D_THREADS, false, false, true>), dim3(grid),
+                    hipLaunchKernelGGL((tlc_pd_tier_kernel<TLC_D_NMAX, TLC_D_MMAX, TLC_D_THREADS, false, true>), dim3(grid),
                                        dim3(TLC_D_THREADS), L.total, s, p);
                 else
-                    hipLaunchKernelGGL((tlc_pd_tier_kernel<TLC_D_NMAX, TLC_D_MMAX, TLC_D_THREADS, false, false>), dim3(grid),
+                    hipLaunchKernelGGL((tlc_pd_tier_kernel<TLC_D_NMAX, TLC_D_MMAX, TLC_D_THREADS, false>), dim3(grid),
                                        dim3(TLC_D_THREADS), L.total, s, p);
             }
             break;                                                    // (no hand-off: tlc_handoff_slot_bytes)
         }
         case TLC_TIER_LARGE: {
-            constexpr Layout L = make_layout(TLC_L_NMAX, TLC_L_MMAX, false, 2);
-            // the whole CU: no SMALL workgroup beside the wavefront that carries the batch's longest serial chain
-            // (bit 0: this kernel, bit 1: the divide-and-conquer kernel behind it.  The latter no longer does: with 107 of 160 KB a
-            // TINY workgroup fits beside it, 0.838 -> 0.818 ms for the PubMed batch; development A/B: tools/gpu_large_excl.sh)
-            // Round 5: off by default.  With the divide and conquer in place a LARGE workgroup holds its CU for ~0.49 ms of a 0.53 ms
-            // pipelined batch (71 of them: 0.065 ms of the batch, profiles/r05_tier_cost_pipelined.txt); the 15 KB its 145 KB leave are
-            // room for two SMALL or one MID / swap workgroup: pipelined batch 0.526 -> 0.517 ms (two alternating runs), one batch alone equal.
-            static const int excl = getenv("TLC_LARGE_EXCL") ? atoi(getenv("TLC_LARGE_EXCL")) : 0;
-            const size_t lds_bytes = (L.total > 156 * 1024 || !(excl & 1)) ? L.total : 156 * 1024;
-            int rc = plain ? set_lds_limit(tlc_pd_tier_kernel<TLC_L_NMAX, TLC_L_MMAX, TLC_L_THREADS, false, false, true>, lds_bytes)
-                           : set_lds_limit(tlc_pd_tier_kernel<TLC_L_NMAX, TLC_L_MMAX, TLC_L_THREADS, false, false>, lds_bytes);
+            constexpr Layout L = make_layout(TLC_L_NMAX, TLC_L_MMAX, 2);
+            // (each kernel asks for its own LDS only, not the whole CU.  Measured: with the divide-and-conquer kernel's 107 of 160 KB a
+            // TINY workgroup fits beside it, 0.838 -> 0.818 ms for the PubMed batch; a LARGE workgroup holds its CU for ~0.49 ms of a
+            // 0.53 ms pipelined batch (71 of them: 0.065 ms of the batch, profiles/r05_tier_cost_pipelined.txt), and the 15 KB its
+            // 145 KB leave are room for two SMALL or one MID / swap workgroup: pipelined batch 0.526 -> 0.517 ms, one batch alone equal)
+            const size_t lds_bytes = L.total;
+            int rc = plain ? set_lds_limit(tlc_pd_tier_kernel<TLC_L_NMAX, TLC_L_MMAX, TLC_L_THREADS, false, true>, lds_bytes)
+                           : set_lds_limit(tlc_pd_tier_kernel<TLC_L_NMAX, TLC_L_MMAX, TLC_L_THREADS, false>, lds_bytes);
             if (rc) return rc;
             if (plain)
-                hipLaunchKernelGGL((tlc_pd_tier_kernel<TLC_L_NMAX, TLC_L_MMAX, TLC_L_THREADS, false, false, true>), dim3(p.tier_count),
+                hipLaunchKernelGGL((tlc_pd_tier_kernel<TLC_L_NMAX, TLC_L_MMAX, TLC_L_THREADS, false, true>), dim3(p.tier_count),
                                    dim3(TLC_L_THREADS), lds_bytes, s, p);
             else
-                hipLaunchKernelGGL((tlc_pd_tier_kernel<TLC_L_NMAX, TLC_L_MMAX, TLC_L_THREADS, false, false>), dim3(p.tier_count),
+                hipLaunchKernelGGL((tlc_pd_tier_kernel<TLC_L_NMAX, TLC_L_MMAX, TLC_L_THREADS, false>), dim3(p.tier_count),
                                    dim3(TLC_L_THREADS), lds_bytes, s, p);
             if (deferring) {
                 // (only the subgraphs marked for the divide and conquer were handed off; tlc_pd_dc_kernel runs the serial walk itself
                 // for those it gives back)
-                // (its own 107 KB only, see above)
-                const size_t dcl = (dc_kernel_lds(TLC_L_NMAX, TLC_L_MMAX) > 156 * 1024 || !(excl & 2)) ? dc_kernel_lds(TLC_L_NMAX, TLC_L_MMAX) : 156 * 1024;
-                if (host_trace) { static int once = 0; if (!once++) fprintf(stderr, "[tlc] LARGE tier LDS %zu (layout %zu), dc %zu (layout %zu)\n", lds_bytes, (size_t)L.total, dcl, (size_t)dc_kernel_lds(TLC_L_NMAX, TLC_L_MMAX)); }
+                constexpr size_t dcl = dc_kernel_lds(TLC_L_NMAX, TLC_L_MMAX);
                 rc = set_lds_limit(tlc_pd_dc_kernel<TLC_L_NMAX, TLC_L_MMAX, TLC_L_THREADS>, dcl);
                 if (rc) return rc;
                 if (p.dc_count && !p.dc_inplace)
@@ -2592,12 +2510,13 @@ int tlc_launch_pd_tier(int tier, const TlcPdParams& p, void* stream) {
             if (p.huge_slots <= 0 || !p.huge_scratch) { tlc_set_error("HUGE tier without scratch"); return TLC_ERR_INVALID_ARG; }
             const int grid = p.tier_count < p.huge_slots ? p.tier_count : p.huge_slots;
             // (LDS for the cycle swap's tables: a HUGE workgroup takes a CU's LDS -- there are a handful of them in a batch, each
-            // the longest serial chain of it; TLC_HUGE_LDS=0: the tables stay in the scratch slot, development A/B)
-            static const int huge_lds = getenv("TLC_HUGE_LDS") ? atoi(getenv("TLC_HUGE_LDS")) : 144 * 1024;
+            // the longest serial chain of it)
+            constexpr int huge_lds = 144 * 1024;
             TlcPdParams q = p;
             q.huge_lds = huge_lds;
-            if (huge_lds > 0) { int rc = set_lds_limit(tlc_pd_tier_kernel<0, 0, 256, false, true>, (size_t)huge_lds); if (rc) return rc; }
-            hipLaunchKernelGGL((tlc_pd_tier_kernel<0, 0, 256, false, true>), dim3(grid), dim3(256), (size_t)huge_lds, s, q);
+            int rc = set_lds_limit(tlc_pd_tier_kernel<0, 0, 256, true>, (size_t)huge_lds);
+            if (rc) return rc;
+            hipLaunchKernelGGL((tlc_pd_tier_kernel<0, 0, 256, true>), dim3(grid), dim3(256), (size_t)huge_lds, s, q);
             break;
         }
         default:
@@ -2613,17 +2532,17 @@ int tlc_launch_pdf_tier(int tier, const TlcPdfParams& p, void* stream) {
     if (p.count <= 0) return TLC_OK;
     switch (tier) {
         case TLC_TIER_SMALL: {
-            constexpr Layout L = make_layout(TLC_S_NMAX, TLC_S_MMAX, false, 2);
+            constexpr Layout L = make_layout(TLC_S_NMAX, TLC_S_MMAX, 2);
             hipLaunchKernelGGL((tlc_pdf_tier_kernel<TLC_S_NMAX, TLC_S_MMAX, 64, false>), dim3(p.count), dim3(64), L.total, s, p);
             break;
         }
         case TLC_TIER_MEDIUM: {
-            constexpr Layout L = make_layout(TLC_M_NMAX, TLC_M_MMAX, false, 2);
+            constexpr Layout L = make_layout(TLC_M_NMAX, TLC_M_MMAX, 2);
             hipLaunchKernelGGL((tlc_pdf_tier_kernel<TLC_M_NMAX, TLC_M_MMAX, 256, false>), dim3(p.count), dim3(256), L.total, s, p);
             break;
         }
         case TLC_TIER_LARGE: {
-            constexpr Layout L = make_layout(TLC_L_NMAX, TLC_L_MMAX, false, 2);
+            constexpr Layout L = make_layout(TLC_L_NMAX, TLC_L_MMAX, 2);
             int rc = set_lds_limit(tlc_pdf_tier_kernel<TLC_L_NMAX, TLC_L_MMAX, 512, false>, L.total);
             if (rc) return rc;
             hipLaunchKernelGGL((tlc_pdf_tier_kernel<TLC_L_NMAX, TLC_L_MMAX, 512, false>), dim3(p.count), dim3(512), L.total, s, p);

@@ -20,7 +20,7 @@
 #define TLC_TIER_MEDHI 6    /* a chunk on its own only: the MEDIUM-sized vicinities with many Pos edges or beyond the compact configuration
                                (reported with MEDIUM): the wide kernels, launched FIRST and on the critical stream, so that their long
                                serial cycle swaps overlap the rest of the MEDIUM tier */
-#ifndef TLC_MH_MIN_POS             /* (overridable for the threshold sweep: tools/gpu_threshold_sweep.sh) */
+#ifndef TLC_MH_MIN_POS             /* (overridable for a threshold sweep: make EXTRA=-DTLC_MH_MIN_POS=n) */
 #define TLC_MH_MIN_POS 120
 #endif
 #define TLC_TIER_TINY 5     /* the lower end of SMALL (reported with it): ONE LANE per subgraph, 64 subgraphs per wavefront (pd_tiny.hip) */

@@ -1,5 +1,5 @@
 """Device time of the sparse feature projection (tlc_spgemm_csr_dense_f32) on the bench workload's features, replayed from a graph of
-20 calls (a Python call costs more than the kernel), next to the dense MFMA kernel.  Used with tools/gpu_spgemm_diag.sh."""
+20 calls (a Python call costs more than the kernel), next to the dense MFMA kernel."""
 import sys, os
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
