@@ -329,6 +329,48 @@ int tlc_lp_decode_bwd_f32(int64_t n_pairs, const int32_t* d_pairs, const float* 
                           const float* d_W2, const float* d_b2, const float* d_gprob, const int32_t* d_node_ptr,
                           const int32_t* d_node_slots, float* d_gemb, float* d_gw, float* d_work, void* stream);
 
+/* ---- Node classification: curvGN of Knowledge_Distillation/ConvCurv_GIN.py:149-185 (nc_curv.hip) ---------------------------------
+ * out[t] = sum over the edges e with edge_index[1][e] = t of alpha[e] * xl[edge_index[0][e]] (per channel), xl = x W^T + b, and
+ * alpha = softmax of wt = W2 PReLU(W1 w_mul[e]) + b2 over the edges of one SOURCE, per channel (PyG's softmax: max, exp, / (sum + 1e-16)).
+ * f32 throughout; C (channels) 1..256, D (w_mul width) 1..64, any F; E < 2^31.  Every call is asynchronous on `stream`, never waits
+ * for the host and uses no floating-point atomics: the same inputs give bit-identical results on every call.  Bad sizes / NULL
+ * pointers: TLC_ERR_INVALID_ARG; C, D or E beyond the built range: TLC_ERR_UNSUPPORTED. */
+
+/* Scratch (int32 words) of the grouping: 2 n_nodes + 4 n_edges; -1 for bad sizes. */
+int64_t tlc_nc_group_work_ints(int32_t n_nodes, int64_t n_edges);
+
+/* Group the edge ids of d_edge_index int64[2,E] (row 0 source, row 1 target) by source and by target, a stable counting sort (edge ids
+ * ascending inside a row); edges are kept as given (duplicates and self loops stay).  Out: d_groups int32[2 (n_nodes + 1) + 4 E] =
+ * src_ptr[n+1] | tgt_ptr[n+1] | src_eid[E] | tgt_eid[E] | src[E] | dst[E].  d_bad int32[1] = the number of edges with an id outside
+ * [0, n_nodes) (read it before using the grouping: such edges are left out).  d_work int32 scratch (tlc_nc_group_work_ints). */
+int tlc_nc_group(int32_t n_nodes, int64_t n_edges, const int64_t* d_edge_index, int32_t* d_groups, int32_t* d_work, int32_t* d_bad,
+                 void* stream);
+
+/* y[M,N] = x[M,K] W^T + b on the f32 MFMA: a Linear with weight d_w f32[N,K] and bias d_b f32[N] (NULL: none).  Any N and K. */
+int tlc_nc_linear_f32(int32_t M, int32_t N, int32_t K, const float* d_x, const float* d_w, const float* d_b, float* d_y, void* stream);
+
+/* Backward of tlc_nc_linear_f32 for d_gy f32[M,N]: d_gw f32[N,K] = gy^T x, d_gb f32[N] = column sums of gy (NULL: skipped), d_gx f32[M,K]
+ * = gy W (NULL: skipped).  Sums over M as fixed-order split-K products.  d_work float32[32 N max(K, 1)] scratch. */
+int tlc_nc_linear_bwd_f32(int32_t M, int32_t N, int32_t K, const float* d_x, const float* d_w, const float* d_gy, float* d_gx,
+                          float* d_gw, float* d_gb, float* d_work, void* stream);
+
+/* Workspace bytes of tlc_nc_curv_bwd_f32: 4 (3 E C + ceil(E / 64) C + 32 C max(C, D)); -1 for sizes outside the built range. */
+int64_t tlc_nc_curv_work_bytes(int32_t n_nodes, int64_t n_edges, int32_t C, int32_t D);
+
+/* Forward of curvGN after the projection: d_groups from tlc_nc_group; d_xl f32[n_nodes,C]; d_wmul f32[E,D]; the edge MLP
+ * create_wmlp([D, C], C, 1): d_w1 f32[C,D] (Linear, no bias), d_prelu f32[C] (PReLU slopes), d_w2 f32[C,C], d_b2 f32[C].
+ * Out: d_alpha f32[E,C] (kept for the backward), d_out f32[n_nodes,C]; a node without in-edges gets a zero row. */
+int tlc_nc_curv_fwd_f32(int32_t n_nodes, int64_t n_edges, int32_t C, int32_t D, const int32_t* d_groups, const float* d_xl,
+                        const float* d_wmul, const float* d_w1, const float* d_prelu, const float* d_w2, const float* d_b2, float* d_alpha,
+                        float* d_out, void* stream);
+
+/* Backward of tlc_nc_curv_fwd_f32 for d_gout f32[n_nodes,C] (d_alpha: the forward's): d_gxl f32[n_nodes,C], d_gw1 f32[C,D],
+ * d_gprelu f32[C], d_gw2 f32[C,C], d_gb2 f32[C].  The edge MLP is recomputed from d_wmul.  d_work: tlc_nc_curv_work_bytes bytes. */
+int tlc_nc_curv_bwd_f32(int32_t n_nodes, int64_t n_edges, int32_t C, int32_t D, const int32_t* d_groups, const float* d_xl,
+                        const float* d_wmul, const float* d_w1, const float* d_prelu, const float* d_w2, const float* d_alpha,
+                        const float* d_gout, float* d_gxl, float* d_gw1, float* d_gprelu, float* d_gw2, float* d_gb2, void* d_work,
+                        int64_t work_bytes, void* stream);
+
 /* ---- Link-prediction scoring (pipelines.py:20-40: roc_auc_score / average_precision_score) ----------------------------------
  * Binary ranking metrics per segment, with sklearn's binary semantics (pos_label 1): scores in descending order, equal scores one
  * threshold, -0.0 == +0.0.  AUC = U2 / (2 P N) with one rounding, U2 = sum over tie groups g of p_g (2 N_below,g + n_g) exact in

@@ -26,7 +26,9 @@ SYMBOLS = [
     "tlc_version", "tlc_last_error", "tlc_device_count", "tlc_graph_create", "tlc_graph_destroy",
     "tlc_pd_pi_batch", "tlc_pd_pi_batch_async", "tlc_pd_pi_batch_join", "tlc_vicinity_filtration", "tlc_pd_pi_batch_stats", "tlc_pd_pi_batch_set_timing",
     "tlc_pd_pi_batch_timings", "tlc_pd_pi_batch_timing_history", "tlc_pd_pi_batch_sizes", "tlc_pd_pi_algorithmic_bytes", "tlc_pd_from_filtration",
-    "tlc_pi_raster", "tlc_pi_raster_wgrad", "tlc_gcn_norm_csr", "tlc_gcn_norm_csr_t", "tlc_gemm_f32", "tlc_gemm_tn_f32", "tlc_lp_decode_bwd_f32", "tlc_binary_rank_metrics", "tlc_binary_rank_metrics_work_bytes", "tlc_spgemm_csr_dense_f32", "tlc_spmm_csr_f32", "tlc_renorm_rows_f32", "tlc_gcn2_encode_f32", "tlc_gcn2_encode_csr_f32",
+    "tlc_pi_raster", "tlc_pi_raster_wgrad", "tlc_gcn_norm_csr", "tlc_gcn_norm_csr_t", "tlc_gemm_f32", "tlc_gemm_tn_f32", "tlc_lp_decode_bwd_f32", "tlc_binary_rank_metrics", "tlc_binary_rank_metrics_work_bytes",
+    "tlc_nc_group_work_ints", "tlc_nc_group", "tlc_nc_linear_f32", "tlc_nc_linear_bwd_f32", "tlc_nc_curv_work_bytes", "tlc_nc_curv_fwd_f32",
+    "tlc_nc_curv_bwd_f32", "tlc_spgemm_csr_dense_f32", "tlc_spmm_csr_f32", "tlc_renorm_rows_f32", "tlc_gcn2_encode_f32", "tlc_gcn2_encode_csr_f32",
     "tlc_lp_decode_fused", "tlc_lp_decode_fused_f32", "tlc_gat_layer_fwd", "tlc_gat_layer_tiled_fwd", "tlc_gat_tile_cut", "tlc_csr_by_target", "tlc_pdgnn_forward", "tlc_pdgnn_forward_work_bytes", "tlc_scatter_f32", "tlc_edge_head_fwd",
     "tlc_complement_rows", "tlc_complement_pairs", "tlc_select_rows", "tlc_pack_vicinities", "tlc_stack_batch", "tlc_ollivier_ricci_sinkhorn",
     "tlc_near_pairs", "tlc_w2_partial_matching", "tlc_w2_inference_matching", "tlc_gat_layer_bwd", "tlc_edge_head_bwd", "tlc_pack_offsets", "tlc_vicinity_sizes", "tlc_debug_dc_stats", "tlc_debug_tier_counts", "tlc_debug_chunk_counters", "tlc_debug_phase_profile", "tlc_debug_set_option", "tlc_debug_pair_times",
@@ -115,6 +117,16 @@ def lib():
             L.tlc_binary_rank_metrics_work_bytes.restype = C.c_int64
             L.tlc_binary_rank_metrics.argtypes = ([C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int32, C.c_uint32]
                                                   + [C.c_void_p] * 6 + [C.c_int64, C.c_void_p])
+        if hasattr(L, "tlc_nc_group"):
+            L.tlc_nc_group_work_ints.argtypes = [C.c_int32, C.c_int64]
+            L.tlc_nc_group_work_ints.restype = C.c_int64
+            L.tlc_nc_group.argtypes = [C.c_int32, C.c_int64] + [C.c_void_p] * 5
+            L.tlc_nc_linear_f32.argtypes = [C.c_int32] * 3 + [C.c_void_p] * 5
+            L.tlc_nc_linear_bwd_f32.argtypes = [C.c_int32] * 3 + [C.c_void_p] * 8
+            L.tlc_nc_curv_work_bytes.argtypes = [C.c_int32, C.c_int64, C.c_int32, C.c_int32]
+            L.tlc_nc_curv_work_bytes.restype = C.c_int64
+            L.tlc_nc_curv_fwd_f32.argtypes = [C.c_int32, C.c_int64, C.c_int32, C.c_int32] + [C.c_void_p] * 10
+            L.tlc_nc_curv_bwd_f32.argtypes = [C.c_int32, C.c_int64, C.c_int32, C.c_int32] + [C.c_void_p] * 14 + [C.c_int64, C.c_void_p]
         if hasattr(L, "tlc_gat_layer_fwd"):
             L.tlc_gat_layer_fwd.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p,

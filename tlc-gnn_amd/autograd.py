@@ -1,6 +1,7 @@
 """Autograd glue for PDGNN training: `loss.backward()` of the reference's training loop
 (Knowledge_Distillation/train_Teacher_Model.py:55-62) through the HIP kernels; and for the TLCGNN link-prediction step
-(pipelines.py:10-18): GcnLayer and LpDecode, used by pipelines.train through Net's private training forward.
+(pipelines.py:10-18): GcnLayer and LpDecode, used by pipelines.train through Net's private training forward; and for the node
+classifier of Knowledge_Distillation/ConvCurv_GIN.py: CurvConv and NcLinear (nc_curv.hip).
 
 torch.autograd only carries the graph: every forward and every backward below is one C-ABI call (`tlc_gat_layer_fwd/_bwd`,
 `tlc_edge_head_fwd/_bwd`, `tlc_w2_partial_matching`, `tlc_pi_raster` / `tlc_pi_raster_wgrad`) or a few (`tlc_gemm_f32` /
@@ -185,3 +186,49 @@ def gcn_layer(x, weight, bias, op, op_t, relu=False):
 
 def lp_decode(emb, pairs, pi, w1, b1, w2, b2):
     return LpDecode.apply(emb, pairs, pi, w1, b1, w2, b2)
+
+
+class CurvConv(torch.autograd.Function):
+    """curvGN.forward (Knowledge_Distillation/ConvCurv_GIN.py:159-170) without the skip branch: xl = lin(x) (tlc_nc_linear_f32), the
+    edge MLP, the softmax grouped by source and the aggregation at the target (tlc_nc_curv_fwd_f32).  Backward: tlc_nc_curv_bwd_f32
+    -> d xl and the edge MLP's gradients, then tlc_nc_linear_bwd_f32 -> dx, d lin.weight, d lin.bias.  w_mul gets no gradient (the
+    reference computes it under no_grad from a frozen teacher)."""
+
+    @staticmethod
+    def forward(ctx, x, lin_w, lin_b, w1, prelu, w2, b2, w_mul, groups):
+        xd = x.detach().contiguous()
+        xl = ops.nc_linear(xd, lin_w.detach(), lin_b.detach())
+        out, alpha = ops.nc_curv_fwd(groups, xl, w_mul, w1.detach(), prelu.detach(), w2.detach(), b2.detach())
+        ctx.save_for_backward(xd, lin_w, xl, w_mul, w1, prelu, w2, alpha, groups)
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        xd, lin_w, xl, w_mul, w1, prelu, w2, alpha, groups = ctx.saved_tensors
+        gxl, gw1, gp, gw2, gb2 = ops.nc_curv_bwd(groups, xl, w_mul, w1.detach(), prelu.detach(), w2.detach(), alpha, gout.contiguous())
+        gx, gw, gb = ops.nc_linear_bwd(xd, lin_w.detach(), gxl, need_gx=ctx.needs_input_grad[0])
+        return gx, gw, gb, gw1, gp, gw2, gb2, None, None
+
+
+class NcLinear(torch.autograd.Function):
+    """torch.nn.Linear on tlc_nc_linear_f32 / tlc_nc_linear_bwd_f32 (curvGN's lin1 of the skip branches, ConvCurv_GIN.py:161)."""
+
+    @staticmethod
+    def forward(ctx, x, w, b):
+        xd = x.detach().contiguous()
+        ctx.save_for_backward(xd, w)
+        return ops.nc_linear(xd, w.detach(), b.detach())
+
+    @staticmethod
+    def backward(ctx, gy):
+        xd, w = ctx.saved_tensors
+        gx, gw, gb = ops.nc_linear_bwd(xd, w.detach(), gy.contiguous(), need_gx=ctx.needs_input_grad[0])
+        return gx, gw, gb
+
+
+def curv_conv(x, lin_w, lin_b, w1, prelu, w2, b2, w_mul, groups):
+    return CurvConv.apply(x, lin_w, lin_b, w1, prelu, w2, b2, w_mul, groups)
+
+
+def nc_linear(x, w, b):
+    return NcLinear.apply(x, w, b)

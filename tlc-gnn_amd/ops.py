@@ -336,6 +336,110 @@ def lp_decode_bwd(pairs, emb_pre, emb, pi, w1, b1, w2, b2, gprob, groups=None):
     return gemb, gw[:1025].view(25, 41), gw[1025:1050], gw[1050:1075].view(1, 25), gw[1075:1076]
 
 
+# ---- node classification: curvGN (nc_curv.hip; autograd.CurvConv / autograd.NcLinear, Knowledge_Distillation/ConvCurv_GIN.py) --
+@_lib.on_device_of
+def nc_group(edge_index, num_nodes):
+    """The edges of edge_index int64 CUDA [2,E] grouped by source and by target (tlc_nc_group), built once per graph:
+    int32 [2 (n + 1) + 4 E] = src_ptr | tgt_ptr | src_eid | tgt_eid | src | dst.  Reads one int back (the count of ids outside
+    [0, num_nodes)) and raises ValueError if there are any."""
+    torch = _lib.require_gpu()
+    assert edge_index.is_cuda and edge_index.dtype == torch.int64 and edge_index.dim() == 2 and edge_index.shape[0] == 2
+    ei = edge_index.contiguous()
+    E, n, dev = int(ei.shape[1]), int(num_nodes), ei.device
+    L = _lib.lib()
+    groups = torch.empty(2 * (n + 1) + 4 * E, dtype=torch.int32, device=dev)
+    work = torch.empty(max(1, int(L.tlc_nc_group_work_ints(C.c_int32(n), C.c_int64(E)))), dtype=torch.int32, device=dev)
+    bad = torch.empty(1, dtype=torch.int32, device=dev)
+    rc = L.tlc_nc_group(C.c_int32(n), C.c_int64(E), _lib.ptr(ei) if E else None, _lib.ptr(groups), _lib.ptr(work), _lib.ptr(bad),
+                        _lib.stream_ptr())
+    _lib.check(rc, "tlc_nc_group")
+    nbad = int(bad.item())
+    if nbad:
+        raise ValueError("nc_group: %d edge(s) with a node id outside [0, %d)" % (nbad, n))
+    return groups
+
+
+@_lib.on_device_of
+def nc_linear(x, w, b=None):
+    """x [M,K] @ w[N,K]^T + b on the f32 MFMA (tlc_nc_linear_f32): torch.nn.Linear's forward for any N and K."""
+    torch = _lib.require_gpu()
+    x, w = _f32(x), _f32(w)
+    M, K = x.shape
+    N = w.shape[0]
+    assert w.shape[1] == K
+    y = torch.empty((M, N), dtype=torch.float32, device=x.device)
+    rc = _lib.lib().tlc_nc_linear_f32(C.c_int32(M), C.c_int32(N), C.c_int32(K), _lib.ptr(x), _lib.ptr(w),
+                                      _lib.ptr(_f32(b)) if b is not None else None, _lib.ptr(y), _lib.stream_ptr())
+    _lib.check(rc, "tlc_nc_linear_f32")
+    return y
+
+
+@_lib.on_device_of
+def nc_linear_bwd(x, w, gy, need_gx=True):
+    """Backward of nc_linear (tlc_nc_linear_bwd_f32) -> (gx [M,K] or None, gw [N,K], gb [N])."""
+    torch = _lib.require_gpu()
+    x, w, gy = _f32(x), _f32(w), _f32(gy)
+    M, K = x.shape
+    N = w.shape[0]
+    dev = x.device
+    gx = torch.empty((M, K), dtype=torch.float32, device=dev) if need_gx else None
+    gw = torch.empty((N, K), dtype=torch.float32, device=dev)
+    gb = torch.empty(N, dtype=torch.float32, device=dev)
+    work = torch.empty(GEMM_TN_MAX_SPLITS * N * max(K, 1), dtype=torch.float32, device=dev)
+    rc = _lib.lib().tlc_nc_linear_bwd_f32(C.c_int32(M), C.c_int32(N), C.c_int32(K), _lib.ptr(x), _lib.ptr(w), _lib.ptr(gy), _lib.ptr(gx),
+                                          _lib.ptr(gw), _lib.ptr(gb), _lib.ptr(work), _lib.stream_ptr())
+    _lib.check(rc, "tlc_nc_linear_bwd_f32")
+    return gx, gw, gb
+
+
+def _nc_ptr(t):
+    return _lib.ptr(t) if t.numel() else None
+
+
+@_lib.on_device_of
+def nc_curv_fwd(groups, xl, w_mul, w1, prelu, w2, b2):
+    """curvGN after the projection (tlc_nc_curv_fwd_f32): groups from nc_group, xl f32 [n,C], w_mul f32 [E,D], the edge MLP's
+    w1 [C,D], prelu [C], w2 [C,C], b2 [C] -> (out [n,C], alpha [E,C])."""
+    torch = _lib.require_gpu()
+    xl, w_mul = _f32(xl), _f32(w_mul)
+    n, Cc = xl.shape
+    E, D = w_mul.shape
+    assert groups.numel() == 2 * (n + 1) + 4 * E, "groups were built for another graph"
+    out = torch.empty((n, Cc), dtype=torch.float32, device=xl.device)
+    alpha = torch.empty((E, Cc), dtype=torch.float32, device=xl.device)
+    rc = _lib.lib().tlc_nc_curv_fwd_f32(C.c_int32(n), C.c_int64(E), C.c_int32(Cc), C.c_int32(D), _lib.ptr(groups), _lib.ptr(xl),
+                                        _nc_ptr(w_mul), _lib.ptr(_f32(w1)), _lib.ptr(_f32(prelu)), _lib.ptr(_f32(w2)), _lib.ptr(_f32(b2)),
+                                        _nc_ptr(alpha), _lib.ptr(out), _lib.stream_ptr())
+    _lib.check(rc, "tlc_nc_curv_fwd_f32")
+    return out, alpha
+
+
+@_lib.on_device_of
+def nc_curv_bwd(groups, xl, w_mul, w1, prelu, w2, alpha, gout):
+    """Backward of nc_curv_fwd (tlc_nc_curv_bwd_f32) -> (d xl [n,C], d w1 [C,D], d prelu [C], d w2 [C,C], d b2 [C])."""
+    torch = _lib.require_gpu()
+    xl, w_mul, gout = _f32(xl), _f32(w_mul), _f32(gout)
+    n, Cc = xl.shape
+    E, D = w_mul.shape
+    dev = xl.device
+    L = _lib.lib()
+    nbytes = int(L.tlc_nc_curv_work_bytes(C.c_int32(n), C.c_int64(E), C.c_int32(Cc), C.c_int32(D)))
+    if nbytes < 0:
+        raise ValueError("nc_curv_bwd: C = %d (1..256) / D = %d (1..64) outside the built range" % (Cc, D))
+    work = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    gxl = torch.empty((n, Cc), dtype=torch.float32, device=dev)
+    gw1 = torch.empty((Cc, D), dtype=torch.float32, device=dev)
+    gp = torch.empty(Cc, dtype=torch.float32, device=dev)
+    gw2 = torch.empty((Cc, Cc), dtype=torch.float32, device=dev)
+    gb2 = torch.empty(Cc, dtype=torch.float32, device=dev)
+    rc = L.tlc_nc_curv_bwd_f32(C.c_int32(n), C.c_int64(E), C.c_int32(Cc), C.c_int32(D), _lib.ptr(groups), _lib.ptr(xl), _nc_ptr(w_mul),
+                               _lib.ptr(_f32(w1)), _lib.ptr(_f32(prelu)), _lib.ptr(_f32(w2)), _nc_ptr(_f32(alpha)), _lib.ptr(gout),
+                               _lib.ptr(gxl), _lib.ptr(gw1), _lib.ptr(gp), _lib.ptr(gw2), _lib.ptr(gb2), _lib.ptr(work), C.c_int64(nbytes),
+                               _lib.stream_ptr())
+    _lib.check(rc, "tlc_nc_curv_bwd_f32")
+    return gxl, gw1, gp, gw2, gb2
+
+
 # ---- link-prediction scoring (lp_metrics.hip; metrics.py, pipelines.test(metrics="device")) -----------------------------------
 RANK_LDS_CAP = 16384             # include/tlcgnn.h TLC_RANK_LDS_CAP: longer segments take the radix tier
 RANK_FORCE_RADIX = 0x1
