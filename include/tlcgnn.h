@@ -53,7 +53,12 @@ extern "C" {
 #define TLC_ST_ZERO_RANGE      3   /* ZeroDivisionError: all filtration values 0 (:54)              */
 #define TLC_ST_NO_TREE_EDGE    4   /* IndexError: single-node vicinity (accelerated_PD.py:122)      */
 #define TLC_ST_TOO_LARGE       5   /* not a reference class: the vicinity has more than 65 535 nodes or
-                                      2^24-2 edges (packed local ids / edge ranks); zero row, never silent */
+                                      2^24-2 edges (packed local ids / edge ranks); zero row, never silent.
+                                      tlc_hks_batch: the graph has more than TLC_HKS_NMAX nodes; its slice of
+                                      the output is left untouched */
+#define TLC_ST_NOT_CONVERGED   6   /* tlc_hks_batch: the Jacobi sweeps did not converge within their bound; slice untouched */
+#define TLC_ST_BAD_INPUT       7   /* tlc_hks_batch: offsets out of order / beyond the totals, an edge with an id outside
+                                      0 .. n-1 or a self loop (nothing of it is dereferenced); slice untouched */
 
 /* ---- variant flags (one kernel family serves the TLC-GNN and the PDGNN forks) ---- */
 #define TLC_KEEP_ZERO_PERS   0x01u /* Knowledge_Distillation/accelerated_PD.py:68-69,108-109,169-170 */
@@ -399,6 +404,33 @@ int64_t tlc_binary_rank_metrics_work_bytes(const int64_t* h_seg_ptr, int32_t n_s
 int tlc_binary_rank_metrics(const void* d_scores, int score_dtype, const void* d_labels, int label_dtype, const int64_t* h_seg_ptr,
                             int32_t n_segs, uint32_t flags, double* d_auc, double* d_ap, int64_t* d_n_pos, int64_t* d_n_neg,
                             int32_t* d_status, void* d_work, int64_t work_bytes, void* stream);
+
+/* ---- Heat-kernel-signature filtration (Knowledge_Distillation/data_utils_LP.py:96-100,128-130; data_utils_NC.py:88-92,120-122;
+ * data_utils_GC.py:90-94,114-116: `hks_signature`, then / (max + 1e-10)) ------------------------------------------------------------
+ * For a packed batch of simple undirected graphs -- d_node_ptr / d_edge_ptr int64[n_graphs + 1] (the last entries are total_nodes /
+ * total_edges), d_edges int32[total_edges, 2] local ids, each edge once -- per graph
+ *   L = I - D^-1/2 A D^-1/2 as scipy.sparse.csgraph.laplacian(normed=True) (a node of degree 0: diagonal 0),
+ *   hks_t(x) = sum_k exp(-t lambda_k) phi_k(x)^2 over the eigenpairs of L, fp64,
+ * for the n_times (1 .. TLC_HKS_TMAX) values of h_times (HOST; read during the call) from ONE decomposition: d_out f64[n_times,
+ * total_nodes], row k bit-equal to a call with h_times[k] alone.  TLC_HKS_NORMALISE: each graph's values divided by (their max + 1e-10).
+ * Eigenpairs: cyclic Jacobi, round-robin order, fixed arithmetic per element, no floating-point atomics: a graph's values are the same
+ * bits run to run, alone or anywhere in any batch.  Agreement with LAPACK's eigh route: rounding level (<= 1e-11 absolute is tested on
+ * normalised values up to n = TLC_HKS_NMAX, t = 10).
+ * d_status uint8[n_graphs]: TLC_ST_OK; TLC_ST_TOO_LARGE (more than TLC_HKS_NMAX nodes), TLC_ST_NOT_CONVERGED, TLC_ST_BAD_INPUT -- the
+ * graph's slice of d_out is then left untouched and no other graph is affected.  A graph without nodes: TLC_ST_OK, nothing written.
+ * The graphs are binned into size tiers on the device (<= 32 nodes: a wavefront each, matrices in LDS; <= 64 and <= TLC_HKS_LDS_NMAX:
+ * a workgroup each, matrices in LDS; <= TLC_HKS_NMAX: a workgroup each, matrices in d_work); nothing is read back, no host wait.
+ * d_work: tlc_hks_batch_work_bytes() bytes, 16-byte aligned -- the tier lists (16 B per graph) and one 1.0 MiB slot of matrices per
+ * resident workgroup of the last tier: min(CUs of the current device, total_nodes / (TLC_HKS_LDS_NMAX + 1)) slots, reused graph after
+ * graph.  Runs on the caller's current device, asynchronous on `stream`. */
+#define TLC_HKS_NMAX           256   /* most nodes of a graph; above it TLC_ST_TOO_LARGE */
+#define TLC_HKS_LDS_NMAX       96    /* most nodes of a graph whose two n x n fp64 arrays stay in the 160 KiB of LDS */
+#define TLC_HKS_TMAX           8     /* most times per call */
+#define TLC_HKS_NORMALISE      0x1u
+int tlc_hks_batch_work_bytes(int64_t n_graphs, int64_t total_nodes, int64_t total_edges, int32_t n_times, int64_t* bytes);
+int tlc_hks_batch(const int64_t* d_node_ptr, const int64_t* d_edge_ptr, const int32_t* d_edges, int64_t n_graphs, int64_t total_nodes,
+                  int64_t total_edges, const double* h_times, int32_t n_times, uint32_t flags, double* d_out, uint8_t* d_status,
+                  void* d_work, int64_t work_bytes, void* stream);
 
 /* ---- M4-M6: PDGNN layer forward (Knowledge_Distillation/gat_conv.py:113-216) ----------------------
  * One GATConv(heads=1, new_node_feat, use_edge_attn) layer on a block-diagonal batch of graphs whose

@@ -1,7 +1,8 @@
 """Drop-in for the ground-truth generation of the reference's Knowledge_Distillation/data_utils_GC.py (PDGNN, graph
 classification: whole graph = one diagram) and for the forward-only loop of train_Teacher_Model_GC.evaluate_time.
 
-  compute_persistence_image :98-170 (filt='degree' and 'hks': node functions on the host, the reference's own numpy / scipy calls),
+  compute_persistence_image :98-170 (filt='degree' and 'hks': node functions on the host, the reference's own numpy / scipy calls; 'hks'
+  on the device with hks_backend='device'),
   original_extended_persistence :78-82, call :228-279 (largest connected component, relabel), evaluate_time :118-143.
 
 The extended persistence of every graph runs in `tlc_pd_from_filtration` (Knowledge_Distillation fork: zero-persistence pairs
@@ -50,11 +51,15 @@ def hks_filtration(n, edges, hks_time):
     return v / (max(v) + 1e-10)
 
 
-def compute_persistence_image_batch(graphs, filt='degree', filtrations=None, hks_time=0.1):
+def compute_persistence_image_batch(graphs, filt='degree', filtrations=None, hks_time=0.1, hks_backend='host'):
     """graphs: list of networkx-like graphs with nodes 0..n-1, or (n, edges[m,2]) tuples.
     Returns a list with the reference's 9-tuple per graph (:166), or (None, None) for graphs without an edge / not
-    connected (:101-103).  filt: 'degree' or 'hks' (host side, :114-119); `filtrations` supplies f per graph for anything else."""
+    connected (:101-103).  filt: 'degree' or 'hks' (host side, :114-119); `filtrations` supplies f per graph for anything else.
+    hks_backend='device': filt='hks' from `tlc_hks_batch`, one launch for the whole list (`data_utils_LP.hks_filtration_device`; graphs
+    it does not take are counted in `data_utils_LP.hks_host_fallback`); it has no effect on the other filtrations."""
     import torch
+    from .data_utils_LP import check_hks_backend, hks_filtration_device
+    check_hks_backend(hks_backend)
     if filt not in ('degree', 'hks') and filtrations is None:
         raise NotImplementedError("data_utils_GC (HIP): filt='degree' and 'hks' are computed here; pass `filtrations` for anything else")
     parsed, keep = [], []
@@ -67,15 +72,20 @@ def compute_persistence_image_batch(graphs, filt='degree', filtrations=None, hks
     out = [(None, None)] * len(graphs)
     if not keep:
         return out
-    fs = [np.asarray(filtrations[gi], dtype=np.float64) if filtrations is not None else
-          (hks_filtration(parsed[gi][0], parsed[gi][1], hks_time) if filt == 'hks' else degree_filtration(*parsed[gi])) for gi in keep]
     node_offs = np.concatenate([[0], np.cumsum([parsed[gi][0] for gi in keep])]).astype(np.int64)
     edge_offs = np.concatenate([[0], np.cumsum([len(parsed[gi][1]) for gi in keep])]).astype(np.int64)
     edges = np.concatenate([parsed[gi][1] for gi in keep]).astype(np.int32)
-    f = np.concatenate(fs)
     dev = "cuda"
-    r = engine.pd_from_filtration(torch.from_numpy(node_offs).to(dev), torch.from_numpy(edge_offs).to(dev),
-                                  torch.from_numpy(edges).to(dev), torch.from_numpy(f).to(dev), _lib.KEEP_ZERO_PERS, want_rank=False)
+    d_node_offs, d_edge_offs, d_edges = torch.from_numpy(node_offs).to(dev), torch.from_numpy(edge_offs).to(dev), torch.from_numpy(edges).to(dev)
+    if filtrations is None and filt == 'hks' and hks_backend == 'device':
+        d_f = hks_filtration_device(d_node_offs, d_edge_offs, d_edges, hks_time, int(node_offs[-1]))
+        f = d_f.cpu().numpy()
+        fs = [f[node_offs[k]:node_offs[k + 1]] for k in range(len(keep))]
+    else:
+        fs = [np.asarray(filtrations[gi], dtype=np.float64) if filtrations is not None else
+              (hks_filtration(parsed[gi][0], parsed[gi][1], hks_time) if filt == 'hks' else degree_filtration(*parsed[gi])) for gi in keep]
+        d_f = torch.from_numpy(np.concatenate(fs)).to(dev)
+    r = engine.pd_from_filtration(d_node_offs, d_edge_offs, d_edges, d_f, _lib.KEEP_ZERO_PERS, want_rank=False)
     counts = r["counts"].cpu().numpy()
     up, one = r["up"], r["one"]
     # gather the ragged diagrams: Ord0 of graph k = up[node_offs[k] : +counts[k,0]], Ext1 = one[edge_offs[k] : +counts[k,2]]
@@ -108,10 +118,13 @@ def compute_persistence_image_batch(graphs, filt='degree', filtrations=None, hks
 
 
 def compute_persistence_image(g, filt='hks', hks_time=0.1, hop=2, ricci_curv=None, mode='PI', num_models=5, max_loop_len=10,
-                              cycle_the=2):
+                              cycle_the=2, hks_backend='host'):
     """Reference signature (:98).  filt='hks' (the default) or 'degree' ('ricci' needs curvatures per graph: pass `filtrations`
-    to compute_persistence_image_batch); mode 'PI' -> 9-tuple, 'filtration' -> (filtration_val, edge_index)."""
+    to compute_persistence_image_batch); mode 'PI' -> 9-tuple, 'filtration' -> (filtration_val, edge_index).
+    hks_backend (not in the reference): 'host' or 'device', see compute_persistence_image_batch."""
     import torch
+    from .data_utils_LP import check_hks_backend, hks_filtration_device
+    check_hks_backend(hks_backend)
     if filt not in ('degree', 'hks'):
         raise NotImplementedError("data_utils_GC (HIP): filt='hks' and 'degree' are implemented; for 'ricci' pass the values as "
                                   "`filtrations` to compute_persistence_image_batch")
@@ -119,9 +132,13 @@ def compute_persistence_image(g, filt='hks', hks_time=0.1, hop=2, ricci_curv=Non
     if len(e) == 0 or not _connected(n, e):
         return None, None
     if mode == 'filtration':
-        f = hks_filtration(n, e, hks_time) if filt == 'hks' else degree_filtration(n, e)
+        if filt == 'hks' and hks_backend == 'device':
+            ptr = lambda k: torch.tensor([0, k], dtype=torch.int64, device="cuda")
+            f = hks_filtration_device(ptr(n), ptr(len(e)), torch.from_numpy(e.astype(np.int32)).cuda(), hks_time, n).cpu().numpy()
+        else:
+            f = hks_filtration(n, e, hks_time) if filt == 'hks' else degree_filtration(n, e)
         return f.tolist(), torch.from_numpy(e.T.copy()).long()
-    return compute_persistence_image_batch([(n, e)], filt=filt, hks_time=hks_time)[0]
+    return compute_persistence_image_batch([(n, e)], filt=filt, hks_time=hks_time, hks_backend=hks_backend)[0]
 
 
 def evaluate_batch(model, samples):

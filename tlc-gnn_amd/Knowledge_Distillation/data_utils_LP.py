@@ -8,7 +8,7 @@ part of the subgraph (:111), there is no connectivity assert (an unreachable roo
 normalisation divides by max + 1e-10 (:64).  Node labels of a vicinity are positions in ASCENDING original id (the reference's
 `convert_node_labels_to_integers` order is arbitrary); edges are listed once, lower label first.
 filt='degree' (:131-133) and 'hks' (:128-130, the signature's default): the same vicinities, f from `structural_filtration` (host side:
-networkx's arithmetic, scipy's eigh).  The CBGNN cycle helpers (:256-448, dead code in the reference) and `call` are not reproduced.
+networkx's arithmetic, scipy's eigh); hks_backend='device': 'hks' from `tlc_hks_batch` instead (a Jacobi eigensolver in HIP, values to rounding).  The CBGNN cycle helpers (:256-448, dead code in the reference) and `call` are not reproduced.
 """
 import sys
 
@@ -20,6 +20,15 @@ KD_LP_FLAGS = _lib.INCLUDE_ROOTS | _lib.NORM_EPS | _lib.UNREACHABLE_100
 
 
 STRUCTURAL_FILTS = ("degree", "centrality", "clustering", "hks")
+HKS_BACKENDS = ("host", "device")
+# graphs of the most recent hks_backend='device' computation (this module's, data_utils_NC's or data_utils_GC's) that the device did not
+# take -- more than _lib.HKS_NMAX nodes, or no convergence -- and that `hks_signature` computed on the host instead
+hks_host_fallback = 0
+
+
+def check_hks_backend(hks_backend):
+    if hks_backend not in HKS_BACKENDS:
+        raise ValueError("hks_backend should be one of %s, not %r" % (HKS_BACKENDS, hks_backend))
 
 
 def hks_signature(n, edges, time):
@@ -86,6 +95,32 @@ def structural_filtration(kind, node_ptr, edge_ptr, edges, hks_time=0.1):
     return raw / (mx[owner] + 1e-10) if N else raw
 
 
+def hks_filtration_device(node_ptr, edge_ptr, edges, hks_time, total_nodes):
+    """The 'hks' case of `structural_filtration` on the device: `engine.hks_batch` (tlc_hks_batch) on the CUDA tensors of a packed batch
+    -> CUDA float64[sum n], normalised per graph.  Offsets and edges stay on the device.  Graphs the kernel does not take (status
+    TLC_ST_TOO_LARGE: more than _lib.HKS_NMAX nodes; TLC_ST_NOT_CONVERGED) are computed by `hks_signature` on the host and scattered
+    in -- one extra copy, only when there are any; their number is left in the module's `hks_host_fallback`."""
+    global hks_host_fallback
+    import torch
+    f, st = engine.hks_batch(node_ptr, edge_ptr, edges, [hks_time], normalise=True, total_nodes=total_nodes)
+    f = f[0]
+    rest = torch.nonzero(st != _lib.ST_OK).reshape(-1).cpu().numpy()
+    hks_host_fallback = len(rest)
+    if len(rest):
+        st_h = st.cpu().numpy()
+        if (st_h[rest] == _lib.ST_BAD_INPUT).any():
+            raise RuntimeError("hks_backend='device': a graph has offsets out of order, an edge id out of range or a self loop")
+        nptr, eptr, e = node_ptr.cpu().numpy(), edge_ptr.cpu().numpy(), edges.cpu().numpy()
+        idx, val = [], []
+        for k in rest:
+            a, b = int(nptr[k]), int(nptr[k + 1])
+            v = hks_signature(b - a, e[int(eptr[k]):int(eptr[k + 1])], hks_time)
+            idx.append(np.arange(a, b))
+            val.append(v / (max(v) + 1e-10))
+        f[torch.from_numpy(np.concatenate(idx)).to(f.device)] = torch.from_numpy(np.concatenate(val)).to(f.device)
+    return f
+
+
 class Vicinities:
     """Device-resident weighted graph for PDGNN's edge-centred vicinities; build once, query many pairs.
     ricci_curv=None: no curvature (the structural filtrations need only the vicinities): unit edge weights."""
@@ -101,15 +136,18 @@ class Vicinities:
         for old, new in self.dict_node.items():
             self.inv[new] = old
 
-    def batch(self, pairs, hop, node_cap=None, edge_cap=None, flags=None, filt='ricci', hks_time=0.1):
+    def batch(self, pairs, hop, node_cap=None, edge_cap=None, flags=None, filt='ricci', hks_time=0.1, hks_backend='host'):
         """pairs: [E,2] original labels -> dict of CUDA tensors: node_ptr int64[E+1], edge_ptr int64[E+1], ids int64 (original
         labels, ascending inside a vicinity), f float64, edges int32 [sum m, 2] (local ids, lower first), status uint8[E].
         Vicinities without an edge have empty slices (the reference returns (None, None) for them, :117-118).
         filt: 'ricci' (the weighted-distance filtration of the device kernels) or one of STRUCTURAL_FILTS (f replaced by
         `structural_filtration` of the extracted vicinities).
+        hks_backend: 'host' (scipy's eigh per vicinity on copies of offsets and edges) or 'device' (`hks_filtration_device` on the tensors
+        the extraction produced; the dict then also has hks_host_fallback); it matters for filt='hks' only.
         node_cap / edge_cap: per-pair capacities of an intermediate layout (one extraction; raises if a vicinity is larger); neither
         given: sizes first, exact offsets, two extractions (`tlc_vicinity_sizes` + `tlc_pack_offsets`)."""
         import torch
+        check_hks_backend(hks_backend)
         dev_graph = self._g2p._device_graph()
         mapped = torch.from_numpy(self._g2p._map_pairs(pairs)).cuda()
         fl = KD_LP_FLAGS if flags is None else flags
@@ -138,6 +176,10 @@ class Vicinities:
             pn = torch.repeat_interleave(owner, counts_n, output_size=int(tot_n))
             pe = torch.repeat_interleave(owner, counts_m, output_size=int(tot_m))
             out_ids, out_f, out_e = self._inv_dev[ids[:int(tot_n)].long()], f[:int(tot_n)], edges[:int(tot_m)]
+            if filt == 'hks' and hks_backend == 'device':
+                out_f = hks_filtration_device(node_ptr, edge_ptr, out_e, hks_time, int(tot_n))
+                return dict(node_ptr=node_ptr, edge_ptr=edge_ptr, ids=out_ids, f=out_f, edges=out_e, status=st, pair_of_node=pn, pair_of_edge=pe,
+                            hks_host_fallback=hks_host_fallback)
             if filt != 'ricci':
                 out_f = torch.from_numpy(structural_filtration(filt, node_ptr.cpu().numpy(), edge_ptr.cpu().numpy(), out_e.cpu().numpy(),
                                                                hks_time=hks_time)).to(out_f.device)
@@ -154,6 +196,10 @@ class Vicinities:
             raise RuntimeError("vicinity larger than the requested node_cap / edge_cap")
         out_ids, out_f, out_e, pn, pe = engine.pack_vicinities(offs, ids, f, eoffs, edges, node_ptr, edge_ptr, int(tot_n), int(tot_m),
                                                                label=self._inv_dev)
+        if filt == 'hks' and hks_backend == 'device':
+            out_f = hks_filtration_device(node_ptr, edge_ptr, out_e, hks_time, int(tot_n))
+            return dict(node_ptr=node_ptr, edge_ptr=edge_ptr, ids=out_ids, f=out_f, edges=out_e, status=st, pair_of_node=pn, pair_of_edge=pe,
+                        hks_host_fallback=hks_host_fallback)
         if filt != 'ricci':
             out_f = torch.from_numpy(structural_filtration(filt, node_ptr.cpu().numpy(), edge_ptr.cpu().numpy(), out_e.cpu().numpy(),
                                                            hks_time=hks_time)).to(out_f.device)
@@ -183,14 +229,16 @@ def _vicinities(g, ricci_curv):
 
 
 def compute_persistence_image(g, u, v, filt='hks', hks_time=0.1, hop=2, ricci_curv=None, mode='PI', num_models=5,
-                              max_loop_len=10, cycle_the=2):
+                              max_loop_len=10, cycle_the=2, hks_backend='host'):
     """Reference signature (:105).  filt='hks' (:128-130), 'degree' (:131-133) or 'ricci'; mode 'filtration' -> (filtration_val
-    list, edge_index LongTensor[2,m]) or (None, None); mode 'PI' -> the reference's 9-tuple (times are 0)."""
+    list, edge_index LongTensor[2,m]) or (None, None); mode 'PI' -> the reference's 9-tuple (times are 0).
+    hks_backend (not in the reference): 'host' or 'device', see `Vicinities.batch`."""
     import torch
+    check_hks_backend(hks_backend)
     if filt not in ('ricci', 'degree', 'hks'):
         print("Error: 'filt' should be 'hks', 'degree' or 'ricci'! ")          # :152-153
         sys.exit()
-    b = _vicinities(g, ricci_curv).batch([[u, v]], hop, filt=filt, hks_time=hks_time)
+    b = _vicinities(g, ricci_curv).batch([[u, v]], hop, filt=filt, hks_time=hks_time, hks_backend=hks_backend)
     if int(b["edge_ptr"][-1]) == 0:
         return None, None
     fv = b["f"].cpu().numpy()

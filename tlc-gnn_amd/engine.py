@@ -276,6 +276,38 @@ def pack_offsets(n, m):
 
 
 @_lib.on_device_of
+def hks_batch(node_ptr, edge_ptr, edges, times, normalise=True, total_nodes=None):
+    """Heat-kernel signatures of a packed batch of simple graphs on the device (tlc_hks_batch; `hks_signature` of the reference's
+    data_utils_LP/NC/GC, one Jacobi eigen-decomposition per graph shared by all `times`).
+
+    node_ptr / edge_ptr int64[B+1], edges int32[sum m, 2] local ids: CUDA tensors, the layout of `Vicinities.batch`.  times: a
+    float or up to 8 floats.  normalise: each graph's values / (max + 1e-10).  Returns (f float64[T, sum n], status uint8[B]); a
+    graph whose status is not ST_OK (ST_TOO_LARGE: more than HKS_NMAX nodes; ST_NOT_CONVERGED) has NaN in its slice.
+    total_nodes: sum n if the caller has it already (`Vicinities.batch` does); else node_ptr[-1] is read, the call's only host read."""
+    torch = _lib.require_gpu()
+    dev = node_ptr.device
+    times = [float(t) for t in (times if hasattr(times, "__len__") else [times])]
+    T, B = len(times), node_ptr.numel() - 1
+    if not 1 <= T <= _lib.HKS_TMAX:
+        raise ValueError("hks_batch: 1 .. %d times per call" % _lib.HKS_TMAX)
+    tot_m = int(edges.shape[0])
+    tot_n = int(total_nodes) if total_nodes is not None else (int(node_ptr[-1]) if B > 0 else 0)
+    out = torch.full((T, tot_n), float("nan"), dtype=torch.float64, device=dev)
+    status = torch.zeros(max(B, 1), dtype=torch.uint8, device=dev)
+    if B > 0:
+        need = C.c_int64(0)
+        _lib.check(_lib.lib().tlc_hks_batch_work_bytes(C.c_int64(B), C.c_int64(tot_n), C.c_int64(tot_m), C.c_int32(T), C.byref(need)),
+                   "tlc_hks_batch_work_bytes")
+        work = torch.empty(need.value, dtype=torch.uint8, device=dev)
+        rc = _lib.lib().tlc_hks_batch(_lib.ptr(node_ptr.contiguous()), _lib.ptr(edge_ptr.contiguous()), _lib.ptr(edges.contiguous()),
+                                      C.c_int64(B), C.c_int64(tot_n), C.c_int64(tot_m), (C.c_double * T)(*times), C.c_int32(T),
+                                      C.c_uint32(_lib.HKS_NORMALISE if normalise else 0), _lib.ptr(out), _lib.ptr(status), _lib.ptr(work),
+                                      C.c_int64(need.value), _lib.stream_ptr())
+        _lib.check(rc, "tlc_hks_batch")
+    return out, status[:B]
+
+
+@_lib.on_device_of
 def pd_from_filtration(node_offs, edge_offs, edges, f, flags=0, want_rank=True):
     """Batched perturb_filter_function + Union_find + Accelerate_PD (sg2dgm/accelerated_PD.py:6-178).
 
