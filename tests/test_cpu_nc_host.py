@@ -1,5 +1,7 @@
 """CPU: the host rules of the node-classification drop-ins (pipelines_GIN.py, Knowledge_Distillation/ConvCurv_GIN.py) against the
-reference's: masks per loader (:101-116), the name rules for hidden size, dropout, hop and epochs, and create_wmlp's structure."""
+reference's: masks per loader (:101-116), the name rules for hidden size, dropout, hop and epochs, and create_wmlp's structure; and
+the two work-size functions of nc_curv.hip, which are host code."""
+import itertools
 import random
 
 import numpy as np
@@ -62,3 +64,22 @@ def test_create_wmlp_structure():
     conv = m.curvGN(500, 3, skip_sum=True)
     assert sorted(k for k, _ in conv.named_parameters()) == ["lin.bias", "lin.weight", "lin1.bias", "lin1.weight", "w_mlp_out.0.weight",
                                                              "w_mlp_out.1.weight", "w_mlp_out.2.bias", "w_mlp_out.2.weight"]
+
+
+def test_nc_work_size_functions():
+    """include/tlcgnn.h: tlc_nc_group_work_ints = 2 n + 4 E; tlc_nc_curv_work_bytes = 4 (3 E C + ceil(E / 64) C + 32 C max(C, D)) for C in
+    1..256 and D in 1..64; -1 outside the range."""
+    from tlc_gnn_amd import _lib
+    L = _lib.lib()
+    for n, E in ((1, 0), (1, 1), (10, 63), (19717, 108365), (5, 2 ** 31 - 1), (2 ** 31 - 1, 0), (2 ** 31 - 1, 2 ** 31 - 1)):
+        assert L.tlc_nc_group_work_ints(n, E) == 2 * n + 4 * E, (n, E)
+    for n, E in ((0, 0), (0, 5), (-1, 5), (3, -1), (-2 ** 31, 0)):
+        assert L.tlc_nc_group_work_ints(n, E) == -1, (n, E)
+    for n, E, Cc, D in itertools.product((1, 19717), (0, 1, 63, 64, 65, 108365, 2 ** 31 - 1), (1, 3, 64, 255, 256), (1, 17, 50, 64)):
+        want = 4 * (3 * E * Cc + -(-E // 64) * Cc + 32 * Cc * max(Cc, D))
+        assert L.tlc_nc_curv_work_bytes(n, E, Cc, D) == want, (n, E, Cc, D)
+    assert L.tlc_nc_curv_work_bytes(1, 0, 1, 1) == 128                           # the split-K scratch alone
+    assert L.tlc_nc_curv_work_bytes(7, 100, 3, 50) == 4 * (900 + 2 * 3 + 32 * 150)
+    for n, E, Cc, D in ((0, 5, 8, 5), (-1, 5, 8, 5), (4, -1, 8, 5), (4, 5, 0, 5), (4, 5, -1, 5), (4, 5, 257, 5), (4, 5, 8, 0), (4, 5, 8, -3),
+                        (4, 5, 8, 65), (4, 5, 257, 65)):
+        assert L.tlc_nc_curv_work_bytes(n, E, Cc, D) == -1, (n, E, Cc, D)

@@ -529,7 +529,7 @@ extern "C" int tlc_nc_group(int32_t n_nodes, int64_t n_edges, const int64_t* d_e
 extern "C" int tlc_nc_linear_f32(int32_t M, int32_t N, int32_t K, const float* d_x, const float* d_w, const float* d_b, float* d_y,
                                  void* stream) {
     TLC_REQUIRE(M >= 0 && N >= 1 && K >= 1, "bad sizes");
-    TLC_REQUIRE(d_w && d_y && (M == 0 || d_x), "null pointer");
+    TLC_REQUIRE(d_w && (M == 0 || (d_x && d_y)), "null pointer");                                   // (M = 0: y has no element)
     TLC_HIP_CHECK(nc_gemm_launch(true, M, N, K, d_x, d_w, d_b, d_y, (hipStream_t)stream));
     return TLC_OK;
 }
