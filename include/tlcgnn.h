@@ -58,7 +58,8 @@ extern "C" {
                                       the output is left untouched */
 #define TLC_ST_NOT_CONVERGED   6   /* tlc_hks_batch: the Jacobi sweeps did not converge within their bound; slice untouched */
 #define TLC_ST_BAD_INPUT       7   /* tlc_hks_batch: offsets out of order / beyond the totals, an edge with an id outside
-                                      0 .. n-1 or a self loop (nothing of it is dereferenced); slice untouched */
+                                      0 .. n-1, a self loop (nothing of it is dereferenced) or an unordered pair listed
+                                      more than once, in either orientation; slice untouched */
 
 /* ---- variant flags (one kernel family serves the TLC-GNN and the PDGNN forks) ---- */
 #define TLC_KEEP_ZERO_PERS   0x01u /* Knowledge_Distillation/accelerated_PD.py:68-69,108-109,169-170 */
@@ -408,7 +409,8 @@ int tlc_binary_rank_metrics(const void* d_scores, int score_dtype, const void* d
 /* ---- Heat-kernel-signature filtration (Knowledge_Distillation/data_utils_LP.py:96-100,128-130; data_utils_NC.py:88-92,120-122;
  * data_utils_GC.py:90-94,114-116: `hks_signature`, then / (max + 1e-10)) ------------------------------------------------------------
  * For a packed batch of simple undirected graphs -- d_node_ptr / d_edge_ptr int64[n_graphs + 1] (the last entries are total_nodes /
- * total_edges), d_edges int32[total_edges, 2] local ids, each edge once -- per graph
+ * total_edges), d_edges int32[total_edges, 2] local ids, each undirected edge ONCE (a pair listed twice, (a, b) (a, b) or (a, b) (b, a),
+ * is TLC_ST_BAD_INPUT: scipy would sum it into a multigraph weight, this kernel does not compute weighted graphs) -- per graph
  *   L = I - D^-1/2 A D^-1/2 as scipy.sparse.csgraph.laplacian(normed=True) (a node of degree 0: diagonal 0),
  *   hks_t(x) = sum_k exp(-t lambda_k) phi_k(x)^2 over the eigenpairs of L, fp64,
  * for the n_times (1 .. TLC_HKS_TMAX) values of h_times (HOST; read during the call) from ONE decomposition: d_out f64[n_times,

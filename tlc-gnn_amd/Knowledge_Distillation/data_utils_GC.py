@@ -56,7 +56,10 @@ def compute_persistence_image_batch(graphs, filt='degree', filtrations=None, hks
     Returns a list with the reference's 9-tuple per graph (:166), or (None, None) for graphs without an edge / not
     connected (:101-103).  filt: 'degree' or 'hks' (host side, :114-119); `filtrations` supplies f per graph for anything else.
     hks_backend='device': filt='hks' from `tlc_hks_batch`, one launch for the whole list (`data_utils_LP.hks_filtration_device`; graphs
-    it does not take are counted in `data_utils_LP.hks_host_fallback`); it has no effect on the other filtrations."""
+    it does not take are counted in `data_utils_LP.hks_host_fallback`); it has no effect on the other filtrations.
+    hks_backend='device' wants each undirected edge ONCE per graph and raises RuntimeError otherwise (an (n, edges) tuple with both
+    directions, as PyG stores edge_index, or with a repeated pair; also self loops and ids outside 0 .. n-1); hks_backend='host' keeps
+    scipy's multigraph semantics: repeated entries add up to edge weights (both directions give the simple graph's values)."""
     import torch
     from .data_utils_LP import check_hks_backend, hks_filtration_device
     check_hks_backend(hks_backend)
@@ -121,7 +124,8 @@ def compute_persistence_image(g, filt='hks', hks_time=0.1, hop=2, ricci_curv=Non
                               cycle_the=2, hks_backend='host'):
     """Reference signature (:98).  filt='hks' (the default) or 'degree' ('ricci' needs curvatures per graph: pass `filtrations`
     to compute_persistence_image_batch); mode 'PI' -> 9-tuple, 'filtration' -> (filtration_val, edge_index).
-    hks_backend (not in the reference): 'host' or 'device', see compute_persistence_image_batch."""
+    hks_backend (not in the reference): 'host' or 'device', see compute_persistence_image_batch: 'device' wants each undirected edge
+    once and raises RuntimeError for a tuple that repeats one; 'host' keeps scipy's multigraph semantics (repeats add up to weights)."""
     import torch
     from .data_utils_LP import check_hks_backend, hks_filtration_device
     check_hks_backend(hks_backend)

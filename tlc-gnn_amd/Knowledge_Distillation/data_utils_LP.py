@@ -99,7 +99,10 @@ def hks_filtration_device(node_ptr, edge_ptr, edges, hks_time, total_nodes):
     """The 'hks' case of `structural_filtration` on the device: `engine.hks_batch` (tlc_hks_batch) on the CUDA tensors of a packed batch
     -> CUDA float64[sum n], normalised per graph.  Offsets and edges stay on the device.  Graphs the kernel does not take (status
     TLC_ST_TOO_LARGE: more than _lib.HKS_NMAX nodes; TLC_ST_NOT_CONVERGED) are computed by `hks_signature` on the host and scattered
-    in -- one extra copy, only when there are any; their number is left in the module's `hks_host_fallback`."""
+    in -- one extra copy, only when there are any; their number is left in the module's `hks_host_fallback`.
+    The device takes SIMPLE graphs, each undirected edge listed once: TLC_ST_BAD_INPUT (offsets out of order, an id outside 0 .. n-1, a
+    self loop, an unordered pair listed twice -- in the same or in both directions) raises RuntimeError; nothing is returned for such a
+    batch.  The host route differs there: scipy sums repeated entries into a weighted multigraph."""
     global hks_host_fallback
     import torch
     f, st = engine.hks_batch(node_ptr, edge_ptr, edges, [hks_time], normalise=True, total_nodes=total_nodes)
@@ -109,7 +112,8 @@ def hks_filtration_device(node_ptr, edge_ptr, edges, hks_time, total_nodes):
     if len(rest):
         st_h = st.cpu().numpy()
         if (st_h[rest] == _lib.ST_BAD_INPUT).any():
-            raise RuntimeError("hks_backend='device': a graph has offsets out of order, an edge id out of range or a self loop")
+            raise RuntimeError("hks_backend='device': a graph has offsets out of order, an edge id out of range, a self loop or a repeated "
+                               "edge (the device wants each undirected edge once; hks_backend='host' sums repeated edges into weights)")
         nptr, eptr, e = node_ptr.cpu().numpy(), edge_ptr.cpu().numpy(), edges.cpu().numpy()
         idx, val = [], []
         for k in rest:

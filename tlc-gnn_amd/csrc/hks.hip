@@ -15,6 +15,8 @@
 // below that, i.e. off-diagonal norm <= ne * max <= 1e-15 <= 1e-15 * ||L||_F (a graph with an edge has ||L||_F >= sqrt(2)).  Degenerate
 // spectra need no care: only sum over an eigenspace of phi^2 enters the signature.  More than TLC_HKS_MAX_SWEEPS sweeps: status byte
 // TLC_ST_NOT_CONVERGED, nothing written.
+// Input check: ids outside 0 .. n-1 and self loops while the degrees are counted; an unordered pair listed twice (either orientation)
+// after L is built, by counting the non-zeros of every column against the degree (integers only) -- TLC_ST_BAD_INPUT, nothing written.
 //
 // Tiers by node count, binned ON THE DEVICE from node_ptr (the host knows B and the two totals only); every tier is a persistent loop that
 // draws graphs from its list by a ticket counter:
@@ -101,6 +103,15 @@ __device__ __forceinline__ int hks_graph(double* A, double* Vt, double* cs, doub
         for (int l = k + 1; l < h; ++l) tab[base + l - k - 1] = (unsigned short)(k | (l << 8));
     }
     hks_sync<WAVE>();
+    // each edge once: a repeated pair {a, b} went into deg twice but is ONE entry of L (scipy would sum it into a multigraph weight), so
+    // column i then holds fewer non-zeros than deg[i] off-diagonals plus its diagonal.  Counting only: no value of L changes.
+    for (int i = tid; i < n; i += NT) {
+        int cnt = 0;
+        for (int j = 0; j < n; ++j) cnt += A[j * ld + i] != 0.0;
+        if (cnt != deg[i] + (deg[i] > 0)) flag[0] = 1;
+    }
+    hks_sync<WAVE>();
+    if (flag[0]) return TLC_ST_BAD_INPUT;
 
     const double tol = 1e-15 / (double)ne;
     const int nblocks = h * (h - 1) / 2, nvt = h * ne;

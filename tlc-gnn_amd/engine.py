@@ -282,7 +282,10 @@ def hks_batch(node_ptr, edge_ptr, edges, times, normalise=True, total_nodes=None
 
     node_ptr / edge_ptr int64[B+1], edges int32[sum m, 2] local ids: CUDA tensors, the layout of `Vicinities.batch`.  times: a
     float or up to 8 floats.  normalise: each graph's values / (max + 1e-10).  Returns (f float64[T, sum n], status uint8[B]); a
-    graph whose status is not ST_OK (ST_TOO_LARGE: more than HKS_NMAX nodes; ST_NOT_CONVERGED) has NaN in its slice.
+    graph whose status is not ST_OK (ST_TOO_LARGE: more than HKS_NMAX nodes; ST_NOT_CONVERGED; ST_BAD_INPUT: offsets out of order or
+    beyond the totals, an id outside 0 .. n-1, a self loop, or an unordered pair listed twice, in the same or in both directions --
+    each undirected edge once is the contract, a multigraph is refused and never computed differently from the host route) has NaN in
+    its slice.
     total_nodes: sum n if the caller has it already (`Vicinities.batch` does); else node_ptr[-1] is read, the call's only host read."""
     torch = _lib.require_gpu()
     dev = node_ptr.device
