@@ -5,6 +5,7 @@
 //   counts] -> FILL (induced subgraphs into the arena) -> one PD kernel per size tier, the tiers running
 //   concurrently on side streams so that the few large subgraphs overlap the many small ones.
 #include <stdarg.h>
+#include <stddef.h>
 #include <stdlib.h>
 
 #include <algorithm>
@@ -45,9 +46,37 @@ extern "C" int tlc_device_count(void) {
 #define TLC_TIMING_RING 64        /* chunks whose kernel events are kept */
 #define TLC_X_REGION 4096         /* arena entries of the region each workgroup of the extraction starts with (extract.hip) */
 
-// a workspace's control block: [0, 64) control words | [64, 64 + TLC_SCAN_MAX_BLOCKS) the scan's per-block flags | 8 ints of statistics | 8 work counters of the
-// general extraction launch, 64 ints apart
-#define TLC_CTL_INTS (64 + TLC_SCAN_MAX_BLOCKS + 8 + 8 * 64)
+// A workspace's control block on the device, zeroed on the chunk's stream ahead of its first kernel.  The kernels get plain pointers to
+// its members and index from there (tier_count[t], scan_sync[k], big_count[k], the statistics as four u64, the work counters 64 ints
+// apart), so no member may move: the assertions below pin every one.  The free* words are unused.
+struct ChunkCtl {
+    int tier_count[TLC_N_TIERS], free8[2];  // lengths of the scan's tier lists
+    int scan_sync[4], free14[2];            // tlc_scan_bin: block ticket, blocks done, the running arena total (u64)
+    int cand_count, early_count;            // early pass: candidates selected, vicinities in the early list
+    int early_started, cand_started;        // ... resident workgroups of the early LARGE tier kernel / of the early extraction
+    unsigned long long bump_top;            // arena entries the bump allocator has handed out
+    int bump_overflow, free23[3];           // vicinities that did not fit the arena: the chunk takes the scan + FILL path
+    struct { int count, pad; } dc[3];       // lists for tlc_pd_dc_kernel (tier_params)
+    int big_count[4], free36[8];            // bins of tlc_classify_kernel (three in use)
+    int dcm_count, free45[3];               // MEDHI / MEDWIDE vicinities with Pos edges enough for the divide and conquer
+    int tiny_bin_count[16];                 // size classes of the TINY list (TLC_TINY_BINS of them)
+    int scan_flag[TLC_SCAN_MAX_BLOCKS];     // tlc_scan_bin: a block's sum is valid
+    struct Stats {                          // (TlcPdParams::stats indexes these as u64 [0], [1], [3])
+        unsigned long long tie_fallback;    // sources that took the exact tie fallback
+        unsigned long long dc_swaps;        // cycle swaps run as a divide and conquer ...
+        int large_started, pad;             // LARGE workgroups started (TlcPdParams::started)
+        unsigned long long dc_given_back;   // ... and those given back to the serial walk
+    } stats;
+    struct { int next, pad[63]; } work[8];  // work counters of the general extraction (extract.hip: TLC_X_COUNTERS, 64 ints apart)
+};
+#define CTL_AT(member, word) static_assert(offsetof(ChunkCtl, member) == (word) * sizeof(int), "ChunkCtl::" #member " moved")
+CTL_AT(tier_count, 0); CTL_AT(scan_sync, 10); CTL_AT(cand_count, 16); CTL_AT(early_count, 17); CTL_AT(early_started, 18);
+CTL_AT(cand_started, 19); CTL_AT(bump_top, 20); CTL_AT(bump_overflow, 22); CTL_AT(dc, 26); CTL_AT(big_count, 32); CTL_AT(dcm_count, 44);
+CTL_AT(tiny_bin_count, 48); CTL_AT(scan_flag, 64); CTL_AT(stats, 64 + TLC_SCAN_MAX_BLOCKS); CTL_AT(work, 64 + TLC_SCAN_MAX_BLOCKS + 8);
+CTL_AT(stats.dc_swaps, 64 + TLC_SCAN_MAX_BLOCKS + 2); CTL_AT(stats.large_started, 64 + TLC_SCAN_MAX_BLOCKS + 4); CTL_AT(stats.dc_given_back, 64 + TLC_SCAN_MAX_BLOCKS + 6);
+#undef CTL_AT
+static_assert(sizeof(ChunkCtl) == (64 + TLC_SCAN_MAX_BLOCKS + 8 + 8 * 64) * sizeof(int) && sizeof(ChunkCtl().dc[0]) == 8 &&
+              sizeof(ChunkCtl().work[0]) == 64 * sizeof(int) && TLC_TINY_BINS <= 16, "ChunkCtl: size / strides the kernels rely on");
 struct HostSync {
     long long total_entries;
     int tier_count[TLC_N_TIERS];
@@ -68,14 +97,30 @@ struct HostSync {
 
 #define TLC_N_WS 4                /* workspaces of a handle: chunks (and asynchronous batches) take them in turn */
 
+// Where the results of a batch go: images and status bytes (tlc_pd_pi_batch) or the filtration outputs (tlc_vicinity_filtration,
+// tlc_vicinity_sizes).  Null: not asked for.
+struct BatchIO {
+    double* out_pi; uint8_t* out_status;
+    const int64_t* ids_off; int32_t* out_ids; double* out_f; int32_t* out_n;
+    const int64_t* edge_offs; int32_t* out_edges; int32_t* out_m;
+    int pi_enabled;
+    bool plain() const { return pi_enabled && !out_ids && !out_f && !out_edges; }   // an image batch with none of the filtration outputs
+    // The view of the chunk that starts at pair `off`.  What is indexed by pair advances to the chunk's first pair, ids_off / edge_offs
+    // included: the kernels index by the chunk-local pair index.  out_ids / out_f / out_edges stay: those offsets count from the batch's start.
+    BatchIO chunk(int64_t off, int res) const {
+        auto at = [off](auto* p, int64_t per_pair = 1) { return p ? p + off * per_pair : p; };
+        return {at(out_pi, (int64_t)res * res), at(out_status), at(ids_off), out_ids, out_f, at(out_n), at(edge_offs), out_edges, at(out_m), pi_enabled};
+    }
+};
+
 // Everything one chunk of pairs writes while it is in flight.  A handle has TLC_N_WS of them, taken in turn, each with its own
 // streams: the chunks of one call, and the batches of tlc_pd_pi_batch_async, overlap -- the lead-in of one (selection, early
 // extraction, the main extraction, all latency-bound) runs under the tail of the tier kernels of the one before.
 // What the second half of a chunk (everything behind the size publication: run_chunk_back) needs from the first.  A pipelined
 // chunk's second half is submitted one call later (see run_batch), so this lives in the workspace.
 struct ChunkCtx {
-    TlcVicParams vp;
-    TlcPdParams pp;
+    TlcVicParams vp;               // the extraction's arguments; a launch that needs them otherwise takes a copy
+    TlcPdParams base;              // what every tier launch of the chunk has in common; each builds its own arguments from it (tier_params)
     hipStream_t s;
     int n_pairs, hop, pi_enabled;
     bool bump, use_x, early, spec, count_only, tiny_bins, pipelined;
@@ -104,12 +149,9 @@ struct Workspace {
     hipEvent_t ev_cls;         // the classification is done (recorded on the early stream)
     int prev_dcm;              // the previous chunk's count of MEDHI vicinities for the divide and conquer (decides the speculative chain)
     long long* edge_off;
-    // small device block: [0..6] tier counts, [10..13] scan, [16..19] early pass, [20..22] bump allocator, [24] work counter,
-    // [26..31] divide-and-conquer lists, [32..35] bins, [36..37] entry sum
-    int* d_ctl;
+    ChunkCtl* d_ctl;
     long long* d_block_sums;   // 1024
     long long* d_totals;       // 1
-    unsigned long long* d_stats;  // [0] tie-fallback sources, [1] divide-and-conquer swaps, [2] (as int) LARGE workgroups started, [3] swaps given back
     HostSync* h_sync;          // pinned
     HostSync* h_sync_dev;      // the same block as the device sees it
     unsigned pub_seq;          // sequence number of the last size publication
@@ -607,8 +649,7 @@ extern "C" int tlc_graph_create(int32_t n_nodes, const int32_t* h_rowptr, const 
     const int n_eager = 3;
     for (int i = 0; i < TLC_N_WS; ++i) {
         Workspace* ws = &g->ws[i];
-        CK(hipMalloc(&ws->d_ctl, TLC_CTL_INTS * sizeof(int)));   // counters, the scan's per-block flags, 4 x u64 statistics, work counters
-        ws->d_stats = reinterpret_cast<unsigned long long*>(ws->d_ctl + 64 + TLC_SCAN_MAX_BLOCKS);      // (8-byte aligned: hipMalloc is 256-byte aligned)
+        CK(hipMalloc(&ws->d_ctl, sizeof(ChunkCtl)));
         CK(hipMalloc(&ws->d_block_sums, TLC_SCAN_MAX_BLOCKS * sizeof(long long)));
         CK(hipMalloc(&ws->d_totals, 2 * sizeof(long long)));
         CK(hipHostMalloc((void**)&ws->h_sync, sizeof(HostSync), hipHostMallocMapped | hipHostMallocCoherent));
@@ -730,27 +771,31 @@ __global__ void tlc_wait_started_dev(const int* counter, const int* target, int 
 //   front_speculative  (a chunk on its own) the many-Pos MEDIUM list behind the scan, sized from the previous chunk
 #define T0(k, st) do { if ((c.tmask >> (k)) & 1) { TLC_HIP_CHECK(hipEventRecord(c.ev_t[2 * (k)], st)); } } while (0)
 #define T1(k, st) do { if ((c.tmask >> (k)) & 1) { TLC_HIP_CHECK(hipEventRecord(c.ev_t[2 * (k) + 1], st)); c.ev_used[k] = 1; } } while (0)
-// lists for tlc_pd_dc_kernel: counters in the control block (zeroed with it), [d_ctl + 26 + 2k];
-// k = 0 MEDIUM, 1 LARGE (regular launch), 2 LARGE (early launch)
-static inline void dc_lists_for(Workspace* ws, TlcPdParams& q, int k) {
-    const size_t cap = ws->cap_pairs + TLC_EARLY_SLOTS;
-    q.dc_count = ws->d_ctl + 26 + 2 * k;
-    q.dc_list = ws->dc_lists + (size_t)k * cap;
+// The arguments of ONE tier launch, by value: the chunk's base plus tier t's list of `count` positions and its diagnostics row,
+// `handoff_cap` hand-off slots at `handoff` (null: the tier kernel runs the cycle swap itself) and the list for tlc_pd_dc_kernel
+// (`dc`: 0 MEDIUM-sized, 1 LARGE (regular launch), 2 LARGE (early launch), counters zeroed with the control block; -1: none).
+// What a launch needs beyond that (a grid of its own, wi_base, phase, a count on the device ...) its site sets on its own copy; what
+// nobody sets is the base's zero, and no launch sees what another one set.
+static TlcPdParams tier_params(const tlc_graph* g, const Workspace* ws, int t, int count, unsigned char* handoff, int handoff_cap, int dc) {
+    TlcPdParams q = ws->ctx.base;
+    q.tier_list = ws->tier_list + (size_t)t * ws->ctx.n_pairs; q.tier_count = count;
+    q.handoff = handoff; q.handoff_stride = handoff ? (long long)tlc_handoff_slot_bytes(t) : 0; q.handoff_cap = handoff_cap;
+    if (dc >= 0) { q.dc_count = &ws->d_ctl->dc[dc].count; q.dc_list = ws->dc_lists + (size_t)dc * (ws->cap_pairs + TLC_EARLY_SLOTS); }
+    q.phase_cycles = g->d_phase ? g->d_phase + 32 * t : nullptr;
+    return q;
 }
 // timing slot of each tier kernel (TINY is reported with SMALL, MEDHI / MEDWIDE as MEDIUM)
 static const int tslot[TLC_N_TIERS] = {3, 4, 5, 6, 7, 3, 4, 4};
 
 static int front_prepare(tlc_graph* g, Workspace* ws, const int32_t* d_pairs, int n_pairs, int hop, uint32_t flags, int res,
-                         double* d_out_pi, uint8_t* d_out_status, const int64_t* d_ids_off, int32_t* d_out_ids,
-                         double* d_out_f, int32_t* d_out_n, const int64_t* d_edge_offs, int32_t* d_out_edges, int32_t* d_out_m,
-                         int pi_enabled, hipStream_t s, bool pipelined) {
+                         const BatchIO& io, hipStream_t s, bool pipelined) {
     int rc;
     ChunkCtx& c = ws->ctx;
     c.ht0 = std::chrono::steady_clock::now();
-    c.s = s; c.n_pairs = n_pairs; c.hop = hop; c.pi_enabled = pi_enabled; c.call_seq = g->call_seq;
+    c.s = s; c.n_pairs = n_pairs; c.hop = hop; c.pi_enabled = io.pi_enabled; c.call_seq = g->call_seq;
     if ((rc = ensure_pairs(g, ws, (size_t)n_pairs)) != TLC_OK) return rc;
     if ((rc = ensure_vic_scratch(g, ws, hop)) != TLC_OK) return rc;
-    TLC_HIP_CHECK(hipMemsetAsync(ws->d_ctl, 0, TLC_CTL_INTS * sizeof(int), s));       // control words, scan flags, statistics, work counters
+    TLC_HIP_CHECK(hipMemsetAsync(ws->d_ctl, 0, sizeof(ChunkCtl), s));
 
     TlcVicParams& vp = c.vp;
     memset(&vp, 0, sizeof(vp));
@@ -768,9 +813,9 @@ static int front_prepare(tlc_graph* g, Workspace* ws, const int32_t* d_pairs, in
     vp.pairs = d_pairs; vp.n_pairs = n_pairs; vp.hop = hop; vp.flags = flags; vp.res = res;
     vp.scratch = ws->vic_scratch; vp.scratch_stride = ws->vic_stride;
     vp.hdr_n = ws->hdr_n; vp.hdr_m2 = ws->hdr_m2; vp.hdr_lu = ws->hdr_lu; vp.hdr_lv = ws->hdr_lv;
-    vp.out_pi = d_out_pi; vp.out_status = d_out_status; vp.out_n = d_out_n; vp.out_m = d_out_m;
+    vp.out_pi = io.out_pi; vp.out_status = io.out_status; vp.out_n = io.out_n; vp.out_m = io.out_m;
     vp.edge_off = ws->edge_off; vp.A_dir = nullptr; vp.A_lw = nullptr;
-    vp.ids_off = (const long long*)d_ids_off; vp.out_ids = d_out_ids;
+    vp.ids_off = (const long long*)io.ids_off; vp.out_ids = io.out_ids;
 
     // (the attribute is per device and per size: tracked in the handle, which is bound to one device and one graph size)
     if (!g->lds_attr_set && g->vic_lds > 64 * 1024) {
@@ -812,10 +857,8 @@ static int front_prepare(tlc_graph* g, Workspace* ws, const int32_t* d_pairs, in
     // (round 4: tlc_vicinity_filtration as well -- its id / f / edge outputs have caller-given offsets, so COUNT can finish the
     // MID / MEDIUM vicinities too, ids included; the 64-thread FILL pass over a handful of MEDIUM pairs was 0.15 - 0.22 ms of a
     // 0.45 ms call on 4 096 Amazon-shaped pairs)
-    const bool plain = pi_enabled && !d_out_ids && !d_out_f && !d_out_edges;
+    const bool plain = io.plain();
     const bool bump = true;
-    unsigned long long* d_bump_top = reinterpret_cast<unsigned long long*>(ws->d_ctl + 20);
-    int* d_bump_overflow = ws->d_ctl + 22;
     // The extraction runs from the ball lists (extract.hip); rounds 3 - 4: hop <= 2 only.  (Round 4: also with the
     // id / f / edge outputs of tlc_vicinity_filtration and with TLC_INCLUDE_ROOTS, the PDGNN fork's vicinities -- the breadth-first
     // COUNT pays two bitmaps of N bits per pair whatever the vicinity's size: 0.18 - 0.25 ms of a 0.37 ms call on 4 096 Amazon-shaped
@@ -828,7 +871,7 @@ static int front_prepare(tlc_graph* g, Workspace* ws, const int32_t* d_pairs, in
         if ((rc = ensure_ball_lists(g, hop, s)) != TLC_OK) return rc;
         use_x = g->ball_list_hop == hop;
     }
-    const bool early = pi_enabled && !d_out_ids && !d_out_f && !d_out_edges && (hop <= 2 || use_x) && n_pairs >= TLC_EARLY_MIN_PAIRS;
+    const bool early = plain && (hop <= 2 || use_x) && n_pairs >= TLC_EARLY_MIN_PAIRS;
     // (2 048 .. 6 400 extraction workgroups measured within 2 %: one per scratch slot)
     const int xgrid = std::min(n_pairs, g->vic_slots);
     // The pairs whose vicinity is a filter over the smaller ball's subgraph list (extract.hip, x_sweep_ball: smaller ball <= 128
@@ -860,17 +903,18 @@ static int front_prepare(tlc_graph* g, Workspace* ws, const int32_t* d_pairs, in
         if (ws->cap_entries == 0 &&
             (rc = ensure_arena(g, ws, std::min<size_t>((size_t)n_pairs * 128, (size_t)1 << 23))) != TLC_OK) return rc;
         vp.A_dir = ws->A_dir; vp.A_lw = ws->A_lw;
-        vp.bump_top = d_bump_top; vp.bump_cap = (long long)ws->cap_entries; vp.bump_overflow = d_bump_overflow;
+        vp.bump_top = &ws->d_ctl->bump_top; vp.bump_cap = (long long)ws->cap_entries; vp.bump_overflow = &ws->d_ctl->bump_overflow;
     }
-    TlcPdParams& pp = c.pp;
+    // what the chunk's tier launches have in common (the arena, which may still grow, and the HUGE scratch join it in run_chunk_back)
+    TlcPdParams& pp = c.base;
     memset(&pp, 0, sizeof(pp));
     pp.hdr_n = ws->hdr_n; pp.hdr_m2 = ws->hdr_m2; pp.hdr_lu = ws->hdr_lu; pp.hdr_lv = ws->hdr_lv;
     pp.edge_off = ws->edge_off;
     pp.small_dir = use_x ? nullptr : ws->S_dir; pp.small_lw = use_x ? nullptr : ws->S_lw;
-    pp.flags = flags; pp.res = res; pp.out_pi = d_out_pi; pp.out_status = d_out_status;
-    pp.ids_off = (const long long*)d_ids_off; pp.out_f = d_out_f; pp.out_n = d_out_n; pp.pi_enabled = pi_enabled;
-    pp.edges_off = (const long long*)d_edge_offs; pp.out_edges = d_out_edges; pp.out_m = d_out_m;
-    pp.stats = ws->d_stats;
+    pp.flags = flags; pp.res = res; pp.out_pi = io.out_pi; pp.out_status = io.out_status;
+    pp.ids_off = (const long long*)io.ids_off; pp.out_f = io.out_f; pp.out_n = io.out_n; pp.pi_enabled = io.pi_enabled;
+    pp.edges_off = (const long long*)io.edge_offs; pp.out_edges = io.out_edges; pp.out_m = io.out_m;
+    pp.stats = &ws->d_ctl->stats.tie_fallback;
     pp.dc_force_fail = g->opt_dc_force_fail;
     pp.no_plain = g->opt_plain_kernels ? 0 : 1;
     c.bump = bump; c.use_x = use_x; c.early = early; c.bump_base = bump_base; c.xgrid = xgrid;
@@ -953,41 +997,36 @@ static int front_early_chain(tlc_graph* g, Workspace* ws) {
     int rc;
     ChunkCtx& c = ws->ctx;
     TlcVicParams& vp = c.vp;
-    TlcPdParams& pp = c.pp;
+    ChunkCtl* ctl = ws->d_ctl;
     hipStream_t s = c.s;
     const int n_pairs = c.n_pairs, hop = c.hop, xgrid = c.xgrid;
     const bool early = c.early, use_x = c.use_x;
     const int32_t* d_pairs = vp.pairs;
-    // control words of the early pass (zeroed with the control block)
-    int* d_cand_count = ws->d_ctl + 16;
-    int* d_early_count = ws->d_ctl + 17;
-    int* d_early_started = ws->d_ctl + 18;
-    int* d_cand_started = ws->d_ctl + 19;
     if (early) {
         if ((rc = ensure_early(g, ws, hop, s)) != TLC_OK) return rc;
         hipStream_t es = ws->side[4];
         // (TLC_INCLUDE_ROOTS adds at most the two roots to a vicinity)
         if (use_x) {
             // exact ball sizes: the candidates of the early pass and the bins the main pass takes first
-            if ((rc = tlc_launch_classify(n_pairs, d_pairs, g->n_nodes, g->d_bptr, TLC_M_NMAX - 1, TLC_EARLY_CAND, d_cand_count,
-                                          ws->d_cand_list, ws->d_ctl + 32, ws->big_lists, es)) != TLC_OK) return rc;
+            if ((rc = tlc_launch_classify(n_pairs, d_pairs, g->n_nodes, g->d_bptr, TLC_M_NMAX - 1, TLC_EARLY_CAND, &ctl->cand_count,
+                                          ws->d_cand_list, ctl->big_count, ws->big_lists, es)) != TLC_OK) return rc;
             TLC_HIP_CHECK(hipEventRecord(ws->ev_cls, es));
         } else if ((rc = tlc_launch_select_heavy(n_pairs, d_pairs, g->n_nodes, g->d_ball_ub[(hop - 1) & 1], TLC_M_NMAX - 1, TLC_EARLY_CAND,
-                                                 d_cand_count, ws->d_cand_list, es)) != TLC_OK) return rc;
+                                                 &ctl->cand_count, ws->d_cand_list, es)) != TLC_OK) return rc;
         TlcVicParams ep = vp;
-        ep.fill_mode = 1; ep.fill_list = ws->d_cand_list; ep.fill_count = TLC_EARLY_CAND; ep.work_count_dev = d_cand_count;
+        ep.fill_mode = 1; ep.fill_list = ws->d_cand_list; ep.fill_count = TLC_EARLY_CAND; ep.work_count_dev = &ctl->cand_count;
         ep.scratch_base_slot = g->vic_slots;
         ep.dbg = g->d_phase ? g->d_phase + 32 * TLC_N_TIERS : nullptr;        // (diagnostics: the early pass has its own row)
-        ep.early_list = ws->d_early_list; ep.early_count = d_early_count; ep.early_cap = TLC_EARLY_SLOTS;
+        ep.early_list = ws->d_early_list; ep.early_count = &ctl->early_count; ep.early_cap = TLC_EARLY_SLOTS;
         ep.early_dir = ws->E_dir; ep.early_lw = ws->E_lw;
-        ep.started = d_cand_started;
+        ep.started = &ctl->cand_started;
         if (use_x) {
             // the early pass OWNS its candidates: headers, status bytes, zero rows, slots and bump-allocated vicinities are all
             // its own, and the main COUNT leaves those pairs out (same predicate as the selection, see TlcVicParams::skip_ub)
             ep.region_base_wg = xgrid;
             if ((rc = tlc_launch_extract(512, TLC_EARLY_WG, g->x_lds512, ep, es)) != TLC_OK) return rc;
-            vp.skip_threshold = TLC_M_NMAX - 1; vp.skip_count = d_cand_count; vp.skip_cap = TLC_EARLY_CAND;
-            vp.big_count = ws->d_ctl + 32; vp.big_list = ws->big_lists;
+            vp.skip_threshold = TLC_M_NMAX - 1; vp.skip_count = &ctl->cand_count; vp.skip_cap = TLC_EARLY_CAND;
+            vp.big_count = ctl->big_count; vp.big_list = ws->big_lists;
         } else {
             ep.bump_top = nullptr;
             ep.out_pi = nullptr; ep.out_status = nullptr; ep.out_n = nullptr; ep.out_m = nullptr;   // the main COUNT reports
@@ -996,18 +1035,13 @@ static int front_early_chain(tlc_graph* g, Workspace* ws) {
             TLC_HIP_CHECK(hipGetLastError());
         }
         TLC_HIP_CHECK(hipEventRecord(ws->ev_early, es));
-        TlcPdParams lp = pp;
-        lp.tier_list = ws->d_early_list; lp.tier_count = TLC_EARLY_SLOTS; lp.tier_count_dev = d_early_count;
+        // the early LARGE launch: the early pass's list, its length on the device, list position wi in slot wi of the early arena
+        const bool hand = tlc_handoff_slot_bytes(TLC_TIER_LARGE) != 0;
+        if (hand && (rc = ensure_handoff_large(g, ws, TLC_EARLY_SLOTS)) != TLC_OK) return rc;
+        TlcPdParams lp = tier_params(g, ws, TLC_TIER_LARGE, TLC_EARLY_SLOTS, hand ? ws->handoff_large : nullptr, hand ? TLC_EARLY_SLOTS : 0, hand ? 2 : -1);
+        lp.tier_list = ws->d_early_list; lp.tier_count_dev = &ctl->early_count; lp.started = &ctl->early_started;
         lp.slot_entries = 2 * TLC_L_MMAX; lp.A_dir = ws->E_dir; lp.A_lw = ws->E_lw;
-        lp.started = d_early_started;
-        if (tlc_handoff_slot_bytes(TLC_TIER_LARGE) != 0) {
-            if ((rc = ensure_handoff_large(g, ws, TLC_EARLY_SLOTS)) != TLC_OK) return rc;
-            lp.handoff = ws->handoff_large; lp.handoff_stride = (long long)tlc_handoff_slot_bytes(TLC_TIER_LARGE);
-            lp.handoff_cap = TLC_EARLY_SLOTS;
-            dc_lists_for(ws, lp, 2);
-            lp.dc_inplace = g->opt_dc_inplace;
-        }
-        lp.phase_cycles = g->d_phase ? g->d_phase + 32 * TLC_TIER_LARGE : nullptr;
+        if (hand) lp.dc_inplace = g->opt_dc_inplace;
         T0(5, es);
         if (((g->opt_tier_mask >> TLC_TIER_LARGE) & 1) && (rc = tlc_launch_pd_tier(TLC_TIER_LARGE, lp, es)) != TLC_OK) return rc;
         T1(5, es);
@@ -1021,9 +1055,6 @@ static int front_early_chain(tlc_graph* g, Workspace* ws) {
 static int front_join_early(tlc_graph* g, Workspace* ws) {
     ChunkCtx& c = ws->ctx;
     hipStream_t s = c.s;
-    const bool use_x = c.use_x;
-    int* d_early_count = ws->d_ctl + 17;
-    int* d_early_started = ws->d_ctl + 18;
     if (c.early) {
         // The workgroups of the main COUNT are persistent (each strides over its share of the pairs) and fill every wavefront
         // slot and most of the LDS of the machine: once they are running, a 512-thread workgroup of the early pass -- let alone
@@ -1036,14 +1067,14 @@ static int front_join_early(tlc_graph* g, Workspace* ws) {
         // needs from the early stream; a pair has one owner, so the two launches write disjoint headers, regions and slots -- and runs
         // BESIDE the early pass; the scan still waits for the early list.  Two libraries in turn, three rounds: 0.4957 -> 0.4847 ms per
         // pipelined batch (-2.2 %), rotating batches -2.9 %.  A chunk on its own keeps the order that gets its LARGE workgroups placed first.)
-        if (g->opt_main_beside_early && c.pipelined && use_x) { TLC_HIP_CHECK(hipStreamWaitEvent(s, ws->ev_cls, 0)); }
+        if (g->opt_main_beside_early && c.pipelined && c.use_x) { TLC_HIP_CHECK(hipStreamWaitEvent(s, ws->ev_cls, 0)); }
         else TLC_HIP_CHECK(hipStreamWaitEvent(s, ws->ev_early, 0));
         // (Round 6: no gate for a pipelined chunk.  With other chunks' tier kernels on every CU the LARGE workgroups are never resident
         // within the bound, so the gate was a 50 us wait -- and a kernel of its own -- in the middle of every first half: in-region timeline
         // profiles/r06_queue_occupancy.txt.  Two libraries in turn, three rounds: 0.5048 -> 0.4930 ms per pipelined batch (-2.3 %).)
         if (!c.pipelined)
-            hipLaunchKernelGGL(tlc_wait_started_dev, dim3(1), dim3(TLC_WAVE), 0, s, (const int*)d_early_started, (const int*)d_early_count,
-                               192, 5000ll);                                // 10 ns ticks
+            hipLaunchKernelGGL(tlc_wait_started_dev, dim3(1), dim3(TLC_WAVE), 0, s, (const int*)&ws->d_ctl->early_started,
+                               (const int*)&ws->d_ctl->early_count, 192, 5000ll);                                // 10 ns ticks
         TLC_HIP_CHECK(hipGetLastError());
     }
     return TLC_OK;
@@ -1058,10 +1089,8 @@ static int front_main_scan(tlc_graph* g, Workspace* ws) {
     const int n_pairs = c.n_pairs, xgrid = c.xgrid, vgrid = c.vgrid;
     const bool early = c.early, use_x = c.use_x, fsplit = c.fsplit, plain = c.plain, pipelined = c.pipelined, bump = c.bump;
     const long long bump_base = c.bump_base;
-    int* d_early_count = ws->d_ctl + 17;
-    unsigned long long* d_bump_top = reinterpret_cast<unsigned long long*>(ws->d_ctl + 20);
-    int* d_bump_overflow = ws->d_ctl + 22;
-    vp.work_counter = ws->d_ctl + 64 + TLC_SCAN_MAX_BLOCKS + 8;         // TLC_X_COUNTERS (8) counters, 64 ints apart, behind the statistics
+    ChunkCtl* ctl = ws->d_ctl;
+    vp.work_counter = &ctl->work[0].next;
     // (about one chunk per RESIDENT extraction wavefront -- 16 per CU, 4 096 -- when batches are pipelined: the machine is full of
     // other chunks' kernels then and the extraction's own tail costs nothing; twice as many for a lone batch.  In-process A/B,
     // x_chunk_div 4096 against 8192 / 16384 / 32768: pipelined batch +0.4 / +2.2 / +2.7 %, latency of one
@@ -1093,8 +1122,8 @@ static int front_main_scan(tlc_graph* g, Workspace* ws) {
     TlcScanParams sp;
     memset(&sp, 0, sizeof(sp));                              // (every optional pointer null unless set below)
     sp.n_pairs = n_pairs; sp.hdr_n = ws->hdr_n; sp.hdr_m2 = ws->hdr_m2;
-    sp.block_agg = ws->d_block_sums; sp.block_flag = ws->d_ctl + 64; sp.sync = ws->d_ctl + 10; sp.totals = ws->d_totals;
-    sp.edge_off = ws->edge_off; sp.tier_count = ws->d_ctl; sp.tier_list = ws->tier_list; sp.small_arena = use_x ? 0 : 1;
+    sp.block_agg = ws->d_block_sums; sp.block_flag = ctl->scan_flag; sp.sync = ctl->scan_sync; sp.totals = ws->d_totals;
+    sp.edge_off = ws->edge_off; sp.tier_count = ctl->tier_count; sp.tier_list = ws->tier_list; sp.small_arena = use_x ? 0 : 1;
     // the plain TLC-GNN image batch at resolution 5: the smallest vicinities go to the lane-per-subgraph kernel (pd_tiny.hip)
     // The MEDIUM tier's split by Pos-edge count exists for the LATENCY of one chunk: the vicinities with the longest serial swaps
     // are submitted behind the scan at once, so that chain starts 50 us earlier (0.79 -> 0.76 ms).  With chunks in flight on both
@@ -1111,13 +1140,11 @@ static int front_main_scan(tlc_graph* g, Workspace* ws) {
     c.mh_front = !mh_split && plain && g->opt_mh_front_pos > 0;
     if (c.mh_front) { sp.mh_min_pos = g->opt_mh_front_pos; sp.mh_compact_only = 1; }
     sp.tiny_ok = (g->opt_tiny && plain && vp.flags == 0u && vp.res == 5) ? 1 : 0;      // (plain: images and none of the filtration outputs)
-    sp.dcm_count = ws->d_ctl + 44; sp.h_dcm = const_cast<int*>(&ws->h_sync_dev->pub_dcm);
-    // (the TINY list by size class as well: d_ctl[48..63] count, zeroed with the control block; the scan's flags start at 64)
-    static_assert(TLC_TINY_BINS <= 16, "the size-class counters of the TINY list live in d_ctl[48..63]");
-    if (sp.tiny_ok) { sp.tiny_bin_count = ws->d_ctl + 48; sp.tiny_bin_list = ws->tiny_bins; sp.h_tiny_bins = const_cast<int*>(ws->h_sync_dev->pub_tiny); }
-    sp.early_list = early ? ws->d_early_list : nullptr; sp.early_count = d_early_count; sp.early_cap = TLC_EARLY_SLOTS;
+    sp.dcm_count = &ctl->dcm_count; sp.h_dcm = const_cast<int*>(&ws->h_sync_dev->pub_dcm);
+    if (sp.tiny_ok) { sp.tiny_bin_count = ctl->tiny_bin_count; sp.tiny_bin_list = ws->tiny_bins; sp.h_tiny_bins = const_cast<int*>(ws->h_sync_dev->pub_tiny); }
+    sp.early_list = early ? ws->d_early_list : nullptr; sp.early_count = &ctl->early_count; sp.early_cap = TLC_EARLY_SLOTS;
     sp.h_early = const_cast<int*>(&ws->h_sync_dev->pub_early);
-    sp.bump_top = bump ? d_bump_top : nullptr; sp.bump_overflow = d_bump_overflow; sp.bump_base = bump_base;
+    sp.bump_top = bump ? &ctl->bump_top : nullptr; sp.bump_overflow = &ctl->bump_overflow; sp.bump_base = bump_base;
     sp.h_overflow = const_cast<int*>(&ws->h_sync_dev->pub_overflow);
     // The arena size and the tier counts come back through mapped host memory: the last block of the scan stores them,
     // fences at system scope and bumps a sequence number the host polls -- no copy kernels, no stream synchronisation on
@@ -1139,11 +1166,9 @@ static int front_main_scan(tlc_graph* g, Workspace* ws) {
 static int front_speculative(tlc_graph* g, Workspace* ws) {
     int rc;
     ChunkCtx& c = ws->ctx;
-    TlcPdParams& pp = c.pp;
     hipStream_t s = c.s;
     const int n_pairs = c.n_pairs;
     const bool early = c.early, plain = c.plain, pipelined = c.pipelined;
-    int* d_bump_overflow = ws->d_ctl + 22;
     // ---- speculative submission of the MID / MEDIUM tiers ---------------------------------------------------------------
     // Their inputs are complete once the scan has run (COUNT wrote the vicinities, the scan the tier lists), so they are
     // submitted behind it right away, with the list lengths on the device and grids / hand-off buffers sized from the
@@ -1175,7 +1200,6 @@ static int front_speculative(tlc_graph* g, Workspace* ws) {
         spec_base[TLC_TIER_MEDWIDE] = spec_base[TLC_TIER_MEDIUM] + (size_t)spec_cap[TLC_TIER_MEDIUM] * tlc_handoff_slot_bytes(TLC_TIER_MEDIUM);
         if ((rc = ensure_handoff(g, ws, spec_base[TLC_TIER_MEDWIDE] +
                                         (size_t)spec_cap[TLC_TIER_MEDWIDE] * tlc_handoff_slot_bytes(TLC_TIER_MEDWIDE))) != TLC_OK) return rc;
-        pp.A_dir = ws->A_dir; pp.A_lw = ws->A_lw;
         // On the caller's stream itself, tier kernels first, then their swap kernels.  (On side streams they would sit behind
         // event waits until the scan is done, and a blocked stream stalls whatever shares its hardware queue -- ROCm maps all
         // streams onto 4 by default: measured, the scan then started 0.1 ms late and took 55 instead of 11 us.)  The fork
@@ -1183,36 +1207,24 @@ static int front_speculative(tlc_graph* g, Workspace* ws) {
         // (only the MEDIUM-sized vicinities with many Pos edges, whose tier kernel + long serial swaps are the longest chain of
         // the small tiers: kernels on one stream do not overlap, and another tier's pair of kernels between that tier kernel and
         // its swap kernel costs more than the host round trip saves -- measured)
-        {
-            const int t = TLC_TIER_MEDHI;
-            pp.tier_list = ws->tier_list + (size_t)t * n_pairs; pp.tier_count = n_pairs; pp.tier_count_dev = ws->d_ctl + t;
-            pp.grid = spec_cap[t]; pp.handoff_cap = spec_cap[t]; pp.phase = 0;
-            pp.handoff = ws->handoff + spec_base[t]; pp.handoff_stride = (long long)tlc_handoff_slot_bytes(t);
-            pp.abort_flag = d_bump_overflow;
-            pp.phase_cycles = g->d_phase ? g->d_phase + 32 * t : nullptr;
-            // (the divide and conquer in this chain only if the previous chunk had vicinities for it: the count is not known yet)
-            pp.dc_count = nullptr; pp.dc_list = nullptr;
-            if (ws->prev_dcm > 0) dc_lists_for(ws, pp, 0);
-            T0(tslot[t], s);
-            if (((g->opt_tier_mask >> t) & 1) && (rc = tlc_launch_pd_tier(t, pp, s)) != TLC_OK) return rc;
-            T1(tslot[t], s);
-            pp.dc_count = nullptr; pp.dc_list = nullptr;
-        }
-        pp.phase = 0;
-        pp.grid = 0; pp.tier_count_dev = nullptr; pp.abort_flag = nullptr; pp.handoff = nullptr; pp.handoff_cap = 0;
+        const int t = TLC_TIER_MEDHI;
+        // (the divide and conquer in this chain only if the previous chunk had vicinities for it: the count is not known yet)
+        TlcPdParams q = tier_params(g, ws, t, n_pairs, ws->handoff + spec_base[t], spec_cap[t], ws->prev_dcm > 0 ? 0 : -1);
+        q.A_dir = ws->A_dir; q.A_lw = ws->A_lw;                  // (the base has no arena yet: complete_base)
+        q.tier_count_dev = &ws->d_ctl->tier_count[t]; q.grid = spec_cap[t]; q.abort_flag = &ws->d_ctl->bump_overflow;
+        T0(tslot[t], s);
+        if (((g->opt_tier_mask >> t) & 1) && (rc = tlc_launch_pd_tier(t, q, s)) != TLC_OK) return rc;
+        T1(tslot[t], s);
     }
     c.spec = spec;
     return TLC_OK;
 }
 
 static int run_chunk_front(tlc_graph* g, Workspace* ws, const int32_t* d_pairs, int n_pairs, int hop, uint32_t flags, int res,
-                     double* d_out_pi, uint8_t* d_out_status, const int64_t* d_ids_off, int32_t* d_out_ids,
-                     double* d_out_f, int32_t* d_out_n, const int64_t* d_edge_offs, int32_t* d_out_edges, int32_t* d_out_m,
-                     int pi_enabled, hipStream_t s, bool pipelined) {
+                           const BatchIO& io, hipStream_t s, bool pipelined) {
     int rc;
     ChunkCtx& c = ws->ctx;
-    if ((rc = front_prepare(g, ws, d_pairs, n_pairs, hop, flags, res, d_out_pi, d_out_status, d_ids_off, d_out_ids, d_out_f, d_out_n,
-                            d_edge_offs, d_out_edges, d_out_m, pi_enabled, s, pipelined)) != TLC_OK) return rc;
+    if ((rc = front_prepare(g, ws, d_pairs, n_pairs, hop, flags, res, io, s, pipelined)) != TLC_OK) return rc;
     // (round 6: the early stream's launches submitted AHEAD of the subgraph-list launch, so that the classification is placed before that
     // launch's 8 192 workgroups ask for every wavefront slot: 0.4872 vs 0.4861 ms per pipelined batch, no difference)
     if ((rc = front_fast(g, ws)) != TLC_OK) return rc;
@@ -1260,29 +1272,36 @@ static int wait_for_sizes(const Workspace* ws, hipStream_t s, unsigned seq) {
     return TLC_OK;
 }
 
+// The last entries of the chunk-wide base of the tier launches: the arena in its final place, the HUGE scratch, the residency count of
+// the LARGE tier.  run_chunk_back, which calls this before its first launch, sees the chunk's context read-only.
+static void complete_base(const tlc_graph* g, Workspace* ws) {
+    TlcPdParams& pp = ws->ctx.base;
+    pp.A_dir = ws->A_dir; pp.A_lw = ws->A_lw;
+    pp.huge_scratch = ws->huge_scratch; pp.huge_stride = (long long)ws->huge_stride;
+    pp.huge_nmax = std::min(g->n_nodes, TLC_MAX_SUBGRAPH_NODES); pp.huge_mmax = (int)std::min<long long>(g->nnz / 2 + 1, TLC_MAX_SUBGRAPH_EDGES); pp.huge_slots = ws->huge_slots;
+    pp.started = &ws->d_ctl->stats.large_started;
+}
+
 // The second half of a chunk: waits (on the host) for the sizes the scan publishes, then submits every launch whose grid or
 // buffers depend on them, and joins the side streams into the chunk's stream.
 static int run_chunk_back(tlc_graph* g, Workspace* ws) {
     int rc;
-    ChunkCtx& c = ws->ctx;
+    const ChunkCtx& c = ws->ctx;                    // (read-only: the launches below take their arguments from it by value)
     // (development: TLC_HOST_TRACE=1 prints where the submitting thread spends a chunk -- front submitted, sizes seen, tiers submitted)
     static const bool host_trace = getenv("TLC_HOST_TRACE") != nullptr;
     const auto ht0 = c.ht0;
     auto ht_us = [&]() { return (double)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - ht0).count() * 1e-3; };
     const double ht_front = c.ht_front;
     double ht_seen = 0;
-    TlcVicParams& vp = c.vp;
-    TlcPdParams& pp = c.pp;
     hipStream_t s = c.s;
     const int n_pairs = c.n_pairs, hop = c.hop, pi_enabled = c.pi_enabled, xgrid = c.xgrid, vgrid = c.vgrid;
     const bool bump = c.bump, use_x = c.use_x, early = c.early, spec = c.spec;
     const long long bump_base = c.bump_base;
-    const unsigned seq = c.seq;
-    size_t (&spec_base)[TLC_N_TIERS] = c.spec_base;
-    int (&spec_cap)[TLC_N_TIERS] = c.spec_cap;
-    bool (&used)[TLC_N_SIDE] = c.used;
+    const size_t (&spec_base)[TLC_N_TIERS] = c.spec_base;
+    const int (&spec_cap)[TLC_N_TIERS] = c.spec_cap;
+    bool (&used)[TLC_N_SIDE] = ws->ctx.used;        // side streams with a launch of this chunk: the one thing the second half adds to
     ws->back_pending = 0;
-    if ((rc = wait_for_sizes(ws, s, seq)) != TLC_OK) return rc;
+    if ((rc = wait_for_sizes(ws, s, c.seq)) != TLC_OK) return rc;
     ht_seen = ht_us();
     std::atomic_thread_fence(std::memory_order_acquire);
     const long long total = ws->h_sync->pub_total;
@@ -1303,8 +1322,8 @@ static int run_chunk_back(tlc_graph* g, Workspace* ws) {
     ws->prev_dcm = n_dcm;
     int todo = tc[0] + tc[1] + tc[2] + tc[3] + tc[4] + tc[5] + tc[6] + tc[7];
     if (c.count_only) {
-        // tlc_vicinity_sizes: the headers are all it asks for (pp.out_n / out_m: the caller's arrays at this chunk's offset)
-        if ((rc = tlc_launch_copy_sizes(n_pairs, ws->hdr_n, ws->hdr_m2, pp.out_n, pp.out_m, s)) != TLC_OK) return rc;
+        // tlc_vicinity_sizes: the headers are all it asks for (out_n / out_m: the caller's arrays at this chunk's offset)
+        if ((rc = tlc_launch_copy_sizes(n_pairs, ws->hdr_n, ws->hdr_m2, c.base.out_n, c.base.out_m, s)) != TLC_OK) return rc;
         todo = 0;
     }
     const bool spec_done = spec && bumped;          // the MID / MEDIUM tiers are already running
@@ -1313,18 +1332,21 @@ static int run_chunk_back(tlc_graph* g, Workspace* ws) {
     ws->prev_tc[TLC_TIER_MID] = tc[TLC_TIER_MID]; ws->prev_tc[TLC_TIER_MEDIUM] = tc[TLC_TIER_MEDIUM]; ws->prev_tc[TLC_TIER_MEDHI] = tc[TLC_TIER_MEDHI];
     ws->prev_tc[TLC_TIER_MEDWIDE] = tc[TLC_TIER_MEDWIDE];
     if (todo > 0) {
-        vp.A_dir = ws->A_dir; vp.A_lw = ws->A_lw;
-        pp.A_dir = ws->A_dir; pp.A_lw = ws->A_lw;
-        pp.huge_scratch = ws->huge_scratch; pp.huge_stride = (long long)ws->huge_stride;
-        pp.huge_nmax = std::min(g->n_nodes, TLC_MAX_SUBGRAPH_NODES); pp.huge_mmax = (int)std::min<long long>(g->nnz / 2 + 1, TLC_MAX_SUBGRAPH_EDGES); pp.huge_slots = ws->huge_slots;
-        pp.started = (int*)(ws->d_stats + 2);
+        complete_base(g, ws);
+        // the arguments of one FILL launch: fill_mode 1 = the pairs of `list`, 2 = every pair outside the heavy tiers, 0 = every pair
+        auto fill_params = [&](int mode, const int* list, int count) {
+            TlcVicParams f = c.vp;
+            f.A_dir = ws->A_dir; f.A_lw = ws->A_lw;                  // (the arena in its final place)
+            f.fill_mode = mode; f.fill_list = list; f.fill_count = count; f.work_count_dev = nullptr;
+            if (use_x) { f.x_fill = 1; f.bump_top = nullptr; }
+            return f;
+        };
         // The extraction ran out of arena: every vicinity below the heavy tiers is laid out by the scan and written by the
         // breadth-first FILL -- before any tier kernel may read it (that includes the SMALL tier, which has no slots of its own here)
         bool filled_all = false;
         if (use_x && !bumped && tc[0] + tc[1] + tc[4] + tc[5] + tc[6] + tc[7] > 0) {
-            vp.fill_mode = (tc[TLC_TIER_LARGE] + tc[TLC_TIER_HUGE] > 0 || n_early > 0) ? 2 : 0; vp.fill_list = nullptr; vp.fill_count = 0;
-            vp.x_fill = 1; vp.bump_top = nullptr; vp.work_count_dev = nullptr;
-            if ((rc = tlc_launch_extract(64, xgrid, g->x_lds64, vp, s)) != TLC_OK) return rc;
+            const TlcVicParams f = fill_params((tc[TLC_TIER_LARGE] + tc[TLC_TIER_HUGE] > 0 || n_early > 0) ? 2 : 0, nullptr, 0);
+            if ((rc = tlc_launch_extract(64, xgrid, g->x_lds64, f, s)) != TLC_OK) return rc;
             filled_all = true;
         }
         // hand-off slots (images only): the tiers with long serial tails run their cycle swap in a second, one-wavefront kernel
@@ -1349,14 +1371,9 @@ static int run_chunk_back(tlc_graph* g, Workspace* ws) {
         // behind it on s (tier kernel only: without a slot a subgraph's cycle swap runs in the tier kernel itself)
         if (spec_done && tc[TLC_TIER_MEDHI] > spec_cap[TLC_TIER_MEDHI]) {
             const int t = TLC_TIER_MEDHI;
-            pp.tier_list = ws->tier_list + (size_t)t * n_pairs; pp.tier_count = tc[t]; pp.tier_count_dev = nullptr;
-            pp.wi_base = spec_cap[t]; pp.grid = tc[t] - spec_cap[t]; pp.handoff_cap = spec_cap[t]; pp.phase = 1;
-            pp.handoff = ws->handoff + spec_base[t]; pp.handoff_stride = (long long)tlc_handoff_slot_bytes(t);
-            pp.abort_flag = nullptr; pp.dc_count = nullptr; pp.dc_list = nullptr;
-            pp.tier_list_hi = nullptr; pp.n_hi = 0;                 // (a chunk on its own has no front list; not left to the order of the launches)
-            pp.phase_cycles = g->d_phase ? g->d_phase + 32 * t : nullptr;
-            if (((g->opt_tier_mask >> t) & 1) && (rc = tlc_launch_pd_tier(t, pp, s)) != TLC_OK) return rc;
-            pp.wi_base = 0; pp.grid = 0; pp.phase = 0; pp.handoff = nullptr; pp.handoff_cap = 0;
+            TlcPdParams q = tier_params(g, ws, t, tc[t], ws->handoff + spec_base[t], spec_cap[t], -1);
+            q.wi_base = spec_cap[t]; q.grid = tc[t] - spec_cap[t]; q.phase = 1;
+            if (((g->opt_tier_mask >> t) & 1) && (rc = tlc_launch_pd_tier(t, q, s)) != TLC_OK) return rc;
         }
         // The tier kernels of all lists first, their second kernels (cycle swap / divide and conquer, same stream, behind a tier kernel
         // that runs > 100 us) afterwards: a launch costs the host 3 - 4 us, and with both kernels of a tier submitted together the last
@@ -1386,35 +1403,28 @@ static int run_chunk_back(tlc_graph* g, Workspace* ws) {
                 TLC_HIP_CHECK(hipEventRecord(ws->ev_fork, s));
                 TLC_HIP_CHECK(hipStreamWaitEvent(ws->side[k], ws->ev_fork, 0));
             }
-            pp.tier_list = ws->tier_list + (size_t)t * n_pairs; pp.tier_count = tc[t];
-            pp.tier_list_hi = nullptr; pp.n_hi = 0;
-            if (t == TLC_TIER_MEDIUM && n_hi > 0) { pp.tier_list_hi = ws->tier_list + (size_t)TLC_TIER_MEDHI * n_pairs; pp.n_hi = n_hi; }
             const size_t hs = pi_enabled ? tlc_handoff_slot_bytes(t) : 0;       // (0: the tier kernel runs the cycle swap itself -- SMALL, MID)
-            pp.handoff = hs ? ws->handoff + hand_base[t] : nullptr;
-            pp.handoff_stride = (long long)hs;
-            pp.handoff_cap = (spec_done && (t == TLC_TIER_MID || t == TLC_TIER_MEDIUM || t == TLC_TIER_MEDWIDE)) ? std::min(tc[t], spec_cap[t]) : tc[t];
-            pp.dc_count = nullptr; pp.dc_list = nullptr; pp.dc_inplace = 0;
-            if (t == TLC_TIER_LARGE) { dc_lists_for(ws, pp, 1); pp.dc_inplace = g->opt_dc_inplace; }
-            if ((t == TLC_TIER_MEDHI || t == TLC_TIER_MEDWIDE) && n_dcm > 0) dc_lists_for(ws, pp, 0);
+            unsigned char* handoff = hs ? ws->handoff + hand_base[t] : nullptr;
             if (hs && t == TLC_TIER_LARGE) {
                 // (the early launch may still be using the first TLC_EARLY_SLOTS slots: this launch takes the ones behind them)
-                int r2 = ensure_handoff_large(g, ws, (size_t)TLC_EARLY_SLOTS + (size_t)tc[t]);
-                if (r2 != TLC_OK) return r2;
-                pp.handoff = ws->handoff_large + (size_t)TLC_EARLY_SLOTS * hs;
+                if (int r2 = ensure_handoff_large(g, ws, (size_t)TLC_EARLY_SLOTS + (size_t)tc[t]); r2 != TLC_OK) return r2;
+                handoff = ws->handoff_large + (size_t)TLC_EARLY_SLOTS * hs;
             }
-            pp.grid = 0; pp.phase = 0; pp.tier_count_dev = nullptr; pp.abort_flag = nullptr;
-            pp.phase_cycles = g->d_phase ? g->d_phase + 32 * t : nullptr;
+            const int handoff_cap = (spec_done && (t == TLC_TIER_MID || t == TLC_TIER_MEDIUM || t == TLC_TIER_MEDWIDE)) ? std::min(tc[t], spec_cap[t]) : tc[t];
+            const int dc = t == TLC_TIER_LARGE ? 1 : (((t == TLC_TIER_MEDHI || t == TLC_TIER_MEDWIDE) && n_dcm > 0) ? 0 : -1);
+            TlcPdParams q = tier_params(g, ws, t, tc[t], handoff, handoff_cap, dc);
+            if (t == TLC_TIER_MEDIUM && n_hi > 0) { q.tier_list_hi = ws->tier_list + (size_t)TLC_TIER_MEDHI * n_pairs; q.n_hi = n_hi; }
+            if (t == TLC_TIER_LARGE) q.dc_inplace = g->opt_dc_inplace;
             const bool timed = !(early && t == TLC_TIER_LARGE) && !(t == TLC_TIER_MEDIUM && spec) && t != TLC_TIER_MEDWIDE;   // (those slots time the early launch / MEDHI / MEDIUM)
             if (timed) T0(tslot[t], ws->side[k]);
-            const bool two = hs && !(pp.flags & TLC_NO_EXT1) &&
+            const bool two = hs && !(q.flags & TLC_NO_EXT1) &&
                              (t == TLC_TIER_MEDIUM || t == TLC_TIER_MID || t == TLC_TIER_MEDHI || t == TLC_TIER_MEDWIDE);
-            if (two) pp.phase = 1;                                                                      // (the tier kernel only)
-            int r = ((g->opt_tier_mask >> t) & 1) ? tlc_launch_pd_tier(t, pp, ws->side[k]) : TLC_OK;   // (development: tiers timed alone)
-            pp.phase = 0;
+            if (two) q.phase = 1;                                                                       // (the tier kernel only)
+            int r = ((g->opt_tier_mask >> t) & 1) ? tlc_launch_pd_tier(t, q, ws->side[k]) : TLC_OK;    // (development: tiers timed alone)
             if (r != TLC_OK) return r;
             used[k] = true;
             if (two) {
-                pend[t].on = true; pend[t].k = k; pend[t].timed = timed; pend[t].pp = pp; pend[t].pp.phase = 2;
+                pend[t].on = true; pend[t].k = k; pend[t].timed = timed; pend[t].pp = q; pend[t].pp.phase = 2;   // (its swap kernel: finish_pending_swaps)
                 return TLC_OK;
             }
             if (timed) T1(tslot[t], ws->side[k]);
@@ -1431,16 +1441,15 @@ static int run_chunk_back(tlc_graph* g, Workspace* ws) {
         T0(2, s);
         for (int t = TLC_TIER_HUGE; t >= TLC_TIER_LARGE; --t) {
             if (tc[t] <= 0) continue;
-            vp.fill_mode = 1; vp.fill_list = ws->tier_list + (size_t)t * n_pairs; vp.fill_count = tc[t];
+            const TlcVicParams f = fill_params(1, ws->tier_list + (size_t)t * n_pairs, tc[t]);
             // the heavy vicinities get 8 wavefronts each (hop <= 2), so that their many long CSR rows are in flight together
             if (use_x) {
                 // (same entry order as the early pass's slots: rows do not depend on which way a vicinity took)
-                vp.x_fill = 1; vp.bump_top = nullptr; vp.work_count_dev = nullptr;
-                if ((rc = tlc_launch_extract(512, std::min(tc[t], TLC_EARLY_WG), g->x_lds512, vp, s)) != TLC_OK) return rc;
+                if ((rc = tlc_launch_extract(512, std::min(tc[t], TLC_EARLY_WG), g->x_lds512, f, s)) != TLC_OK) return rc;
             } else if (hop <= 2)
-                hipLaunchKernelGGL((tlc_vicinity_kernel<true, 512>), dim3(std::min(tc[t], g->vic_slots)), dim3(512), g->vic_lds, s, vp);
+                hipLaunchKernelGGL((tlc_vicinity_kernel<true, 512>), dim3(std::min(tc[t], g->vic_slots)), dim3(512), g->vic_lds, s, f);
             else
-                hipLaunchKernelGGL((tlc_vicinity_kernel<true, 64>), dim3(std::min(tc[t], g->vic_slots)), dim3(TLC_WAVE), g->vic_lds, s, vp);
+                hipLaunchKernelGGL((tlc_vicinity_kernel<true, 64>), dim3(std::min(tc[t], g->vic_slots)), dim3(TLC_WAVE), g->vic_lds, s, f);
             TLC_HIP_CHECK(hipGetLastError());
             if ((rc = launch_side(1, t)) != TLC_OK) return rc;
         }
@@ -1449,7 +1458,7 @@ static int run_chunk_back(tlc_graph* g, Workspace* ws) {
         // path of the batch, starts ~0.35 ms late).  So the main stream -- and with it the SMALL fork and the MEDIUM fill --
         // is held until the LARGE workgroups report themselves resident; the wait is bounded (50 us).
         if (tc[TLC_TIER_LARGE] > 0) {
-            hipLaunchKernelGGL(tlc_wait_started, dim3(1), dim3(TLC_WAVE), 0, s, (const int*)pp.started,
+            hipLaunchKernelGGL(tlc_wait_started, dim3(1), dim3(TLC_WAVE), 0, s, (const int*)c.base.started,
                                std::min(tc[TLC_TIER_LARGE], 192), 5000ll);
             TLC_HIP_CHECK(hipGetLastError());
         }
@@ -1461,19 +1470,13 @@ static int run_chunk_back(tlc_graph* g, Workspace* ws) {
             if (tc[TLC_TIER_TINY] > 0) {
                 if (bumped) { TLC_HIP_CHECK(hipStreamWaitEvent(ws->side[5], ws->ev_scan, 0)); }
                 else { TLC_HIP_CHECK(hipEventRecord(ws->ev_fork, s)); TLC_HIP_CHECK(hipStreamWaitEvent(ws->side[5], ws->ev_fork, 0)); }
-                pp.tier_list = ws->tier_list + (size_t)TLC_TIER_TINY * n_pairs; pp.tier_count = tc[TLC_TIER_TINY];
+                TlcPdParams q = tier_params(g, ws, TLC_TIER_TINY, tc[TLC_TIER_TINY], nullptr, 0, -1);
                 // (by size class, largest first, as the scan binned it: a wavefront of that kernel waits for its slowest lane)
-                pp.tiny_bin_list = nullptr;
                 if (c.tiny_bins) {
-                    pp.tiny_bin_list = ws->tiny_bins; pp.tiny_bin_stride = n_pairs;
-                    for (int b = 0; b < TLC_TINY_BINS; ++b) pp.tiny_bin_cnt[b] = ws->h_sync->pub_tiny[b];
+                    q.tiny_bin_list = ws->tiny_bins; q.tiny_bin_stride = n_pairs;
+                    for (int b = 0; b < TLC_TINY_BINS; ++b) q.tiny_bin_cnt[b] = ws->h_sync->pub_tiny[b];
                 }
-                pp.handoff = nullptr; pp.handoff_stride = 0; pp.handoff_cap = 0; pp.grid = 0; pp.phase = 0;
-                pp.tier_count_dev = nullptr; pp.abort_flag = nullptr;
-                pp.dc_count = nullptr; pp.dc_list = nullptr;
-                pp.tier_list_hi = nullptr; pp.n_hi = 0;             // (the MEDIUM launch's front list, if it went first: not the TINY list's)
-                pp.phase_cycles = g->d_phase ? g->d_phase + 32 * TLC_TIER_TINY : nullptr;
-                int r = ((g->opt_tier_mask >> TLC_TIER_TINY) & 1) ? tlc_launch_pd_tiny(pp, ws->side[5]) : TLC_OK;
+                int r = ((g->opt_tier_mask >> TLC_TIER_TINY) & 1) ? tlc_launch_pd_tiny(q, ws->side[5]) : TLC_OK;
                 if (r != TLC_OK) return r;
                 TLC_HIP_CHECK(hipEventRecord(ws->ev_join[5], ws->side[5]));
                 used[5] = true;
@@ -1486,8 +1489,8 @@ static int run_chunk_back(tlc_graph* g, Workspace* ws) {
             int r;
             if (tc[TLC_TIER_MEDIUM] + tc[TLC_TIER_MEDHI] + tc[TLC_TIER_MEDWIDE] + tc[TLC_TIER_MID] > 0) {
                 if (!bumped && !filled_all) {
-                    vp.fill_mode = (heavy > 0 || n_early > 0) ? 2 : 0; vp.fill_list = nullptr; vp.fill_count = 0;
-                    hipLaunchKernelGGL((tlc_vicinity_kernel<true, 64>), dim3(vgrid), dim3(TLC_WAVE), g->vic_lds, s, vp);
+                    const TlcVicParams f = fill_params((heavy > 0 || n_early > 0) ? 2 : 0, nullptr, 0);
+                    hipLaunchKernelGGL((tlc_vicinity_kernel<true, 64>), dim3(vgrid), dim3(TLC_WAVE), g->vic_lds, s, f);
                     TLC_HIP_CHECK(hipGetLastError());
                 }
                 T1(2, s);
@@ -1587,7 +1590,7 @@ static int acquire_workspace(tlc_graph* g, Workspace** out, bool same) {
         ws->busy = 0;
         if (ws->in_call) {                                    // statistics of a chunk of the call in progress
             unsigned long long tie = 0;
-            TLC_HIP_CHECK(hipMemcpy(&tie, ws->d_stats, sizeof(tie), hipMemcpyDeviceToHost));
+            TLC_HIP_CHECK(hipMemcpy(&tie, &ws->d_ctl->stats.tie_fallback, sizeof(tie), hipMemcpyDeviceToHost));
             g->acc_tie += (long long)tie;
             long long e = 0;
             int rc = chunk_entries(ws, &e);
@@ -1613,10 +1616,8 @@ static int fail_batch(tlc_graph* g, int rc) {
     return rc;
 }
 
-static int run_batch(tlc_graph* g, const int32_t* d_pairs, int64_t n_pairs, int hop, uint32_t flags, int res,
-                     double* d_out_pi, uint8_t* d_out_status, const int64_t* d_ids_off, int32_t* d_out_ids,
-                     double* d_out_f, int32_t* d_out_n, const int64_t* d_edge_offs, int32_t* d_out_edges, int32_t* d_out_m,
-                     int pi_enabled, void* stream, bool join) {
+static int run_batch(tlc_graph* g, const int32_t* d_pairs, int64_t n_pairs, int hop, uint32_t flags, int res, const BatchIO& io,
+                     void* stream, bool join) {
     TLC_REQUIRE(g != nullptr, "graph handle is null");
     TLC_REQUIRE(n_pairs >= 0, "n_pairs < 0");
     TLC_REQUIRE(hop >= 1 && hop <= 64, "hop must be in 1..64");
@@ -1659,13 +1660,7 @@ static int run_batch(tlc_graph* g, const int32_t* d_pairs, int64_t n_pairs, int 
                 return fail_batch(g, TLC_ERR_HIP);
             }
         }
-        // NOTE: ids_off is indexed by the global pair index, the kernels index by chunk-local index
-        rc = run_chunk_front(g, ws, d_pairs + 2 * off, cnt, hop, flags, res,
-                       d_out_pi ? d_out_pi + (size_t)off * res * res : nullptr,
-                       d_out_status ? d_out_status + off : nullptr,
-                       d_ids_off ? d_ids_off + off : nullptr, d_out_ids, d_out_f,
-                       d_out_n ? d_out_n + off : nullptr, d_edge_offs ? d_edge_offs + off : nullptr, d_out_edges,
-                       d_out_m ? d_out_m + off : nullptr, pi_enabled, m, !inline_main);
+        rc = run_chunk_front(g, ws, d_pairs + 2 * off, cnt, hop, flags, res, io.chunk(off, res), m, !inline_main);
         if (rc != TLC_OK) return fail_batch(g, rc);
         ws->busy = 1; ws->in_call = 1; ws->n_pairs = cnt;
         g->last_ws = ws;
@@ -1688,6 +1683,11 @@ static int run_batch(tlc_graph* g, const int32_t* d_pairs, int64_t n_pairs, int 
     return TLC_OK;
 }
 
+// the outputs of tlc_pd_pi_batch / tlc_pd_pi_batch_async: images and status bytes, none of the filtration outputs
+static BatchIO image_batch(double* d_out_pi, uint8_t* d_out_status) {
+    return {d_out_pi, d_out_status, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 1};
+}
+
 extern "C" int tlc_pd_pi_batch(tlc_graph* g, const int32_t* d_pairs, int64_t n_pairs, int hop, uint32_t flags, int res,
                                double* d_out_pi, uint8_t* d_out_status, void* stream) {
     TLC_REQUIRE(n_pairs == 0 || d_out_pi != nullptr, "out_pi is null");
@@ -1696,8 +1696,7 @@ extern "C" int tlc_pd_pi_batch(tlc_graph* g, const int32_t* d_pairs, int64_t n_p
                       "[0, 1]); use tlc_vicinity_filtration + tlc_pd_from_filtration + tlc_pi_raster");
         return TLC_ERR_UNSUPPORTED;
     }
-    return run_batch(g, d_pairs, n_pairs, hop, flags, res, d_out_pi, d_out_status, nullptr, nullptr, nullptr, nullptr, nullptr,
-                     nullptr, nullptr, 1, stream, true);
+    return run_batch(g, d_pairs, n_pairs, hop, flags, res, image_batch(d_out_pi, d_out_status), stream, true);
 }
 
 // tlc_pd_pi_batch without the final join: the batch is ordered AFTER what `stream` holds at the time of the call (its inputs may
@@ -1711,8 +1710,7 @@ extern "C" int tlc_pd_pi_batch_async(tlc_graph* g, const int32_t* d_pairs, int64
         tlc_set_error("tlc_pd_pi_batch_async: TLC_NO_NORM is not supported by the fused image stage");
         return TLC_ERR_UNSUPPORTED;
     }
-    return run_batch(g, d_pairs, n_pairs, hop, flags, res, d_out_pi, d_out_status, nullptr, nullptr, nullptr, nullptr, nullptr,
-                     nullptr, nullptr, 1, stream, false);
+    return run_batch(g, d_pairs, n_pairs, hop, flags, res, image_batch(d_out_pi, d_out_status), stream, false);
 }
 
 // makes `stream` wait for every batch submitted on this handle so far (asynchronous: nothing is waited for on the host)
@@ -1733,8 +1731,8 @@ extern "C" int tlc_vicinity_filtration(tlc_graph* g, const int32_t* d_pairs, int
     TLC_REQUIRE(d_node_offs && d_out_ids && d_out_f && d_out_n, "null output");
     const int ne = (d_edge_offs != nullptr) + (d_out_edges != nullptr) + (d_out_m != nullptr);
     TLC_REQUIRE(ne == 0 || ne == 3, "edge_offs / out_edges / out_m must be given together");
-    return run_batch(g, d_pairs, n_pairs, hop, flags, 5, nullptr, d_out_status, d_node_offs, d_out_ids, d_out_f, d_out_n,
-                     d_edge_offs, d_out_edges, d_out_m, 0, stream, true);
+    const BatchIO io = {nullptr, d_out_status, d_node_offs, d_out_ids, d_out_f, d_out_n, d_edge_offs, d_out_edges, d_out_m, 0};
+    return run_batch(g, d_pairs, n_pairs, hop, flags, 5, io, stream, true);
 }
 
 extern "C" int tlc_pd_pi_batch_stats(tlc_graph* g, int64_t* h_out, void* stream) {
@@ -1748,7 +1746,7 @@ extern "C" int tlc_pd_pi_batch_stats(tlc_graph* g, int64_t* h_out, void* stream)
         if (!ws->in_call) continue;
         if (ws->busy) { TLC_HIP_CHECK(hipEventSynchronize(ws->ev_done)); ws->busy = 0; }   // (an asynchronous call not joined yet)
         unsigned long long v = 0;
-        TLC_HIP_CHECK(hipMemcpy(&v, ws->d_stats, sizeof(v), hipMemcpyDeviceToHost));
+        TLC_HIP_CHECK(hipMemcpy(&v, &ws->d_ctl->stats.tie_fallback, sizeof(v), hipMemcpyDeviceToHost));
         tie += (long long)v;
         long long e = 0;
         int rc = chunk_entries(ws, &e);
@@ -1828,8 +1826,8 @@ extern "C" int tlc_vicinity_sizes(tlc_graph* g, const int32_t* d_pairs, int64_t 
     TLC_REQUIRE(g != nullptr, "graph handle is null");
     TLC_REQUIRE(n_pairs == 0 || (d_n && d_m), "null output");
     g->count_only = 1;
-    const int rc = run_batch(g, d_pairs, n_pairs, hop, flags, 5, nullptr, nullptr, nullptr, nullptr, nullptr, d_n, nullptr, nullptr, d_m,
-                             0, stream, true);
+    const BatchIO io = {nullptr, nullptr, nullptr, nullptr, nullptr, d_n, nullptr, nullptr, d_m, 0};
+    const int rc = run_batch(g, d_pairs, n_pairs, hop, flags, 5, io, stream, true);
     g->count_only = 0;
     return rc;
 }
@@ -1914,13 +1912,13 @@ extern "C" int tlc_debug_dc_stats(tlc_graph* g, long long* h_out, void* stream) 
     TLC_ON_DEVICE(g->device);
     { int rc_p = finish_pending(g); if (rc_p != TLC_OK) return rc_p; }
     TLC_HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
-    unsigned long long v[4] = {0, 0, 0, 0};
+    ChunkCtl::Stats st = {};
     if (g->last_ws) {
         if (g->last_ws->busy) { TLC_HIP_CHECK(hipEventSynchronize(g->last_ws->ev_done)); g->last_ws->busy = 0; }
-        TLC_HIP_CHECK(hipMemcpy(v, g->last_ws->d_stats, sizeof(v), hipMemcpyDeviceToHost));
+        TLC_HIP_CHECK(hipMemcpy(&st, &g->last_ws->d_ctl->stats, sizeof(st), hipMemcpyDeviceToHost));
     }
-    h_out[0] = (long long)v[1];
-    h_out[1] = (long long)v[3];
+    h_out[0] = (long long)st.dc_swaps;
+    h_out[1] = (long long)st.dc_given_back;
     return TLC_OK;
 }
 
