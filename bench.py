@@ -16,6 +16,11 @@ the encoder of leg 2 either node-row sharded with one RCCL all-gather per layer 
 `--gpus N` without a launcher starts its own N ranks (torch.distributed.run, before any GPU call).  Rank 0 prints ONE JSON line.
 `--dump-outputs DIR`: rank 0 also writes what the timed region's LAST step computed as DIR/<name>.npy (see dump_outputs); the
 inputs are seeded, so two builds run with the same arguments can be compared output for output.
+A plain run does what the headline needs and no more: set-up, warm-up, the K timed steps, the dump, the line (`value`, `ms_per_step`,
+the legs' times, `pi_latency_ms`, `encoder`, `dist`).  `--full` adds everything else the line can carry, each with runs of its own:
+the rocprofv3 counter passes (child processes, before this one touches the GPU), the bit-for-bit check of what the timed region
+wrote, the other batch mode, two forwards in flight, strong scaling, the sweeps, the other graph shapes, Ricci curvature, PDGNN, the
+per-kernel rooflines and the CPU baseline; --no-cpu-baseline, --no-sweep and --no-traffic prune a --full run and mean nothing without it.
 """
 import argparse
 import json
@@ -90,7 +95,7 @@ def measure_traffic():
     try:
         for cname, sub in (("FETCH_SIZE", "fetch"), ("WRITE_SIZE", "write")):
             cmd = [exe, "--pmc", cname, "--output-format", "csv", "-d", os.path.join(tmp, sub), "--", sys.executable,
-                   os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-sweep"]
+                   os.path.join(ROOT, "bench.py"), "--full", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-sweep"]
             pr = subprocess.Popen(cmd, cwd=tmp, env=env, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, start_new_session=True)
             try:
                 rc = pr.wait(timeout=150)
@@ -130,7 +135,7 @@ def measure_issue():
                                         ("SQ_INSTS", "SQ_INSTS_SMEM", "SQ_INSTS_VMEM_RD", "SQ_INSTS_VMEM_WR", "SQ_INSTS_BRANCH"))):
             sub = os.path.join(tmp, "issue%d" % pi_)
             cmd = [exe, "--pmc"] + list(counters) + ["--output-format", "csv", "-d", sub, "--",
-                   sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-sweep"]
+                   sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-sweep"]
             pr = subprocess.Popen(cmd, cwd=tmp, env=env, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, start_new_session=True)
             try:
                 rc = pr.wait(timeout=240)
@@ -377,8 +382,11 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-sweep", action="store_true", help="skip the auxiliary blocks (profiling runs)")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline, everything else the line can carry: counter passes, the check of the timed region's "
+                         "outputs, the other batch mode, strong scaling, sweeps, other shapes, Ricci, PDGNN, rooflines, CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baselines")
+    ap.add_argument("--no-sweep", action="store_true", help="--full without the auxiliary blocks (profiling runs)")
     ap.add_argument("--rotate-batches", action="store_true",
                     help="timed region over different 37 676-pair batches (see rotated_batches) instead of the same one")
     ap.add_argument("--encoder", default="auto", choices=["auto", "allgather", "replicated"],
@@ -410,7 +418,8 @@ def main():
     # roofline.traffic: two child passes of this script under rocprofv3 --pmc, BEFORE this process initialises the GPU
     pre_traffic, pre_traffic_detail = None, "not attempted"
     pre_issue, pre_issue_detail = None, "not attempted"
-    if args.gpus == 1 and int(os.environ.get("WORLD_SIZE", "1")) == 1 and not args.no_sweep and not args.no_traffic \
+    aux = args.full and not args.no_sweep                              # the auxiliary blocks below, each with runs of its own
+    if aux and args.gpus == 1 and int(os.environ.get("WORLD_SIZE", "1")) == 1 and not args.no_traffic \
             and not os.environ.get("TLC_BENCH_CHILD"):
         pre_traffic, pre_traffic_detail = measure_traffic()
         pre_issue, pre_issue_detail = measure_issue()
@@ -575,7 +584,7 @@ def main():
     # Beside the leg (not part of it, nothing below reads it): the same forward with TWO in flight, each on its own stream and
     # its own buffers.  One forward is four small kernels back to back, each too short to fill 256 CUs; what two of them
     # together take per forward says how much of the leg's time is the machine standing half empty.
-    if world == 1 and enc_mode == "replicated":
+    if args.full and world == 1 and enc_mode == "replicated":
         try:
             prob_b = torch.empty_like(prob)
             pair_of_legs = [legs["replicated"], make_encoder("replicated", prob_out=prob_b)]
@@ -698,7 +707,9 @@ def main():
     # The snapshot of the last step's rows is what `cpu_baseline` checks against the oracle below.
     timed_equal, timed_checked = True, 0
     timed_snapshot = None
-    for s_ in range(max(K - 3, 0), K):
+    if not args.full and args.dump_outputs:
+        timed_snapshot = (pi_outs[(K - 1) % 3].clone(), pi_sts[(K - 1) % 3].clone(), None)
+    for s_ in range(max(K - 3, 0), K) if args.full else ():
         b_ = rot[s_ % len(rot)] if args.rotate_batches else pi_pairs
         ref_o, ref_s = g.pd_pi_batch(b_, hop)
         torch.cuda.synchronize()
@@ -742,15 +753,16 @@ def main():
             import torch.distributed as dist
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
         return float(t.item())
-    t_other = pi_region(not args.rotate_batches)
-    g.pd_pi_batch(pi_pairs, hop, out=pi_out, status=pi_status)          # the headline batch's header for sizes()/stats() below
-    torch.cuda.synchronize()
+    if args.full:
+        t_other = pi_region(not args.rotate_batches)
+        g.pd_pi_batch(pi_pairs, hop, out=pi_out, status=pi_status)      # the headline batch's header for sizes()/stats() below
+        torch.cuda.synchronize()
 
     # ---- strong scaling (every N): ONE list -- the non-edges of the graph inside each other's hop-ball, the part of the
     # reference's negative sweep that has non-zero images (loaddatas.py:44-53, riccidist2dgm.py:362-370) -- cut into N
     # contiguous shards of equal estimated cost, each rank runs its shard, the image rows are exchanged (one all-gather) ------
     strong = None
-    if not args.no_sweep:
+    if aux:
         try:
             ci = engine.ComplementIndex(wl["rowptr"], wl["col"], device=local_rank)
             near, ranks = engine.near_pairs(ci, hop)
@@ -803,7 +815,7 @@ def main():
     # auxiliary (untimed region, single pass): the negative sweep of loaddatas.py:44-53 is dominated by pairs with
     # d(u,v) > hop; report the throughput on 2^20 uniformly random pairs (PI-C of SURVEY.md 8d) next to the headline
     sweep = None
-    if rank == 0 and not args.no_sweep:
+    if rank == 0 and aux:
         g.set_timing(False)
         rsw = np.random.RandomState(99)
         sw_pairs = torch.from_numpy(rsw.randint(0, n, size=(1 << 20, 2)).astype(np.int32)).to(dev)
@@ -825,7 +837,7 @@ def main():
     # tlc_pd_pi_batch in 2^22-pair chunks, informative rows kept by tlc_select_rows.  List order (the reference's seeded
     # shuffle permutes the same list; it costs ~20 s of host MT19937 and does not change the device work).
     full_sweep = None
-    if rank == 0 and not args.no_sweep:
+    if rank == 0 and aux:
         try:
             from tlc_gnn_amd import pi_cache
             ci = engine.ComplementIndex(wl["rowptr"], wl["col"], device=local_rank)
@@ -858,7 +870,7 @@ def main():
     # auxiliary (untimed region): BASELINE.json's other graph shapes (hop 1, TLCGNN.py:102) -- all positive pairs of the
     # shaped synthetic graph through tlc_pd_pi_batch, one call, device-resident; host wall clock
     other_shapes = None
-    if rank == 0 and not args.no_sweep:
+    if rank == 0 and aux:
         other_shapes = {}
         for shape_name in ("Cora", "PPI", "Photo", "Computers"):
             try:
@@ -885,7 +897,7 @@ def main():
     # auxiliary (untimed region): the step before the path -- Ollivier-Ricci curvature (alpha 0.5, Sinkhorn reg 0.1) of every
     # edge of the training graph (loaddatas.py:105-123), the producer of the path's edge weights
     ricci = None
-    if rank == 0 and not args.no_sweep:
+    if rank == 0 and aux:
         try:
             te_ = wl["train_edges"]
             rp_, col_ = wl["rowptr"], wl["col"]
@@ -913,13 +925,13 @@ def main():
     # (n ~ Poisson(25), a random tree plus a few ring-closing edges, degree filtration / (max + 1e-10), data_utils_GC.py:117-119),
     # one block-diagonal batch, weights random-init with a fixed seed.  Reported beside `value`, never part of it.
     pdgnn = None
-    if rank == 0 and not args.no_sweep:
+    if rank == 0 and aux:
         try:
             pdgnn = pdgnn_aux(torch, dev)
         except Exception as ex:                                   # the headline line must not depend on the auxiliary
             pdgnn = {"error": repr(ex)}
     pdgnn_amazon = None
-    if rank == 0 and not args.no_sweep:
+    if rank == 0 and aux:
         try:
             pdgnn_amazon = pdgnn_amazon_aux(torch, dev)
         except Exception as ex:
@@ -927,7 +939,7 @@ def main():
     # auxiliary (untimed): the LP leg's two bounded kernels on their own -- the feature GEMM against the f32 MFMA peak and
     # the scatter-add SpMM against HBM (north_star); torch events on the current stream, which is where ops.* enqueue
     lp_roof = None
-    if rank == 0:
+    if rank == 0 and args.full:
         def _avg_us(fn, reps=20):
             """device time per call: `reps` calls replayed from a captured graph where that works (one rank, no collective inside) -- a
             call through the Python wrappers takes the host 10 - 25 us, longer than most of these kernels run, so that timed over
@@ -1046,6 +1058,25 @@ def main():
                                         "(~370 fp64 instructions per point), not HBM"}
         del bd, offs_r
     if rank == 0:
+        # what the timed region and the warm-up measured: the whole line of a plain run, the head of a --full one
+        headline = {
+            "metric": "persistence-images/sec + LP-forward edges/sec, PubMed-scale, 1/2/4/8 GPU",
+            "value": world * E * K / t_pi,
+            "unit": "persistence-images/sec",
+            "lp_forward_edges_per_sec": world * dec_pairs.shape[0] * K / t_lp,
+            "n_gpus": world, "steps": K, "warmup": args.warmup, "full": bool(args.full),
+            "ms_per_step": wall / K * 1e3,
+            "pi_ms_per_step": t_pi / K * 1e3, "lp_ms_per_step": t_lp / K * 1e3,
+            "pi_ms_per_step_median": float(np.median(pi_steps)), "lp_ms_per_step_median": float(np.median(lp_steps)),
+            "pi_latency_ms": float(np.median(lat_plain)),
+            "dist": dist_info,
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "dtype": "f64", "data": "synthetic",
+            "encoder": {"mode": enc_mode, "lp_submit": lp_submit, "lp_leg_ms": encoder_ms,
+                        "note": "LP leg (encode + decode) timed per mode before the timed region, max over ranks; N=1 has no exchange"},
+        }
+        out = headline
+    if rank == 0 and args.full:
         # per-pair byte model and tier of every pair of the batches the timed region ran
         used = [rot[j] for j in range(min(K, len(rot)))] if args.rotate_batches else [pi_pairs]
         weight = [len(range(j, K, len(rot))) for j in range(len(used))] if args.rotate_batches else [K]
@@ -1134,19 +1165,8 @@ def main():
         else:
             roofline_issue = {"error": str(pre_issue_detail)}
         out = {
-            "metric": "persistence-images/sec + LP-forward edges/sec, PubMed-scale, 1/2/4/8 GPU",
-            "value": world * E * K / t_pi,
-            "unit": "persistence-images/sec",
-            "lp_forward_edges_per_sec": world * dec_pairs.shape[0] * K / t_lp,
-            "n_gpus": world, "steps": K, "warmup": args.warmup,
-            "ms_per_step": wall / K * 1e3,
-            "pi_ms_per_step": t_pi / K * 1e3, "lp_ms_per_step": t_lp / K * 1e3,
-            "pi_ms_per_step_median": float(np.median(pi_steps)), "lp_ms_per_step_median": float(np.median(lp_steps)),
-            "pi_latency_ms": float(np.median(lat_plain)),
+            **headline,
             "timed_outputs_equal": bool(timed_equal), "timed_outputs_checked": int(timed_checked),
-            "dist": dist_info,
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "f64", "data": "synthetic",
             "config": {"workload": "PubMed-shaped synthetic graph (N=19717, M=44324, F=500, seed 1234), hop=2; per GPU and step: "
                                    "PI-A = %s -> 5x5 persistence images, and one TLCGNN forward "
                                    "(GCN 500->100->16 encode + fused decode of %d pairs, image rows resident)"
@@ -1184,8 +1204,6 @@ def main():
                 "note": "the same K-step region with %s" % ("the one train-positive batch every step" if args.rotate_batches else
                                                             "8 different 37 676-pair samples of the positive pairs in turn: the "
                                                             "previous chunk's sizes never match exactly")},
-            "encoder": {"mode": enc_mode, "lp_submit": lp_submit, "lp_leg_ms": encoder_ms,
-                        "note": "LP leg (encode + decode) timed per mode before the timed region, max over ranks; N=1 has no exchange"},
             "strong_scaling": strong,
             "kernel_ms": kavg,
             "kernel_ms_note": "'%s' (the roofline kernel): HIP events kept by the library in a ring and read after the timed region, "
@@ -1199,7 +1217,8 @@ def main():
             "pdgnn": pdgnn,
             "pdgnn_amazon": pdgnn_amazon,
         }
-        if world == 1 and not args.no_cpu_baseline:
+    if rank == 0:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             # the CPU restatement (oracle/tlc_oracle.c, a port of the reference's algorithm) on this box's host cores,
             # same batch, bounded sample.  A reported baseline, not a target.
             from oracle import oracle

@@ -46,7 +46,7 @@ def fold(fetch_dir, write_dir):
     return res, dict(out), raw
 
 
-NOTE = ("rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE in separate passes over `bench.py --steps 3 --warmup 1 --no-sweep`; bytes per batch = "
+NOTE = ("rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE in separate passes over `bench.py --full --steps 3 --warmup 1 --no-sweep`; bytes per batch = "
         "(FETCH_SIZE + WRITE_SIZE) * 1024 summed over the pass / batches in the pass (one of them is the 75 352-pair set-up batch of the decode "
         "table). gfx950 caveat (MI355X_MICROARCH.md, HBM): FETCH_SIZE counts 64 B per 128-B request for wide coalesced streams and is "
         "uncalibrated for the 4/8-byte gathers these kernels issue, so the read side is a lower bound; the working set (CSR 1.1 MB, arena "
