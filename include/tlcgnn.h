@@ -57,7 +57,7 @@ extern "C" {
                                       tlc_hks_batch: the graph has more than TLC_HKS_NMAX nodes; its slice of
                                       the output is left untouched */
 #define TLC_ST_NOT_CONVERGED   6   /* tlc_hks_batch: the Jacobi sweeps did not converge within their bound; slice untouched */
-#define TLC_ST_BAD_INPUT       7   /* tlc_hks_batch: offsets out of order / beyond the totals, an edge with an id outside
+#define TLC_ST_BAD_INPUT       7   /* tlc_hks_batch, tlc_struct_batch: offsets out of order / beyond the totals, an edge with an id outside
                                       0 .. n-1, a self loop (nothing of it is dereferenced) or an unordered pair listed
                                       more than once, in either orientation; slice untouched */
 
@@ -433,6 +433,40 @@ int tlc_hks_batch_work_bytes(int64_t n_graphs, int64_t total_nodes, int64_t tota
 int tlc_hks_batch(const int64_t* d_node_ptr, const int64_t* d_edge_ptr, const int32_t* d_edges, int64_t n_graphs, int64_t total_nodes,
                   int64_t total_edges, const double* h_times, int32_t n_times, uint32_t flags, double* d_out, uint8_t* d_status,
                   void* d_work, int64_t work_bytes, void* stream);
+
+/* ---- Degree / centrality / clustering filtrations (Knowledge_Distillation/data_utils_LP.py:131-133; data_utils_NC.py:124-135: networkx's
+ * degree(), degree_centrality and clustering of the vicinity, then / (max + 1e-10)) ------------------------------------------------------
+ * For the packed batch of tlc_hks_batch (simple undirected graphs, each edge ONCE, local ids), per node v of a graph of n nodes with
+ * d = its degree and t = the sum over its incident edges (v, w) of |N(v) & N(w)| (each triangle at v twice):
+ *   TLC_STRUCT_DEGREE      d
+ *   TLC_STRUCT_CENTRALITY  d * (1.0 / (n - 1.0)) -- the reciprocal first, then one multiply; n == 1: 1.0
+ *   TLC_STRUCT_CLUSTERING  t / (d * (d - 1)); 0.0 where t == 0
+ * d_out f64[popcount(kinds), total_nodes], rows in the order degree, centrality, clustering of the bits set in `kinds`; each row bit-equal
+ * to a call with that kind alone.  TLC_STRUCT_NORMALISE: each graph's values divided by (their max + 1e-10).
+ * d and t are integers, counted with integer atomics or fixed-order sums, followed by one or two correctly rounded fp64 operations; no
+ * floating-point atomics: the values are bit for bit those of the host route (`structural_filtration`), run to run, alone or in any batch.
+ * d_status uint8[n_graphs]: TLC_ST_OK, or TLC_ST_BAD_INPUT -- offsets out of order or beyond the totals, an id outside 0 .. n-1, a self
+ * loop, an unordered pair listed twice in either orientation (more than n (n - 1) / 2 edges is refused as such without looking at them),
+ * more than 2^31 - 1 nodes (int32 ids cannot name them); nothing out of range is dereferenced, the graph's slice of d_out is left untouched
+ * and no other graph is affected.  There is no size cap: a graph of any size the int32 ids can express is computed on the device.  A graph
+ * without nodes: TLC_ST_OK, nothing written.
+ * Tiers, binned on the device (nothing is read back, no host wait): <= TLC_STRUCT_WAVE_NMAX nodes a wavefront each (a u64 adjacency row per
+ * lane in LDS); <= TLC_STRUCT_LDS_SMALL_NMAX and <= TLC_STRUCT_LDS_NMAX a workgroup each (adjacency bitmap in LDS, work per edge); larger: a
+ * workgroup each over a CSR built in d_work, neighbour bitmaps of TLC_STRUCT_BITMAP_BITS bits per wavefront in LDS, 64-bit counts.
+ * d_work: tlc_struct_batch_work_bytes() bytes, 16-byte aligned: the tier lists (16 B per graph) and, when total_nodes > TLC_STRUCT_LDS_NMAX,
+ * 16 B per node + 16 B per graph + 8 B per edge for the CSR tier.  Runs on the caller's current device, asynchronous on `stream`. */
+#define TLC_STRUCT_DEGREE           0x1u
+#define TLC_STRUCT_CENTRALITY       0x2u
+#define TLC_STRUCT_CLUSTERING       0x4u
+#define TLC_STRUCT_NORMALISE        0x100u
+#define TLC_STRUCT_WAVE_NMAX        64      /* most nodes of a graph that one wavefront computes */
+#define TLC_STRUCT_LDS_SMALL_NMAX   256     /* ... whose adjacency bitmap takes the narrow LDS tier (12 KiB) */
+#define TLC_STRUCT_LDS_NMAX         1024    /* ... whose adjacency bitmap fits LDS: 1024 rows of 16 + 1 u64 words, 136 KiB of the 160 KiB */
+#define TLC_STRUCT_BITMAP_BITS      65536   /* CSR tier: bits of one wavefront's neighbour bitmap (8 KiB) */
+int tlc_struct_batch_work_bytes(int64_t n_graphs, int64_t total_nodes, int64_t total_edges, uint32_t kinds, int64_t* bytes);
+int tlc_struct_batch(const int64_t* d_node_ptr, const int64_t* d_edge_ptr, const int32_t* d_edges, int64_t n_graphs,
+                     int64_t total_nodes, int64_t total_edges, uint32_t kinds, uint32_t flags, double* d_out,
+                     uint8_t* d_status, void* d_work, int64_t work_bytes, void* stream);
 
 /* ---- M4-M6: PDGNN layer forward (Knowledge_Distillation/gat_conv.py:113-216) ----------------------
  * One GATConv(heads=1, new_node_feat, use_edge_attn) layer on a block-diagonal batch of graphs whose

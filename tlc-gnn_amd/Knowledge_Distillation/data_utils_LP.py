@@ -8,7 +8,8 @@ part of the subgraph (:111), there is no connectivity assert (an unreachable roo
 normalisation divides by max + 1e-10 (:64).  Node labels of a vicinity are positions in ASCENDING original id (the reference's
 `convert_node_labels_to_integers` order is arbitrary); edges are listed once, lower label first.
 filt='degree' (:131-133) and 'hks' (:128-130, the signature's default): the same vicinities, f from `structural_filtration` (host side:
-networkx's arithmetic, scipy's eigh); hks_backend='device': 'hks' from `tlc_hks_batch` instead (a Jacobi eigensolver in HIP, values to rounding).  The CBGNN cycle helpers (:256-448, dead code in the reference) and `call` are not reproduced.
+networkx's arithmetic, scipy's eigh); hks_backend='device': 'hks' from `tlc_hks_batch` instead (a Jacobi eigensolver in HIP, values to rounding);
+struct_backend='device': 'degree' / 'centrality' / 'clustering' from `tlc_struct_batch` instead (integer counting in HIP, the same bits).  The CBGNN cycle helpers (:256-448, dead code in the reference) and `call` are not reproduced.
 """
 import sys
 
@@ -21,6 +22,8 @@ KD_LP_FLAGS = _lib.INCLUDE_ROOTS | _lib.NORM_EPS | _lib.UNREACHABLE_100
 
 STRUCTURAL_FILTS = ("degree", "centrality", "clustering", "hks")
 HKS_BACKENDS = ("host", "device")
+STRUCT_BACKENDS = ("host", "device")
+STRUCT_DEVICE_FILTS = ("degree", "centrality", "clustering")      # what struct_backend='device' computes with tlc_struct_batch
 # graphs of the most recent hks_backend='device' computation (this module's, data_utils_NC's or data_utils_GC's) that the device did not
 # take -- more than _lib.HKS_NMAX nodes, or no convergence -- and that `hks_signature` computed on the host instead
 hks_host_fallback = 0
@@ -29,6 +32,11 @@ hks_host_fallback = 0
 def check_hks_backend(hks_backend):
     if hks_backend not in HKS_BACKENDS:
         raise ValueError("hks_backend should be one of %s, not %r" % (HKS_BACKENDS, hks_backend))
+
+
+def check_struct_backend(struct_backend):
+    if struct_backend not in STRUCT_BACKENDS:
+        raise ValueError("struct_backend should be one of %s, not %r" % (STRUCT_BACKENDS, struct_backend))
 
 
 def hks_signature(n, edges, time):
@@ -125,6 +133,20 @@ def hks_filtration_device(node_ptr, edge_ptr, edges, hks_time, total_nodes):
     return f
 
 
+def struct_filtration_device(kind, node_ptr, edge_ptr, edges, total_nodes):
+    """The 'degree' / 'centrality' / 'clustering' cases of `structural_filtration` on the device: `engine.struct_batch` (tlc_struct_batch)
+    on the CUDA tensors of a packed batch -> CUDA float64[sum n], normalised per graph, the host function's values bit for bit.  Offsets
+    and edges stay on the device; one byte comes back, whether any graph was refused.  There is no size cap and no host fallback.
+    The device takes SIMPLE graphs, each undirected edge listed once: TLC_ST_BAD_INPUT (offsets out of order, an id outside 0 .. n-1, a
+    self loop, an unordered pair listed twice -- in the same or in both directions) raises RuntimeError; nothing is returned for such a
+    batch.  The host route differs there: it counts repeated entries into a multigraph's degrees."""
+    f, st = engine.struct_batch(node_ptr, edge_ptr, edges, kind, normalise=True, total_nodes=total_nodes)
+    if bool((st != _lib.ST_OK).any()):
+        raise RuntimeError("struct_backend='device': a graph has offsets out of order, an edge id out of range, a self loop or a repeated "
+                           "edge (the device wants each undirected edge once; struct_backend='host' counts repeated edges into the degrees)")
+    return f[0]
+
+
 class Vicinities:
     """Device-resident weighted graph for PDGNN's edge-centred vicinities; build once, query many pairs.
     ricci_curv=None: no curvature (the structural filtrations need only the vicinities): unit edge weights."""
@@ -140,7 +162,7 @@ class Vicinities:
         for old, new in self.dict_node.items():
             self.inv[new] = old
 
-    def batch(self, pairs, hop, node_cap=None, edge_cap=None, flags=None, filt='ricci', hks_time=0.1, hks_backend='host'):
+    def batch(self, pairs, hop, node_cap=None, edge_cap=None, flags=None, filt='ricci', hks_time=0.1, hks_backend='host', struct_backend='host'):
         """pairs: [E,2] original labels -> dict of CUDA tensors: node_ptr int64[E+1], edge_ptr int64[E+1], ids int64 (original
         labels, ascending inside a vicinity), f float64, edges int32 [sum m, 2] (local ids, lower first), status uint8[E].
         Vicinities without an edge have empty slices (the reference returns (None, None) for them, :117-118).
@@ -148,10 +170,13 @@ class Vicinities:
         `structural_filtration` of the extracted vicinities).
         hks_backend: 'host' (scipy's eigh per vicinity on copies of offsets and edges) or 'device' (`hks_filtration_device` on the tensors
         the extraction produced; the dict then also has hks_host_fallback); it matters for filt='hks' only.
+        struct_backend: 'host' (`structural_filtration` on copies of offsets and edges) or 'device' (`struct_filtration_device` on the tensors
+        the extraction produced: the same bits, no copy of offsets or edges); it matters for filt 'degree' / 'centrality' / 'clustering' only.
         node_cap / edge_cap: per-pair capacities of an intermediate layout (one extraction; raises if a vicinity is larger); neither
         given: sizes first, exact offsets, two extractions (`tlc_vicinity_sizes` + `tlc_pack_offsets`)."""
         import torch
         check_hks_backend(hks_backend)
+        check_struct_backend(struct_backend)
         dev_graph = self._g2p._device_graph()
         mapped = torch.from_numpy(self._g2p._map_pairs(pairs)).cuda()
         fl = KD_LP_FLAGS if flags is None else flags
@@ -184,7 +209,9 @@ class Vicinities:
                 out_f = hks_filtration_device(node_ptr, edge_ptr, out_e, hks_time, int(tot_n))
                 return dict(node_ptr=node_ptr, edge_ptr=edge_ptr, ids=out_ids, f=out_f, edges=out_e, status=st, pair_of_node=pn, pair_of_edge=pe,
                             hks_host_fallback=hks_host_fallback)
-            if filt != 'ricci':
+            if filt in STRUCT_DEVICE_FILTS and struct_backend == 'device':
+                out_f = struct_filtration_device(filt, node_ptr, edge_ptr, out_e, int(tot_n))
+            elif filt != 'ricci':
                 out_f = torch.from_numpy(structural_filtration(filt, node_ptr.cpu().numpy(), edge_ptr.cpu().numpy(), out_e.cpu().numpy(),
                                                                hks_time=hks_time)).to(out_f.device)
             return dict(node_ptr=node_ptr, edge_ptr=edge_ptr, ids=out_ids, f=out_f, edges=out_e, status=st, pair_of_node=pn, pair_of_edge=pe)
@@ -204,7 +231,9 @@ class Vicinities:
             out_f = hks_filtration_device(node_ptr, edge_ptr, out_e, hks_time, int(tot_n))
             return dict(node_ptr=node_ptr, edge_ptr=edge_ptr, ids=out_ids, f=out_f, edges=out_e, status=st, pair_of_node=pn, pair_of_edge=pe,
                         hks_host_fallback=hks_host_fallback)
-        if filt != 'ricci':
+        if filt in STRUCT_DEVICE_FILTS and struct_backend == 'device':
+            out_f = struct_filtration_device(filt, node_ptr, edge_ptr, out_e, int(tot_n))
+        elif filt != 'ricci':
             out_f = torch.from_numpy(structural_filtration(filt, node_ptr.cpu().numpy(), edge_ptr.cpu().numpy(), out_e.cpu().numpy(),
                                                            hks_time=hks_time)).to(out_f.device)
         return dict(node_ptr=node_ptr, edge_ptr=edge_ptr, ids=out_ids, f=out_f, edges=out_e, status=st, pair_of_node=pn, pair_of_edge=pe)
@@ -233,16 +262,17 @@ def _vicinities(g, ricci_curv):
 
 
 def compute_persistence_image(g, u, v, filt='hks', hks_time=0.1, hop=2, ricci_curv=None, mode='PI', num_models=5,
-                              max_loop_len=10, cycle_the=2, hks_backend='host'):
+                              max_loop_len=10, cycle_the=2, hks_backend='host', struct_backend='host'):
     """Reference signature (:105).  filt='hks' (:128-130), 'degree' (:131-133) or 'ricci'; mode 'filtration' -> (filtration_val
     list, edge_index LongTensor[2,m]) or (None, None); mode 'PI' -> the reference's 9-tuple (times are 0).
-    hks_backend (not in the reference): 'host' or 'device', see `Vicinities.batch`."""
+    hks_backend, struct_backend (not in the reference): 'host' or 'device', see `Vicinities.batch`."""
     import torch
     check_hks_backend(hks_backend)
+    check_struct_backend(struct_backend)
     if filt not in ('ricci', 'degree', 'hks'):
         print("Error: 'filt' should be 'hks', 'degree' or 'ricci'! ")          # :152-153
         sys.exit()
-    b = _vicinities(g, ricci_curv).batch([[u, v]], hop, filt=filt, hks_time=hks_time, hks_backend=hks_backend)
+    b = _vicinities(g, ricci_curv).batch([[u, v]], hop, filt=filt, hks_time=hks_time, hks_backend=hks_backend, struct_backend=struct_backend)
     if int(b["edge_ptr"][-1]) == 0:
         return None, None
     fv = b["f"].cpu().numpy()

@@ -9,7 +9,8 @@ device that is the pair (u, u) -- ball(u) & ball(u) -- with TLC_DESC_ROOT1 | TLC
 TLC_UNREACHABLE_100.  Node labels of a vicinity are positions in ASCENDING original id (the reference's
 `convert_node_labels_to_integers` order is arbitrary); edges are listed once, lower label first.
 filt='degree' / 'centrality' / 'clustering' (:124-135; the shipped training script's filtrations, train_Teacher_Model.py:158-159): the
-same vicinities from the device, f from `data_utils_LP.structural_filtration` (host side, networkx's arithmetic: bit-equal values);
+same vicinities from the device, f from `data_utils_LP.structural_filtration` (host side, networkx's arithmetic: bit-equal values), or with
+struct_backend='device' from `tlc_struct_batch` on the extracted tensors (the same bits);
 filt='hks' (:120-122): `hks_signature` with scipy's eigh, host side (values to rounding: the node order inside a vicinity differs), or with
 hks_backend='device' `tlc_hks_batch` on the extracted tensors.
 `call` is not reproduced.
@@ -27,14 +28,16 @@ KD_NC_FLAGS = _lib.INCLUDE_ROOTS | _lib.NORM_EPS | _lib.UNREACHABLE_100 | _lib.D
 class NodeVicinities(Vicinities):
     """Device-resident weighted graph for PDGNN's node-centred vicinities; build once, query many nodes."""
 
-    def batch(self, nodes, hop, node_cap=None, edge_cap=None, filt='ricci', hks_time=0.1, hks_backend='host'):
+    def batch(self, nodes, hop, node_cap=None, edge_cap=None, filt='ricci', hks_time=0.1, hks_backend='host', struct_backend='host'):
         """nodes: [B] original labels -> the dict of Vicinities.batch (one vicinity per node).  filt: 'ricci', or 'degree' /
-        'centrality' / 'clustering' / 'hks' (:120-135; `data_utils_LP.structural_filtration`); hks_backend as in `Vicinities.batch`."""
-        from .data_utils_LP import check_hks_backend
+        'centrality' / 'clustering' / 'hks' (:120-135; `data_utils_LP.structural_filtration`); hks_backend and struct_backend as in
+        `Vicinities.batch`."""
+        from .data_utils_LP import check_hks_backend, check_struct_backend
         check_hks_backend(hks_backend)
+        check_struct_backend(struct_backend)
         nodes = np.asarray(nodes, dtype=np.int64).reshape(-1)
         return super().batch(np.stack([nodes, nodes], 1), hop, node_cap=node_cap, edge_cap=edge_cap, flags=KD_NC_FLAGS, filt=filt, hks_time=hks_time,
-                             hks_backend=hks_backend)
+                             hks_backend=hks_backend, struct_backend=struct_backend)
 
 
 _CACHE = {}
@@ -66,17 +69,18 @@ def _vicinities(g, ricci_curv):
 
 
 def compute_persistence_image(g, u, filt='hks', hks_time=0.1, hop=2, ricci_curv=None, mode='PI', num_models=5, max_loop_len=10,
-                              cycle_the=2, hks_backend='host'):
+                              cycle_the=2, hks_backend='host', struct_backend='host'):
     """Reference signature (:95).  filt='hks' (the default), 'ricci', 'degree', 'centrality' or 'clustering' (the last two are what the shipped
     train_Teacher_Model.py:158-159 trains on); mode 'filtration' -> (filtration_val list, edge_index LongTensor[2,m]) or
     (None, None) for a ball without an edge (:103-104); mode 'PI' -> the reference's 9-tuple (:183; times are 0).
-    hks_backend (not in the reference): 'host' or 'device', see `data_utils_LP.Vicinities.batch`."""
-    from .data_utils_LP import STRUCTURAL_FILTS, check_hks_backend
+    hks_backend, struct_backend (not in the reference): 'host' or 'device', see `data_utils_LP.Vicinities.batch`."""
+    from .data_utils_LP import STRUCTURAL_FILTS, check_hks_backend, check_struct_backend
     check_hks_backend(hks_backend)
+    check_struct_backend(struct_backend)
     if filt != 'ricci' and filt not in STRUCTURAL_FILTS:
         print("Error: 'filt' should be 'hks', 'clustering',' centrality', 'degree' or 'ricci'! ")      # :154-155
         sys.exit()
-    b = _vicinities(g, ricci_curv).batch([u], hop, filt=filt, hks_time=hks_time, hks_backend=hks_backend)
+    b = _vicinities(g, ricci_curv).batch([u], hop, filt=filt, hks_time=hks_time, hks_backend=hks_backend, struct_backend=struct_backend)
     if int(b["edge_ptr"][-1]) == 0:
         return None, None
     fv = b["f"].cpu().numpy()

@@ -310,6 +310,46 @@ def hks_batch(node_ptr, edge_ptr, edges, times, normalise=True, total_nodes=None
     return out, status[:B]
 
 
+def struct_kinds(kinds):
+    """A name or a sequence of names of _lib.STRUCT_KINDS -> (bit mask, the names in output-row order: degree, centrality, clustering)."""
+    names = [kinds] if isinstance(kinds, str) else list(kinds)
+    if not names or any(k not in _lib.STRUCT_KINDS for k in names) or len(set(names)) != len(names):
+        raise ValueError("struct_batch: kinds should be one or more of %s, each once, not %r" % (tuple(_lib.STRUCT_KINDS), kinds))
+    return sum(_lib.STRUCT_KINDS[k] for k in names), [k for k in _lib.STRUCT_KINDS if k in names]
+
+
+@_lib.on_device_of
+def struct_batch(node_ptr, edge_ptr, edges, kinds, normalise=True, total_nodes=None):
+    """The degree / centrality / clustering node functions of a packed batch of simple graphs on the device (tlc_struct_batch; the
+    values of `data_utils_LP.structural_filtration`, bit for bit).
+
+    node_ptr / edge_ptr int64[B+1], edges int32[sum m, 2] local ids: CUDA tensors, the layout of `Vicinities.batch`.  kinds: a name or
+    a sequence of names out of 'degree', 'centrality', 'clustering'.  normalise: each graph's values / (max + 1e-10).  Returns
+    (f float64[K, sum n], status uint8[B]): the rows of f in the order degree, centrality, clustering of the kinds asked for (whatever
+    order they were named in); a graph whose status is ST_BAD_INPUT (offsets out of order or beyond the totals, an id outside
+    0 .. n-1, a self loop, an unordered pair listed twice in either orientation) has NaN in its slice.  No size cap, no host fallback.
+    total_nodes: sum n if the caller has it already (`Vicinities.batch` does); else node_ptr[-1] is read, the call's only host read."""
+    torch = _lib.require_gpu()
+    dev = node_ptr.device
+    mask, names = struct_kinds(kinds)
+    K, B = len(names), node_ptr.numel() - 1
+    tot_m = int(edges.shape[0])
+    tot_n = int(total_nodes) if total_nodes is not None else (int(node_ptr[-1]) if B > 0 else 0)
+    out = torch.full((K, tot_n), float("nan"), dtype=torch.float64, device=dev)
+    status = torch.zeros(max(B, 1), dtype=torch.uint8, device=dev)
+    if B > 0:
+        need = C.c_int64(0)
+        _lib.check(_lib.lib().tlc_struct_batch_work_bytes(C.c_int64(B), C.c_int64(tot_n), C.c_int64(tot_m), C.c_uint32(mask), C.byref(need)),
+                   "tlc_struct_batch_work_bytes")
+        work = torch.empty(need.value, dtype=torch.uint8, device=dev)
+        rc = _lib.lib().tlc_struct_batch(_lib.ptr(node_ptr.contiguous()), _lib.ptr(edge_ptr.contiguous()), _lib.ptr(edges.contiguous()),
+                                         C.c_int64(B), C.c_int64(tot_n), C.c_int64(tot_m), C.c_uint32(mask),
+                                         C.c_uint32(_lib.STRUCT_NORMALISE if normalise else 0), _lib.ptr(out), _lib.ptr(status), _lib.ptr(work),
+                                         C.c_int64(need.value), _lib.stream_ptr())
+        _lib.check(rc, "tlc_struct_batch")
+    return out, status[:B]
+
+
 @_lib.on_device_of
 def pd_from_filtration(node_offs, edge_offs, edges, f, flags=0, want_rank=True):
     """Batched perturb_filter_function + Union_find + Accelerate_PD (sg2dgm/accelerated_PD.py:6-178).
