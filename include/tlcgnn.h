@@ -689,6 +689,32 @@ int tlc_ollivier_ricci_sinkhorn(int32_t n_nodes, const int32_t* d_rowptr, const 
                                 double* d_kappa, int32_t* d_iters, void* d_work, int64_t work_bytes, int32_t max_support,
                                 int64_t max_product, void* stream);
 
+/* The same curvature with the EXACT transport distance: `OllivierRicci(G, alpha, method="OTD")` (POT's emd2), which the reference's
+ * node-classification pipeline uses for its curvature files (pipelines_GIN.py:79).  Integer throughout: with alpha = alpha_num /
+ * alpha_den and D = alpha_den * deg(s) * deg(t) the scaled masses are alpha_num * deg(s) * deg(t) at s and (alpha_den - alpha_num) *
+ * deg(t) on each neighbour of s (t likewise), the costs are the hop distances 0..3, W = the integer minimum cost of that
+ * transportation problem (primal-dual, level-synchronous searches; every loop bounded by the sizes), and kappa = 1.0 - (double)W /
+ * (double)D -- the only floating-point operations.  Bit-identical from run to run, independent of the batch, symmetric in (s, t).
+ * Not reproduced: the library's nbr_topk cut of neighbourhoods above 3 000, weighted graphs, directed graphs.
+ *   CSR and d_edges: as for tlc_ollivier_ricci_sinkhorn (symmetric, loop-free, columns ascending and unique, adjacent pairs only; a
+ *   self pair gets kappa 0, W 0, D 0).  d_kappa double[n_edges]; d_cost / d_denom int64[n_edges] (either may be NULL): W and D.
+ *   One wavefront solves an edge with (deg(s)+1)*(deg(t)+1) <= TLC_OTD_WAVE_PRODUCT, deg(s)+deg(t)+2 <= TLC_OTD_WAVE_SUPPORT and
+ *   D <= TLC_OTD_WAVE_DENOM in LDS; the others take one workgroup each and a slot of the workspace (2-bit codes when they do not
+ *   fit the LDS, and the flow cells: 4 bytes each, 8 when max_support >= 4 094).  max_support >= max over all edges of
+ *   deg(s)+deg(t)+2, at most TLC_OTD_MAX_SUPPORT; max_product >= max of (deg(s)+1)*(deg(t)+1) over the edges of the second kind (>= 1).
+ *   An edge beyond them, or one whose solve ran out of its bound, gets NaN and W = -1, never a silent value.
+ *   d_work: 16-byte aligned, >= 16 + 4*n_edges (rounded up to 16) + one slot; tlc_ollivier_ricci_otd_work_bytes() gives the size with
+ *   min(n_edges, 32) slots (more bytes = more hub edges in flight, up to 1 024).  Stream-ordered, no host synchronisation. */
+#define TLC_OTD_WAVE_PRODUCT   8192
+#define TLC_OTD_WAVE_SUPPORT   256
+#define TLC_OTD_WAVE_DENOM     65535
+#define TLC_OTD_MAX_SUPPORT    12794   /* 12 bytes of LDS per support entry + 64 within 150 KiB */
+#define TLC_OTD_LDS_BYTES      153600  /* of which the hub kernel's codes get what 12 * max_support (rounded up to 16) + 32 leave */
+int tlc_ollivier_ricci_otd_work_bytes(int64_t n_edges, int32_t max_support, int64_t max_product, int64_t* bytes);
+int tlc_ollivier_ricci_otd(int32_t n_nodes, const int32_t* d_rowptr, const int32_t* d_col, int64_t n_edges, const int32_t* d_edges,
+                           int32_t alpha_num, int32_t alpha_den, double* d_kappa, int64_t* d_cost, int64_t* d_denom, void* d_work,
+                           int64_t work_bytes, int32_t max_support, int64_t max_product, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

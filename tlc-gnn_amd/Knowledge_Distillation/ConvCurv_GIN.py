@@ -61,14 +61,21 @@ def _undirected_edges(edge_index):
 
 class Net(torch.nn.Module):
     def __init__(self, data, name, num_features, num_classes, hop=None, g=None, dimension=5, skip_cat=False, skip_sum=False,
-                 teacher=None, ricci_curv=None, w_mul=None, chunk=4096):
+                 teacher=None, ricci_curv=None, w_mul=None, chunk=4096, ricci_method="Sinkhorn"):
         """teacher: the trained Teacher_Model (frozen here) or its state dict -- required to compute w_mul (the reference loads it from
         a hard-coded path, :43-44; a random teacher would give meaningless images, so there is no default); ricci_curv: the
         reference's [[u, v, kappa], ...] list of g's edges (None: loaddatas.compute_ricci_curvature on the GPU); g: the graph as an
         edge array or networkx graph (None: the edges of data.edge_index).  w_mul: precomputed edge inputs [E, 2 dimension^2]
         (skips compute_NodeFeat / compute_PI; the teacher may then be left out: an untrained one only fills the state dict's
-        modelGIN entries)."""
+        modelGIN entries).  ricci_method: how that curvature is computed when ricci_curv is None -- "Sinkhorn" (the default) or
+        "OTD", the exact transport distance the reference's node-classification pipeline builds its curvature files with
+        (pipelines_GIN.py:79: `OllivierRicci(Gd, alpha=0.5, method="OTD")`); not reproduced: the library's nbr_topk cut of
+        neighbourhoods above 3 000, weighted graphs, directed graphs."""
         super(Net, self).__init__()
+        from ..loaddatas import RICCI_METHODS
+        if ricci_method not in RICCI_METHODS:
+            raise ValueError("ConvCurv_GIN.Net: ricci_method must be 'Sinkhorn' or 'OTD', got %r" % (ricci_method,))
+        self.ricci_method = ricci_method
         from .Teacher_model import Teacher_Model
         self.dimension = dimension
         hidden_dim = hidden_dim_of(name)
@@ -115,7 +122,7 @@ class Net(torch.nn.Module):
             else:
                 e = torch.from_numpy(np.asarray(g if not hasattr(g, "edges") else list(g.edges()), dtype=np.int64).reshape(-1, 2).T.copy())
             # (compute_ricci_curvature takes the node count from len(data.y))
-            ricci_curv = compute_ricci_curvature(Data(edge_index=e, y=torch.zeros(data.num_nodes, dtype=torch.long)))
+            ricci_curv = compute_ricci_curvature(Data(edge_index=e, y=torch.zeros(data.num_nodes, dtype=torch.long)), method=self.ricci_method)
         self._vic = NodeVicinities(g, ricci_curv)
 
     @torch.no_grad()
@@ -220,12 +227,12 @@ def num(strings):
         return float(strings)
 
 
-def call(data, name, num_features, num_classes, teacher=None, ricci_curv=None, g=None, w_mul=None):
+def call(data, name, num_features, num_classes, teacher=None, ricci_curv=None, g=None, w_mul=None, ricci_method="Sinkhorn"):
     """:193-208: remove_self_loops, then one self loop per node appended (add_self_loops); the model and the data on the device.
-    teacher (or w_mul) is required: see Net."""
+    teacher (or w_mul) is required, and ricci_method ("Sinkhorn" or "OTD") is handed on: see Net."""
     hop = hop_of(name)
     data.edge_index = _add_self_loops(_remove_self_loops(data.edge_index), data.x.size(0))
     device = torch.device('cuda' if torch.cuda.is_available() else 'cpu')
     data = data.to(device)
-    model = Net(data, name, num_features, num_classes, hop, g, teacher=teacher, ricci_curv=ricci_curv, w_mul=w_mul).to(device)
+    model = Net(data, name, num_features, num_classes, hop, g, teacher=teacher, ricci_curv=ricci_curv, w_mul=w_mul, ricci_method=ricci_method).to(device)
     return model, data

@@ -322,18 +322,23 @@ def load_ricci_file(filename):
     return ricci_list
 
 
-def compute_ricci_curvature(data, data_name, cache_dir='./data/curvature'):
+def compute_ricci_curvature(data, data_name, cache_dir='./data/curvature', method="Sinkhorn"):
     """data_utils_LP.py:202-242: Ollivier-Ricci curvature (alpha 0.5, Sinkhorn) of data.edge_index, cached as a text file of
     `u v kappa` lines.  The reference delegates to GraphRicciCurvature and writes under a hard-wired absolute path; here the
     curvature comes from the GPU (loaddatas.compute_ricci_curvature -> tlc_ollivier_ricci_sinkhorn) and the path is a
-    parameter (None disables the cache)."""
+    parameter (None disables the cache).  method="OTD": the exact transport distance instead (tlc_ollivier_ricci_otd, see
+    loaddatas.compute_ricci_curvature), cached under a name of its own (suffix `_otd`), so neither method is ever served the other's
+    file; not reproduced there: the library's nbr_topk cut, weighted graphs, directed graphs."""
     import os
-    from ..loaddatas import compute_ricci_curvature as _compute
-    filename = os.path.join(cache_dir, 'graph_' + data_name + '_removevaltest.edge_list') if cache_dir else None
+    from ..loaddatas import compute_ricci_curvature as _compute, RICCI_METHODS
+    if method not in RICCI_METHODS:
+        raise ValueError("compute_ricci_curvature: method must be 'Sinkhorn' or 'OTD', got %r" % (method,))
+    stem = 'graph_' + data_name + '_removevaltest' + ('_otd' if method == "OTD" else '')
+    filename = os.path.join(cache_dir, stem + '.edge_list') if cache_dir else None
     if filename and os.path.exists(filename):
         print("curvature file exists, directly loading")
         return load_ricci_file(filename)
-    ricci_list = _compute(data)
+    ricci_list = _compute(data, method=method)
     if filename:
         os.makedirs(os.path.dirname(filename), exist_ok=True)
         with open(filename, 'w') as f:

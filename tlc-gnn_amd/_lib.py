@@ -22,6 +22,7 @@ HKS_NMAX, HKS_LDS_NMAX, HKS_TMAX, HKS_NORMALISE = 256, 96, 8, 0x1   # TLC_HKS_* 
 STRUCT_DEGREE, STRUCT_CENTRALITY, STRUCT_CLUSTERING, STRUCT_NORMALISE = 0x1, 0x2, 0x4, 0x100      # TLC_STRUCT_* of include/tlcgnn.h
 STRUCT_WAVE_NMAX, STRUCT_LDS_SMALL_NMAX, STRUCT_LDS_NMAX, STRUCT_BITMAP_BITS = 64, 256, 1024, 65536
 STRUCT_KINDS = {"degree": STRUCT_DEGREE, "centrality": STRUCT_CENTRALITY, "clustering": STRUCT_CLUSTERING}   # in output-row order
+OTD_WAVE_PRODUCT, OTD_WAVE_SUPPORT, OTD_WAVE_DENOM, OTD_MAX_SUPPORT, OTD_LDS_BYTES = 8192, 256, 65535, 12794, 153600   # TLC_OTD_* of include/tlcgnn.h
 KEEP_ZERO_PERS, INCLUDE_ROOTS, NORM_EPS, PI_ORD0_EXT1, NO_EXT1, UNREACHABLE_100 = 0x1, 0x2, 0x4, 0x8, 0x10, 0x20
 DESC_MIN, DESC_MAX, DESC_ROOT1, NO_NORM = 0x40, 0x80, 0xC0, 0x100
 DESCRIPTOR_FLAG = {"sum": 0, "min": DESC_MIN, "max": DESC_MAX}      # the three node values of filtration.build_fv
@@ -38,6 +39,7 @@ SYMBOLS = [
     "tlc_complement_rows", "tlc_complement_pairs", "tlc_select_rows", "tlc_pack_vicinities", "tlc_stack_batch", "tlc_ollivier_ricci_sinkhorn",
     "tlc_near_pairs", "tlc_w2_partial_matching", "tlc_w2_inference_matching", "tlc_gat_layer_bwd", "tlc_edge_head_bwd", "tlc_pack_offsets", "tlc_vicinity_sizes", "tlc_debug_dc_stats", "tlc_debug_tier_counts", "tlc_debug_chunk_counters", "tlc_debug_phase_profile", "tlc_debug_set_option", "tlc_debug_pair_times",
     "tlc_hks_batch", "tlc_hks_batch_work_bytes", "tlc_struct_batch", "tlc_struct_batch_work_bytes",
+    "tlc_ollivier_ricci_otd", "tlc_ollivier_ricci_otd_work_bytes",
 ]
 
 
@@ -176,6 +178,9 @@ def lib():
                                     C.c_void_p, C.c_int64, C.c_void_p])
         L.tlc_struct_batch_work_bytes.argtypes = [C.c_int64, C.c_int64, C.c_int64, C.c_uint32, C.POINTER(C.c_int64)]
         L.tlc_struct_batch.argtypes = [C.c_void_p] * 3 + [C.c_int64] * 3 + [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+        L.tlc_ollivier_ricci_otd_work_bytes.argtypes = [C.c_int64, C.c_int32, C.c_int64, C.POINTER(C.c_int64)]
+        L.tlc_ollivier_ricci_otd.argtypes = ([C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 4
+                                             + [C.c_int64, C.c_int32, C.c_int64, C.c_void_p])
         L.tlc_debug_set_option.argtypes = [C.c_void_p, C.c_char_p, C.c_int]
         L.tlc_debug_dc_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.tlc_debug_tier_counts.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]

@@ -12,6 +12,7 @@
 // neighbour) or else exactly 3, and K has four distinct values: the cost matrix is a byte code per entry, staged in LDS (one
 // wavefront per edge; one 256-thread workgroup per hub edge, with an HBM slot for supports beyond the LDS).  u, v and the marginals live in LDS.  Integer/latency-bound graph work plus short fp64 mat-vecs: no MFMA.
 #include "tlc_common.h"
+#include "ricci_codes.h"
 
 namespace {
 
@@ -34,17 +35,6 @@ struct RicciParams {
     int max_support;             // LDS capacity of the workgroup kernel for u, v, a, b (entries of each)
 };
 
-template <int W>
-__device__ __forceinline__ void group_sync() {
-    if (W == 64) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-    } else {
-        __syncthreads();
-    }
-}
-
 // sum of one double per thread over the group; red: W doubles of LDS
 template <int W>
 __device__ __forceinline__ double group_sum(double v, double* red, int tid) {
@@ -62,9 +52,6 @@ __device__ __forceinline__ double group_sum(double v, double* red, int tid) {
     for (int w = 0; w < W / 64; ++w) s += red[w];
     return s;
 }
-
-// hop codes are packed sixteen to a 32-bit word (a 437 x 404 hub-hub edge: 44 KB instead of 176 KB -- LDS instead of HBM)
-__device__ __forceinline__ int code_at(const unsigned int* codes, int q) { return (int)((codes[q >> 4] >> ((q & 15) * 2)) & 3u); }
 
 // out-of-place mat-vec over the coded cost matrix with ALL threads of the group: s(r) = sum_c kval(code(r, c)) * x[c] for
 // r < rows.  A short side (a 172 x 5 hub edge has five columns) would leave most lanes idle with one thread per row, so every
@@ -103,75 +90,12 @@ template <int W>
 __device__ void ricci_edge(const RicciParams& p, long long e, unsigned int* codes, double* u, double* v, int* idx, double* red,
                            int tid) {
     const int s = p.edges[2 * e], t = p.edges[2 * e + 1];
-    const int sl = p.rowptr[s], tl = p.rowptr[t];
-    const int ds = p.rowptr[s + 1] - sl, dt = p.rowptr[t + 1] - tl;
+    const int ds = p.rowptr[s + 1] - p.rowptr[s], dt = p.rowptr[t + 1] - p.rowptr[t];
     const int na = ds + 1, nb = dt + 1;
-    // support a_i: the neighbours of s, then s itself (mass alpha); the target support likewise (its ids are staged in LDS below)
-    auto sup_a = [&](int i) { return i < ds ? p.col[sl + i] : s; };
     const double ma = ds > 0 ? (1.0 - p.alpha) / (double)ds : 0.0, mb = dt > 0 ? (1.0 - p.alpha) / (double)dt : 0.0;
     auto mass_a = [&](int i) { return i < ds ? ma : (ds > 0 ? p.alpha : 1.0); };
     auto mass_b = [&](int j) { return j < dt ? mb : (dt > 0 ? p.alpha : 1.0); };
-    // Hop codes.  One entry at a time (two dependent binary searches over global rows per entry) took 4.7 ms on a 172 x 172 hub
-    // edge; instead the rows around the source support are streamed once: the target support's ids sit in LDS (sorted), every
-    // entry starts at 3, and for every (a_i, y in row(a_i)) unit -- dealt to the threads through a prefix over deg(a_i) -- the
-    // row of y marks distance 2, y itself distance 1, a_i itself distance 0 (later passes overwrite earlier ones).
-    int* const bid = idx;                    // [nb - 1] neighbours of t, ascending
-    int* const off = idx + nb;               // [na + 1] prefix of deg(a_i)
-    for (int j = tid; j < dt; j += W) bid[j] = p.col[tl + j];
-    for (int i = tid; i < na; i += W) { const int a = sup_a(i); off[i + 1] = p.rowptr[a + 1] - p.rowptr[a]; }
-    for (int q = tid; q < (na * nb + 15) / 16; q += W) codes[q] = 0xffffffffu;         // every entry 3
-    group_sync<W>();
-    if (tid == 0) {
-        int run = 0;
-        off[0] = 0;
-        for (int i = 0; i < na; ++i) { run += off[i + 1]; off[i + 1] = run; }
-    }
-    group_sync<W>();
-    const int units = off[na];
-    auto pos_b = [&](int z) -> int {         // index of z in the target support, or -1
-        if (z == t) return dt;
-        int lo = 0, hi = dt;
-        while (lo < hi) {
-            const int mid = (lo + hi) >> 1;
-            const int c = bid[mid];
-            if (c == z) return mid;
-            if (c < z) lo = mid + 1; else hi = mid;
-        }
-        return -1;
-    };
-    auto unit_row = [&](int k) -> int {      // the i whose row holds unit k: last i with off[i] <= k
-        int lo = 0, hi = na;
-        while (hi - lo > 1) {
-            const int mid = (lo + hi) >> 1;
-            if (off[mid] <= k) lo = mid; else hi = mid;
-        }
-        return lo;
-    };
-    for (int k = tid; k < units; k += W) {
-        const int i = unit_row(k);
-        const int a = sup_a(i);
-        const int y = p.col[p.rowptr[a] + (k - off[i])];
-        const int yl = p.rowptr[y], yh = p.rowptr[y + 1];
-        for (int q = yl; q < yh; ++q) {
-            const int j = pos_b(p.col[q]);
-            if (j >= 0) { const int q2 = i * nb + j; atomicAnd(&codes[q2 >> 4], ~(1u << ((q2 & 15) * 2))); }        // 3 -> 2
-        }
-    }
-    group_sync<W>();
-    for (int k = tid; k < units; k += W) {
-        const int i = unit_row(k);
-        const int j = pos_b(p.col[p.rowptr[sup_a(i)] + (k - off[i])]);
-        if (j >= 0) {                                                                           // -> 1
-            const int q1 = i * nb + j;
-            atomicAnd(&codes[q1 >> 4], ~(3u << ((q1 & 15) * 2)));
-            atomicOr(&codes[q1 >> 4], 1u << ((q1 & 15) * 2));
-        }
-    }
-    group_sync<W>();
-    for (int i = tid; i < na; i += W) {
-        const int j = pos_b(sup_a(i));
-        if (j >= 0) { const int q0 = i * nb + j; atomicAnd(&codes[q0 >> 4], ~(3u << ((q0 & 15) * 2))); }            // -> 0
-    }
+    ricci_stage_codes<W>(p.rowptr, p.col, s, t, codes, idx, tid);            // ricci_codes.h
     for (int i = tid; i < na; i += W) u[i] = 1.0 / (double)na;
     for (int j = tid; j < nb; j += W) v[j] = 1.0 / (double)nb;
     const double kv0 = 1.0, kv1 = exp(-1.0 / p.reg), kv2 = exp(-2.0 / p.reg), kv3 = exp(-3.0 / p.reg);

@@ -583,3 +583,89 @@ def ollivier_ricci_sinkhorn(rowptr, col, edges, alpha=0.5, reg=0.1, max_iter=100
     if np.isnan(out).any():
         raise _lib.TlcError("tlc_ollivier_ricci_sinkhorn: an edge exceeded the workspace (max_support / max_product)")
     return (out, it) if want_iters else out
+
+
+def otd_lds_codes(max_support):
+    """How many 2-bit hop codes the workgroup kernel of tlc_ollivier_ricci_otd keeps in LDS for a batch with this max_support (a larger
+    support matrix has its codes in the workspace slot): what 12 bytes per support entry and the control block leave of TLC_OTD_LDS_BYTES."""
+    return 4 * max(0, _lib.OTD_LDS_BYTES - ((12 * int(max_support) + 15) // 16) * 16 - 32)
+
+
+def _otd_fraction(alpha):
+    from fractions import Fraction
+    try:
+        fr = Fraction(alpha).limit_denominator(1024)
+    except (TypeError, ValueError, OverflowError):
+        raise ValueError("ollivier_ricci_otd: alpha must be a number")
+    if fr != Fraction(alpha) or not 0 <= fr <= 1:
+        raise ValueError("ollivier_ricci_otd: alpha must be exactly p/q with 0 <= p <= q <= 1024 (the computation is integer); "
+                         "got %r" % (alpha,))
+    return fr.numerator, fr.denominator
+
+
+def ollivier_ricci_otd(rowptr, col, edges, alpha=0.5, device=None, want_cost=False, max_product=None):
+    """Ollivier-Ricci curvature of the given edges with the EXACT transport distance -- GraphRicciCurvature's
+    OllivierRicci(G, alpha, method="OTD") (POT's emd2) as pipelines_GIN.py:79 calls it (tlc_ollivier_ricci_otd).  Integer up to one
+    fp64 division: kappa = 1.0 - W / D with W the minimum cost of the transportation problem scaled by D = q * deg(s) * deg(t),
+    alpha = p / q.  Bit-identical from run to run, independent of the batch and of an edge's orientation.
+
+    rowptr/col: numpy CSR of the symmetric, loop-free, unit-weight graph (columns ascending); edges: int [E,2] adjacent pairs.
+    alpha: a float, Fraction or int that is exactly p/q with q <= 1024 (0.5, 0.25, Fraction(1, 3); 0.3 is not) -- ValueError otherwise.
+    Returns float64 numpy [E]; want_cost: (kappa, W int64 [E], D int64 [E]).  max_product (testing): workspace sized for hub edges
+    up to this many support pairs only; an edge beyond it comes back NaN with W = -1 instead of raising.
+    Not reproduced: the library's nbr_topk cut of neighbourhoods above 3 000, weighted graphs, directed graphs."""
+    num, den = _otd_fraction(alpha)
+    torch = _lib.require_gpu()
+    dev = torch.device("cuda", torch.cuda.current_device() if device is None else int(device))
+    rowptr = np.ascontiguousarray(rowptr, dtype=np.int32)
+    col = np.ascontiguousarray(col, dtype=np.int32)
+    edges = np.ascontiguousarray(edges, dtype=np.int32).reshape(-1, 2)
+    E, n = len(edges), len(rowptr) - 1
+    if E == 0:
+        return (np.zeros(0), np.zeros(0, dtype=np.int64), np.zeros(0, dtype=np.int64)) if want_cost else np.zeros(0)
+    deg = np.diff(rowptr).astype(np.int64)
+    ok = (edges >= 0).all(1) & (edges < n).all(1)
+    if not ok.all():
+        raise ValueError("ollivier_ricci_otd: edge endpoint out of range")
+    # the 0/1/2/3 hop-distance rule of the kernel holds for ADJACENT pairs only: every edge must be in the CSR (self pairs get 0)
+    keys = np.repeat(np.arange(n, dtype=np.int64), deg) * n + col.astype(np.int64)
+    want = edges[:, 0].astype(np.int64) * n + edges[:, 1].astype(np.int64)
+    loops = edges[:, 0] == edges[:, 1]
+    pos = np.searchsorted(keys, want)
+    found = (pos < len(keys)) & (keys[np.minimum(pos, max(len(keys) - 1, 0))] == want) if len(keys) else np.zeros(E, dtype=bool)
+    if not (found | loops).all():
+        raise ValueError("ollivier_ricci_otd: every pair must be an edge of the CSR (columns ascending)")
+    ds, dt = deg[edges[:, 0]], deg[edges[:, 1]]
+    na, nb = ds + 1, dt + 1
+    prod = na * nb
+    big = ((prod > _lib.OTD_WAVE_PRODUCT) | (na + nb > _lib.OTD_WAVE_SUPPORT) | (den * ds * dt > _lib.OTD_WAVE_DENOM)) & ~loops
+    max_support = int(max(2, (na + nb)[~loops].max())) if (~loops).any() else 2
+    if max_support > _lib.OTD_MAX_SUPPORT:
+        raise _lib.TlcError("ollivier_ricci_otd: an edge with deg(s) + deg(t) + 2 = %d > %d (the LDS of a workgroup)" % (max_support, _lib.OTD_MAX_SUPPORT))
+    strict = max_product is None
+    if strict:
+        max_product = int(prod[big].max()) if big.any() else 16
+    # tlc_ollivier_ricci_otd_work_bytes sizes for min(E, 32) hub edges in flight; here: one slot per hub edge, up to one per
+    # compute unit (256) and 1 GiB in all
+    need1 = C.c_int64(0)
+    _lib.check(_lib.lib().tlc_ollivier_ricci_otd_work_bytes(C.c_int64(1), C.c_int32(max_support), C.c_int64(int(max_product)), C.byref(need1)),
+               "tlc_ollivier_ricci_otd_work_bytes")
+    slot = need1.value - 32                                             # 16 (counter) + 16 (a list of one edge) + one slot
+    slots = max(1, min(int(big.sum()), 256, (1 << 30) // slot))
+    work_bytes = 16 + ((4 * E + 15) // 16) * 16 + slots * slot
+    with torch.cuda.device(dev):
+        d_rowptr, d_col = torch.from_numpy(rowptr).to(dev), torch.from_numpy(col).to(dev)
+        d_edges = torch.from_numpy(edges).to(dev)
+        kappa = torch.empty(E, dtype=torch.float64, device=dev)
+        cost = torch.empty(E, dtype=torch.int64, device=dev)
+        denom = torch.empty(E, dtype=torch.int64, device=dev)
+        work = torch.empty(work_bytes, dtype=torch.uint8, device=dev)
+        rc = _lib.lib().tlc_ollivier_ricci_otd(C.c_int32(n), _lib.ptr(d_rowptr), _lib.ptr(d_col), C.c_int64(E), _lib.ptr(d_edges),
+                                               C.c_int32(num), C.c_int32(den), _lib.ptr(kappa), _lib.ptr(cost), _lib.ptr(denom),
+                                               _lib.ptr(work), C.c_int64(work_bytes), C.c_int32(max_support), C.c_int64(int(max_product)),
+                                               _lib.stream_ptr())
+        _lib.check(rc, "tlc_ollivier_ricci_otd")
+        out, w, d = kappa.cpu().numpy(), cost.cpu().numpy(), denom.cpu().numpy()
+    if strict and np.isnan(out).any():
+        raise _lib.TlcError("tlc_ollivier_ricci_otd: an edge exceeded the workspace or the solver's bound (edge %d)" % int(np.flatnonzero(np.isnan(out))[0]))
+    return (out, w, d) if want_cost else out

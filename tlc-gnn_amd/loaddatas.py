@@ -5,8 +5,8 @@
 `compute_persistence_image` is the caller of the hot path: it fixes the order of the six
 pair lists, builds the graph FROM EDGES ONLY (isolated nodes are "missing"), takes weights kappa+1 and calls
 graph2pi(...).get_pimg_for_all_edges(hop, norm=True, extended_flag=True, resolution=5, descriptor='sum').
-Dataset download (`loaddatas`) and the Ollivier-Ricci solver are out of scope: curvature is an INPUT here
-(`data.ricci_list`, the reference's sorted [u, v, kappa] list).
+Dataset download (`loaddatas`) is out of scope; curvature is an INPUT here (`data.ricci_list`, the reference's sorted
+[u, v, kappa] list) or computed on the GPU by compute_ricci_curvature.
 """
 import os
 
@@ -160,12 +160,21 @@ def compute_persistence_image_streamed(data, train_edges, negatives, val_edges, 
     return assemble(pieces, len(total), 25), total
 
 
-def compute_ricci_curvature(data):
-    """loaddatas.py:105-123: Ollivier-Ricci curvature (alpha 0.5, Sinkhorn) of every edge of data.edge_index as the sorted list
+RICCI_METHODS = ("Sinkhorn", "OTD")
+
+
+def compute_ricci_curvature(data, method="Sinkhorn"):
+    """loaddatas.py:105-123: Ollivier-Ricci curvature (alpha 0.5) of every edge of data.edge_index as the sorted list
     [[u, v, kappa], [v, u, kappa], ...].  The reference delegates to the third-party GraphRicciCurvature (absent here); this
-    runs the same computation on the GPU (tlc_ollivier_ricci_sinkhorn; parity unpinned, see the checker's header in
-    tests/).  A caller-supplied `data.ricci_list` (the reference's format) takes precedence -- e.g. curvature computed
-    elsewhere, or the seeded stand-in of tlc_gnn_amd.synth.synthetic_curvature."""
+    runs the same computation on the GPU.  method="Sinkhorn" (the default, what loaddatas.py asks for): the entropic distance,
+    tlc_ollivier_ricci_sinkhorn (parity unpinned, see the checker's header in tests/).  method="OTD": the exact transport distance
+    (POT's emd2), what pipelines_GIN.py:79 computes the node-classification curvature files with -- tlc_ollivier_ricci_otd, integer
+    arithmetic up to one division, symmetric in the endpoints (no orientation step); not reproduced: the library's nbr_topk cut of
+    neighbourhoods above 3 000, weighted graphs, directed graphs.  Anything else: ValueError.  A caller-supplied
+    `data.ricci_list` (the reference's format) takes precedence -- e.g. curvature computed elsewhere, or the seeded stand-in of
+    tlc_gnn_amd.synth.synthetic_curvature."""
+    if method not in RICCI_METHODS:
+        raise ValueError("compute_ricci_curvature: method must be 'Sinkhorn' or 'OTD', got %r" % (method,))
     ricci = getattr(data, "ricci_list", None)
     if ricci is not None:
         return ricci
@@ -175,6 +184,13 @@ def compute_ricci_curvature(data):
     und = np.unique(np.sort(ei.T, axis=1), axis=0)
     n = int(max(len(data.y), und.max() + 1)) if len(und) else len(data.y)
     rowptr, col, _ = synth.edges_to_csr(n, und)
+    if method == "OTD":
+        kappa = engine.ollivier_ricci_otd(rowptr, col, und, alpha=0.5)
+        ricci_list = []
+        for (n1, n2), k in zip(und.tolist(), kappa.tolist()):
+            ricci_list.append([n1, n2, k])
+            ricci_list.append([n2, n1, k])
+        return sorted(ricci_list)
     # (source, target) as networkx's G.edges() yields it after add_edges_from(edge list): the endpoint that entered the graph
     # first is the source.  The Sinkhorn loop stops on the target marginal, so the orientation shows at the 1e-6 level.
     flat = ei.T.reshape(-1)
