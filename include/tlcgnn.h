@@ -434,6 +434,36 @@ int tlc_hks_batch(const int64_t* d_node_ptr, const int64_t* d_edge_ptr, const in
                   int64_t total_edges, const double* h_times, int32_t n_times, uint32_t flags, double* d_out, uint8_t* d_status,
                   void* d_work, int64_t work_bytes, void* stream);
 
+/* ---- Heat-kernel signatures of graphs above TLC_HKS_NMAX nodes ---------------------------------------------------------------------------
+ * The same values for SELECTED graphs of the packed batch of tlc_hks_batch, without eigenpairs: hks_t(v) = [exp(-t L)]_vv, and with
+ * M = D^-1/2 A D^-1/2, [exp(-t L)]_vv = exp(-t) [exp(t M)]_vv for a node of degree > 0 and 1 for a node of degree 0.  Per time:
+ * s = the least integer >= 0 with t / 2^s <= 1/2, X = (t / 2^s) M, the Taylor series of exp(X) to degree 14 by Horner (13 products),
+ * times exp(-t / 2^s), s - 1 squarings, and the row sums of squares of the last matrix (s = 0: its diagonal) -- dense symmetric fp64
+ * products on the matrix cores (v_mfma_f64_16x16x4_f64), 64 x 64 output tiles on and above the diagonal, mirrored on store.  No entry is
+ * negative, so nothing cancels; every K-sum runs in one fixed order, no split-K, no floating-point atomics: a graph's values are the same
+ * bits run to run, alone or in any selection, with any workspace.  Agreement with LAPACK's eigh route: <= 1e-11 absolute is tested up to
+ * n = TLC_HKS_LARGE_NMAX, t = TLC_HKS_LARGE_TIME_MAX.
+ * h_sel (HOST) int64[n_sel]: the indices of the graphs to compute, strictly ascending inside 0 .. n_graphs-1; h_sel_nodes (HOST)
+ * int64[n_sel]: their node counts as the caller knows them (slots and groups are sized from them; nothing is read back, no host wait).
+ * Only the slices of d_out f64[n_times, total_nodes] and the bytes of d_status u8[n_graphs] of selected graphs are written: TLC_ST_OK;
+ * TLC_ST_TOO_LARGE (a declared count above TLC_HKS_LARGE_NMAX); TLC_ST_BAD_INPUT (the contract of tlc_hks_batch on offsets and edges,
+ * or a declared count that is not node_ptr[g + 1] - node_ptr[g]: checked on the device before anything is indexed with it) -- the
+ * slice is then left untouched.  A selected graph may have any size from 0 on (small ones are merely wasteful); no nodes: TLC_ST_OK,
+ * nothing written.  n_times, flags (TLC_HKS_NORMALISE), row k of d_out bit-equal to a call with h_times[k] alone: as tlc_hks_batch.
+ * d_work: 16-byte aligned, any work_bytes >= *min_bytes (the largest selected graph alone: three np x np fp64 matrices, np = n rounded
+ * up to 64, and its lists); *all_bytes lets every selected graph run at once; in between the selection runs in groups that fit, in
+ * h_sel order.  tlc_hks_large_work_bytes is host arithmetic (no device needed); both are 0 for an empty selection.
+ * TLC_ERR_INVALID_ARG (nothing launched): null pointers, h_sel not ascending or out of range, a negative count, n_times outside
+ * 1 .. TLC_HKS_TMAX, an unknown flag, a time outside [0, TLC_HKS_LARGE_TIME_MAX] or not finite, work_bytes < *min_bytes, d_work misaligned.
+ * Runs on the caller's current device, asynchronous on `stream`. */
+#define TLC_HKS_LARGE_NMAX      4096   /* most nodes of a graph; above it TLC_ST_TOO_LARGE, slice untouched */
+#define TLC_HKS_LARGE_TIME_MAX  64.0   /* times outside [0, 64] or not finite: TLC_ERR_INVALID_ARG, nothing launched */
+int tlc_hks_large_work_bytes(const int64_t* h_sel_nodes, int64_t n_sel, int32_t n_times, int64_t* min_bytes, int64_t* all_bytes);
+int tlc_hks_large_batch(const int64_t* d_node_ptr, const int64_t* d_edge_ptr, const int32_t* d_edges, int64_t n_graphs,
+                        int64_t total_nodes, int64_t total_edges, const int64_t* h_sel, const int64_t* h_sel_nodes, int64_t n_sel,
+                        const double* h_times, int32_t n_times, uint32_t flags, double* d_out, uint8_t* d_status,
+                        void* d_work, int64_t work_bytes, void* stream);
+
 /* ---- Degree / centrality / clustering filtrations (Knowledge_Distillation/data_utils_LP.py:131-133; data_utils_NC.py:124-135: networkx's
  * degree(), degree_centrality and clustering of the vicinity, then / (max + 1e-10)) ------------------------------------------------------
  * For the packed batch of tlc_hks_batch (simple undirected graphs, each edge ONCE, local ids), per node v of a graph of n nodes with

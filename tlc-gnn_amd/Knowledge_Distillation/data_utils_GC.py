@@ -52,12 +52,15 @@ def hks_filtration(n, edges, hks_time):
     return v / (max(v) + 1e-10)
 
 
-def compute_persistence_image_batch(graphs, filt='degree', filtrations=None, hks_time=0.1, hks_backend='host', struct_backend='host'):
+def compute_persistence_image_batch(graphs, filt='degree', filtrations=None, hks_time=0.1, hks_backend='host', struct_backend='host',
+                                    hks_large='host'):
     """graphs: list of networkx-like graphs with nodes 0..n-1, or (n, edges[m,2]) tuples.
     Returns a list with the reference's 9-tuple per graph (:166), or (None, None) for graphs without an edge / not
     connected (:101-103).  filt: 'degree' or 'hks' (host side, :114-119); `filtrations` supplies f per graph for anything else.
     hks_backend='device': filt='hks' from `tlc_hks_batch`, one launch for the whole list (`data_utils_LP.hks_filtration_device`; graphs
     it does not take are counted in `data_utils_LP.hks_host_fallback`); it has no effect on the other filtrations.
+    hks_large='device': with filt='hks' and hks_backend='device', the graphs above _lib.HKS_NMAX nodes from `tlc_hks_large_batch` instead of
+    the host (`data_utils_LP.hks_filtration_device`; counted in `data_utils_LP.hks_large_device`); no effect otherwise.
     hks_backend='device' wants each undirected edge ONCE per graph and raises RuntimeError otherwise (an (n, edges) tuple with both
     directions, as PyG stores edge_index, or with a repeated pair; also self loops and ids outside 0 .. n-1); hks_backend='host' keeps
     scipy's multigraph semantics: repeated entries add up to edge weights (both directions give the simple graph's values).
@@ -66,9 +69,11 @@ def compute_persistence_image_batch(graphs, filt='degree', filtrations=None, hks
     backend's); the same contract on the edges as hks_backend='device'.  With the default 'host', 'centrality' and 'clustering' are not
     computed here (pass `filtrations`).  It has no effect on 'hks' or on `filtrations`."""
     import torch
-    from .data_utils_LP import STRUCT_DEVICE_FILTS, check_hks_backend, check_struct_backend, hks_filtration_device, struct_filtration_device
+    from .data_utils_LP import (STRUCT_DEVICE_FILTS, check_hks_backend, check_hks_large, check_struct_backend, hks_filtration_device,
+                                struct_filtration_device)
     check_hks_backend(hks_backend)
     check_struct_backend(struct_backend)
+    check_hks_large(hks_large)
     on_device = filtrations is None and filt in STRUCT_DEVICE_FILTS and struct_backend == 'device'
     if filt not in ('degree', 'hks') and filtrations is None and not on_device:
         raise NotImplementedError("data_utils_GC (HIP): filt='degree' and 'hks' are computed here; pass `filtrations` for anything else")
@@ -88,7 +93,7 @@ def compute_persistence_image_batch(graphs, filt='degree', filtrations=None, hks
     dev = "cuda"
     d_node_offs, d_edge_offs, d_edges = torch.from_numpy(node_offs).to(dev), torch.from_numpy(edge_offs).to(dev), torch.from_numpy(edges).to(dev)
     if filtrations is None and filt == 'hks' and hks_backend == 'device':
-        d_f = hks_filtration_device(d_node_offs, d_edge_offs, d_edges, hks_time, int(node_offs[-1]))
+        d_f = hks_filtration_device(d_node_offs, d_edge_offs, d_edges, hks_time, int(node_offs[-1]), hks_large=hks_large)
         f = d_f.cpu().numpy()
         fs = [f[node_offs[k]:node_offs[k + 1]] for k in range(len(keep))]
     elif on_device:
@@ -132,16 +137,18 @@ def compute_persistence_image_batch(graphs, filt='degree', filtrations=None, hks
 
 
 def compute_persistence_image(g, filt='hks', hks_time=0.1, hop=2, ricci_curv=None, mode='PI', num_models=5, max_loop_len=10,
-                              cycle_the=2, hks_backend='host', struct_backend='host'):
+                              cycle_the=2, hks_backend='host', struct_backend='host', hks_large='host'):
     """Reference signature (:98).  filt='hks' (the default) or 'degree' ('ricci' needs curvatures per graph: pass `filtrations`
     to compute_persistence_image_batch); mode 'PI' -> 9-tuple, 'filtration' -> (filtration_val, edge_index).
     hks_backend (not in the reference): 'host' or 'device', see compute_persistence_image_batch: 'device' wants each undirected edge
     once and raises RuntimeError for a tuple that repeats one; 'host' keeps scipy's multigraph semantics (repeats add up to weights).
-    struct_backend (not in the reference): 'host' or 'device': filt='degree' from `tlc_struct_batch` (the same bits, the same contract)."""
+    struct_backend (not in the reference): 'host' or 'device': filt='degree' from `tlc_struct_batch` (the same bits, the same contract).
+    hks_large (not in the reference): 'host' or 'device', see compute_persistence_image_batch."""
     import torch
-    from .data_utils_LP import check_hks_backend, check_struct_backend, hks_filtration_device, struct_filtration_device
+    from .data_utils_LP import check_hks_backend, check_hks_large, check_struct_backend, hks_filtration_device, struct_filtration_device
     check_hks_backend(hks_backend)
     check_struct_backend(struct_backend)
+    check_hks_large(hks_large)
     if filt not in ('degree', 'hks'):
         raise NotImplementedError("data_utils_GC (HIP): filt='hks' and 'degree' are implemented; for 'ricci' pass the values as "
                                   "`filtrations` to compute_persistence_image_batch")
@@ -151,14 +158,16 @@ def compute_persistence_image(g, filt='hks', hks_time=0.1, hop=2, ricci_curv=Non
     if mode == 'filtration':
         if filt == 'hks' and hks_backend == 'device':
             ptr = lambda k: torch.tensor([0, k], dtype=torch.int64, device="cuda")
-            f = hks_filtration_device(ptr(n), ptr(len(e)), torch.from_numpy(e.astype(np.int32)).cuda(), hks_time, n).cpu().numpy()
+            f = hks_filtration_device(ptr(n), ptr(len(e)), torch.from_numpy(e.astype(np.int32)).cuda(), hks_time, n,
+                                      hks_large=hks_large).cpu().numpy()
         elif filt == 'degree' and struct_backend == 'device':
             ptr = lambda k: torch.tensor([0, k], dtype=torch.int64, device="cuda")
             f = struct_filtration_device(filt, ptr(n), ptr(len(e)), torch.from_numpy(e.astype(np.int32)).cuda(), n).cpu().numpy()
         else:
             f = hks_filtration(n, e, hks_time) if filt == 'hks' else degree_filtration(n, e)
         return f.tolist(), torch.from_numpy(e.T.copy()).long()
-    return compute_persistence_image_batch([(n, e)], filt=filt, hks_time=hks_time, hks_backend=hks_backend, struct_backend=struct_backend)[0]
+    return compute_persistence_image_batch([(n, e)], filt=filt, hks_time=hks_time, hks_backend=hks_backend, struct_backend=struct_backend,
+                                           hks_large=hks_large)[0]
 
 
 def evaluate_batch(model, samples):

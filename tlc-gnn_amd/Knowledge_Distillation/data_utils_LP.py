@@ -8,7 +8,8 @@ part of the subgraph (:111), there is no connectivity assert (an unreachable roo
 normalisation divides by max + 1e-10 (:64).  Node labels of a vicinity are positions in ASCENDING original id (the reference's
 `convert_node_labels_to_integers` order is arbitrary); edges are listed once, lower label first.
 filt='degree' (:131-133) and 'hks' (:128-130, the signature's default): the same vicinities, f from `structural_filtration` (host side:
-networkx's arithmetic, scipy's eigh); hks_backend='device': 'hks' from `tlc_hks_batch` instead (a Jacobi eigensolver in HIP, values to rounding);
+networkx's arithmetic, scipy's eigh); hks_backend='device': 'hks' from `tlc_hks_batch` instead (a Jacobi eigensolver in HIP, values to rounding),
+and with hks_large='device' the vicinities above its 256-node cap from `tlc_hks_large_batch` (exp(-tL) by fp64 matrix products) instead of the host;
 struct_backend='device': 'degree' / 'centrality' / 'clustering' from `tlc_struct_batch` instead (integer counting in HIP, the same bits).  The CBGNN cycle helpers (:256-448, dead code in the reference) and `call` are not reproduced.
 """
 import sys
@@ -27,11 +28,21 @@ STRUCT_DEVICE_FILTS = ("degree", "centrality", "clustering")      # what struct_
 # graphs of the most recent hks_backend='device' computation (this module's, data_utils_NC's or data_utils_GC's) that the device did not
 # take -- more than _lib.HKS_NMAX nodes, or no convergence -- and that `hks_signature` computed on the host instead
 hks_host_fallback = 0
+# hks_large: who computes the graphs `tlc_hks_batch` leaves at TLC_ST_TOO_LARGE -- 'host' (`hks_signature`, the default) or 'device'
+# (`engine.hks_large_batch`, up to _lib.HKS_LARGE_NMAX nodes and hks_time inside [0, _lib.HKS_LARGE_TIME_MAX]; values to rounding)
+HKS_LARGE = ("host", "device")
+# graphs of the most recent hks_backend='device' computation that the large tier (hks_large='device') computed
+hks_large_device = 0
 
 
 def check_hks_backend(hks_backend):
     if hks_backend not in HKS_BACKENDS:
         raise ValueError("hks_backend should be one of %s, not %r" % (HKS_BACKENDS, hks_backend))
+
+
+def check_hks_large(hks_large):
+    if hks_large not in HKS_LARGE:
+        raise ValueError("hks_large should be one of %s, not %r" % (HKS_LARGE, hks_large))
 
 
 def check_struct_backend(struct_backend):
@@ -103,26 +114,47 @@ def structural_filtration(kind, node_ptr, edge_ptr, edges, hks_time=0.1):
     return raw / (mx[owner] + 1e-10) if N else raw
 
 
-def hks_filtration_device(node_ptr, edge_ptr, edges, hks_time, total_nodes):
+def hks_filtration_device(node_ptr, edge_ptr, edges, hks_time, total_nodes, hks_large='host'):
     """The 'hks' case of `structural_filtration` on the device: `engine.hks_batch` (tlc_hks_batch) on the CUDA tensors of a packed batch
     -> CUDA float64[sum n], normalised per graph.  Offsets and edges stay on the device.  Graphs the kernel does not take (status
     TLC_ST_TOO_LARGE: more than _lib.HKS_NMAX nodes; TLC_ST_NOT_CONVERGED) are computed by `hks_signature` on the host and scattered
     in -- one extra copy, only when there are any; their number is left in the module's `hks_host_fallback`.
+    hks_large='device' (and 0 <= hks_time <= _lib.HKS_LARGE_TIME_MAX): the TLC_ST_TOO_LARGE graphs of at most _lib.HKS_LARGE_NMAX nodes go
+    through `engine.hks_large_batch` (tlc_hks_large_batch) into the same tensor first -- their sizes come from the status and offsets
+    read-back; their number is left in the module's `hks_large_device` -- and only what is still not TLC_ST_OK afterwards takes the host.
     The device takes SIMPLE graphs, each undirected edge listed once: TLC_ST_BAD_INPUT (offsets out of order, an id outside 0 .. n-1, a
     self loop, an unordered pair listed twice -- in the same or in both directions) raises RuntimeError; nothing is returned for such a
     batch.  The host route differs there: scipy sums repeated entries into a weighted multigraph."""
-    global hks_host_fallback
+    global hks_host_fallback, hks_large_device
     import torch
-    f, st = engine.hks_batch(node_ptr, edge_ptr, edges, [hks_time], normalise=True, total_nodes=total_nodes)
-    f = f[0]
+    check_hks_large(hks_large)
+    f2, st = engine.hks_batch(node_ptr, edge_ptr, edges, [hks_time], normalise=True, total_nodes=total_nodes)
+    f = f2[0]
     rest = torch.nonzero(st != _lib.ST_OK).reshape(-1).cpu().numpy()
     hks_host_fallback = len(rest)
+    hks_large_device = 0
     if len(rest):
+        bad = ("hks_backend='device': a graph has offsets out of order, an edge id out of range, a self loop or a repeated "
+               "edge (the device wants each undirected edge once; hks_backend='host' sums repeated edges into weights)")
         st_h = st.cpu().numpy()
         if (st_h[rest] == _lib.ST_BAD_INPUT).any():
-            raise RuntimeError("hks_backend='device': a graph has offsets out of order, an edge id out of range, a self loop or a repeated "
-                               "edge (the device wants each undirected edge once; hks_backend='host' sums repeated edges into weights)")
-        nptr, eptr, e = node_ptr.cpu().numpy(), edge_ptr.cpu().numpy(), edges.cpu().numpy()
+            raise RuntimeError(bad)
+        nptr = node_ptr.cpu().numpy()
+        if hks_large == 'device' and 0.0 <= float(hks_time) <= _lib.HKS_LARGE_TIME_MAX:
+            sizes = nptr[rest + 1] - nptr[rest]
+            take = (st_h[rest] == _lib.ST_TOO_LARGE) & (sizes <= _lib.HKS_LARGE_NMAX)
+            if take.any():
+                engine.hks_large_batch(node_ptr, edge_ptr, edges, rest[take].tolist(), sizes[take].tolist(), [hks_time], normalise=True,
+                                       total_nodes=total_nodes, out=f2, status=st)
+                st_l = st.cpu().numpy()[rest[take]]
+                if (st_l == _lib.ST_BAD_INPUT).any():
+                    raise RuntimeError(bad)
+                hks_large_device = int((st_l == _lib.ST_OK).sum())
+                rest = np.concatenate([rest[~take], rest[take][st_l != _lib.ST_OK]])
+                rest.sort()
+                hks_host_fallback = len(rest)
+    if len(rest):
+        eptr, e = edge_ptr.cpu().numpy(), edges.cpu().numpy()
         idx, val = [], []
         for k in rest:
             a, b = int(nptr[k]), int(nptr[k + 1])
@@ -162,14 +194,17 @@ class Vicinities:
         for old, new in self.dict_node.items():
             self.inv[new] = old
 
-    def batch(self, pairs, hop, node_cap=None, edge_cap=None, flags=None, filt='ricci', hks_time=0.1, hks_backend='host', struct_backend='host'):
+    def batch(self, pairs, hop, node_cap=None, edge_cap=None, flags=None, filt='ricci', hks_time=0.1, hks_backend='host', struct_backend='host',
+              hks_large='host'):
         """pairs: [E,2] original labels -> dict of CUDA tensors: node_ptr int64[E+1], edge_ptr int64[E+1], ids int64 (original
         labels, ascending inside a vicinity), f float64, edges int32 [sum m, 2] (local ids, lower first), status uint8[E].
         Vicinities without an edge have empty slices (the reference returns (None, None) for them, :117-118).
         filt: 'ricci' (the weighted-distance filtration of the device kernels) or one of STRUCTURAL_FILTS (f replaced by
         `structural_filtration` of the extracted vicinities).
         hks_backend: 'host' (scipy's eigh per vicinity on copies of offsets and edges) or 'device' (`hks_filtration_device` on the tensors
-        the extraction produced; the dict then also has hks_host_fallback); it matters for filt='hks' only.
+        the extraction produced; the dict then also has hks_host_fallback and hks_large_device); it matters for filt='hks' only.
+        hks_large: 'host' or 'device', who computes the vicinities above _lib.HKS_NMAX nodes (`hks_filtration_device`); it matters for
+        filt='hks' with hks_backend='device' only.
         struct_backend: 'host' (`structural_filtration` on copies of offsets and edges) or 'device' (`struct_filtration_device` on the tensors
         the extraction produced: the same bits, no copy of offsets or edges); it matters for filt 'degree' / 'centrality' / 'clustering' only.
         node_cap / edge_cap: per-pair capacities of an intermediate layout (one extraction; raises if a vicinity is larger); neither
@@ -177,6 +212,7 @@ class Vicinities:
         import torch
         check_hks_backend(hks_backend)
         check_struct_backend(struct_backend)
+        check_hks_large(hks_large)
         dev_graph = self._g2p._device_graph()
         mapped = torch.from_numpy(self._g2p._map_pairs(pairs)).cuda()
         fl = KD_LP_FLAGS if flags is None else flags
@@ -206,9 +242,9 @@ class Vicinities:
             pe = torch.repeat_interleave(owner, counts_m, output_size=int(tot_m))
             out_ids, out_f, out_e = self._inv_dev[ids[:int(tot_n)].long()], f[:int(tot_n)], edges[:int(tot_m)]
             if filt == 'hks' and hks_backend == 'device':
-                out_f = hks_filtration_device(node_ptr, edge_ptr, out_e, hks_time, int(tot_n))
+                out_f = hks_filtration_device(node_ptr, edge_ptr, out_e, hks_time, int(tot_n), hks_large=hks_large)
                 return dict(node_ptr=node_ptr, edge_ptr=edge_ptr, ids=out_ids, f=out_f, edges=out_e, status=st, pair_of_node=pn, pair_of_edge=pe,
-                            hks_host_fallback=hks_host_fallback)
+                            hks_host_fallback=hks_host_fallback, hks_large_device=hks_large_device)
             if filt in STRUCT_DEVICE_FILTS and struct_backend == 'device':
                 out_f = struct_filtration_device(filt, node_ptr, edge_ptr, out_e, int(tot_n))
             elif filt != 'ricci':
@@ -228,9 +264,9 @@ class Vicinities:
         out_ids, out_f, out_e, pn, pe = engine.pack_vicinities(offs, ids, f, eoffs, edges, node_ptr, edge_ptr, int(tot_n), int(tot_m),
                                                                label=self._inv_dev)
         if filt == 'hks' and hks_backend == 'device':
-            out_f = hks_filtration_device(node_ptr, edge_ptr, out_e, hks_time, int(tot_n))
+            out_f = hks_filtration_device(node_ptr, edge_ptr, out_e, hks_time, int(tot_n), hks_large=hks_large)
             return dict(node_ptr=node_ptr, edge_ptr=edge_ptr, ids=out_ids, f=out_f, edges=out_e, status=st, pair_of_node=pn, pair_of_edge=pe,
-                        hks_host_fallback=hks_host_fallback)
+                        hks_host_fallback=hks_host_fallback, hks_large_device=hks_large_device)
         if filt in STRUCT_DEVICE_FILTS and struct_backend == 'device':
             out_f = struct_filtration_device(filt, node_ptr, edge_ptr, out_e, int(tot_n))
         elif filt != 'ricci':
@@ -262,17 +298,19 @@ def _vicinities(g, ricci_curv):
 
 
 def compute_persistence_image(g, u, v, filt='hks', hks_time=0.1, hop=2, ricci_curv=None, mode='PI', num_models=5,
-                              max_loop_len=10, cycle_the=2, hks_backend='host', struct_backend='host'):
+                              max_loop_len=10, cycle_the=2, hks_backend='host', struct_backend='host', hks_large='host'):
     """Reference signature (:105).  filt='hks' (:128-130), 'degree' (:131-133) or 'ricci'; mode 'filtration' -> (filtration_val
     list, edge_index LongTensor[2,m]) or (None, None); mode 'PI' -> the reference's 9-tuple (times are 0).
-    hks_backend, struct_backend (not in the reference): 'host' or 'device', see `Vicinities.batch`."""
+    hks_backend, struct_backend, hks_large (not in the reference): 'host' or 'device', see `Vicinities.batch`."""
     import torch
     check_hks_backend(hks_backend)
     check_struct_backend(struct_backend)
+    check_hks_large(hks_large)
     if filt not in ('ricci', 'degree', 'hks'):
         print("Error: 'filt' should be 'hks', 'degree' or 'ricci'! ")          # :152-153
         sys.exit()
-    b = _vicinities(g, ricci_curv).batch([[u, v]], hop, filt=filt, hks_time=hks_time, hks_backend=hks_backend, struct_backend=struct_backend)
+    b = _vicinities(g, ricci_curv).batch([[u, v]], hop, filt=filt, hks_time=hks_time, hks_backend=hks_backend, struct_backend=struct_backend,
+                                         hks_large=hks_large)
     if int(b["edge_ptr"][-1]) == 0:
         return None, None
     fv = b["f"].cpu().numpy()

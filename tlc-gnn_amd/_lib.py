@@ -19,6 +19,8 @@ ERRORS = {1: "TLC_ERR_INVALID_ARG", 2: "TLC_ERR_HIP", 3: "TLC_ERR_NO_DEVICE", 4:
 ST_OK, ST_MISSING_NODE, ST_DISCONNECTED, ST_ZERO_RANGE, ST_NO_TREE_EDGE, ST_TOO_LARGE = range(6)
 ST_NOT_CONVERGED, ST_BAD_INPUT = 6, 7                               # tlc_hks_batch (both), tlc_struct_batch (ST_BAD_INPUT)
 HKS_NMAX, HKS_LDS_NMAX, HKS_TMAX, HKS_NORMALISE = 256, 96, 8, 0x1   # TLC_HKS_* of include/tlcgnn.h
+HKS_LARGE_NMAX, HKS_LARGE_TIME_MAX = 4096, 64.0                     # TLC_HKS_LARGE_* of include/tlcgnn.h (tlc_hks_large_batch)
+HKS_LARGE_TILE, HKS_LARGE_KSTEP = 64, 16                            # HKSL_T, HKSL_KS of csrc/hks_large.hip: output-tile side, K-step
 STRUCT_DEGREE, STRUCT_CENTRALITY, STRUCT_CLUSTERING, STRUCT_NORMALISE = 0x1, 0x2, 0x4, 0x100      # TLC_STRUCT_* of include/tlcgnn.h
 STRUCT_WAVE_NMAX, STRUCT_LDS_SMALL_NMAX, STRUCT_LDS_NMAX, STRUCT_BITMAP_BITS = 64, 256, 1024, 65536
 STRUCT_KINDS = {"degree": STRUCT_DEGREE, "centrality": STRUCT_CENTRALITY, "clustering": STRUCT_CLUSTERING}   # in output-row order
@@ -38,7 +40,7 @@ SYMBOLS = [
     "tlc_lp_decode_fused", "tlc_lp_decode_fused_f32", "tlc_gat_layer_fwd", "tlc_gat_layer_tiled_fwd", "tlc_gat_tile_cut", "tlc_csr_by_target", "tlc_pdgnn_forward", "tlc_pdgnn_forward_work_bytes", "tlc_scatter_f32", "tlc_edge_head_fwd",
     "tlc_complement_rows", "tlc_complement_pairs", "tlc_select_rows", "tlc_pack_vicinities", "tlc_stack_batch", "tlc_ollivier_ricci_sinkhorn",
     "tlc_near_pairs", "tlc_w2_partial_matching", "tlc_w2_inference_matching", "tlc_gat_layer_bwd", "tlc_edge_head_bwd", "tlc_pack_offsets", "tlc_vicinity_sizes", "tlc_debug_dc_stats", "tlc_debug_tier_counts", "tlc_debug_chunk_counters", "tlc_debug_phase_profile", "tlc_debug_set_option", "tlc_debug_pair_times",
-    "tlc_hks_batch", "tlc_hks_batch_work_bytes", "tlc_struct_batch", "tlc_struct_batch_work_bytes",
+    "tlc_hks_batch", "tlc_hks_batch_work_bytes", "tlc_hks_large_batch", "tlc_hks_large_work_bytes", "tlc_struct_batch", "tlc_struct_batch_work_bytes",
     "tlc_ollivier_ricci_otd", "tlc_ollivier_ricci_otd_work_bytes",
 ]
 
@@ -176,6 +178,9 @@ def lib():
         L.tlc_hks_batch_work_bytes.argtypes = [C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.POINTER(C.c_int64)]
         L.tlc_hks_batch.argtypes = ([C.c_void_p] * 3 + [C.c_int64] * 3 + [C.POINTER(C.c_double), C.c_int32, C.c_uint32, C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_int64, C.c_void_p])
+        L.tlc_hks_large_work_bytes.argtypes = [C.POINTER(C.c_int64), C.c_int64, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+        L.tlc_hks_large_batch.argtypes = ([C.c_void_p] * 3 + [C.c_int64] * 3 + [C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int64,
+                                          C.POINTER(C.c_double), C.c_int32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p])
         L.tlc_struct_batch_work_bytes.argtypes = [C.c_int64, C.c_int64, C.c_int64, C.c_uint32, C.POINTER(C.c_int64)]
         L.tlc_struct_batch.argtypes = [C.c_void_p] * 3 + [C.c_int64] * 3 + [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
         L.tlc_ollivier_ricci_otd_work_bytes.argtypes = [C.c_int64, C.c_int32, C.c_int64, C.POINTER(C.c_int64)]

@@ -310,6 +310,63 @@ def hks_batch(node_ptr, edge_ptr, edges, times, normalise=True, total_nodes=None
     return out, status[:B]
 
 
+HKS_LARGE_WORK_CAP = 2 << 30      # hks_large_batch(work_bytes=None): the workspace it allocates at most (never below min_bytes)
+
+
+def hks_large_work_bytes(sel_nodes, n_times=1):
+    """(min_bytes, all_bytes) of tlc_hks_large_work_bytes for the node counts of a selection: host arithmetic, no device needed."""
+    nodes = [int(v) for v in sel_nodes]
+    lo, hi = C.c_int64(0), C.c_int64(0)
+    arr = (C.c_int64 * max(len(nodes), 1))(*nodes)
+    _lib.check(_lib.lib().tlc_hks_large_work_bytes(arr, C.c_int64(len(nodes)), C.c_int32(n_times), C.byref(lo), C.byref(hi)),
+               "tlc_hks_large_work_bytes")
+    return lo.value, hi.value
+
+
+@_lib.on_device_of
+def hks_large_batch(node_ptr, edge_ptr, edges, sel, sel_nodes, times, normalise=True, total_nodes=None, out=None, status=None, work_bytes=None):
+    """Heat-kernel signatures of SELECTED graphs of a packed batch on the device without eigenpairs (tlc_hks_large_batch: exp(-tL) by
+    scaling, a degree-14 Taylor series and squarings, fp64 products on the matrix cores) -- the tier for graphs above HKS_NMAX nodes,
+    up to HKS_LARGE_NMAX; times inside [0, HKS_LARGE_TIME_MAX].
+
+    node_ptr / edge_ptr / edges, times, normalise, total_nodes: as `hks_batch`.  sel: the indices of the graphs to compute, strictly
+    ascending; sel_nodes: their node counts (HOST sequences: the library sizes its workspace from them without a read-back; a count
+    that is not the device's is ST_BAD_INPUT, one above HKS_LARGE_NMAX ST_TOO_LARGE).  out float64[T, sum n] / status uint8[B]: written
+    for the selected graphs only (given: e.g. what `hks_batch` returned; not given: NaN-filled / zero-filled).  work_bytes: the
+    workspace to allocate, at least min_bytes of `hks_large_work_bytes` (the selection then runs in groups that fit, same bits);
+    None: all_bytes, bounded by HKS_LARGE_WORK_CAP.  Returns (out, status)."""
+    torch = _lib.require_gpu()
+    dev = node_ptr.device
+    times = [float(t) for t in (times if hasattr(times, "__len__") else [times])]
+    T, B = len(times), node_ptr.numel() - 1
+    if not 1 <= T <= _lib.HKS_TMAX:
+        raise ValueError("hks_large_batch: 1 .. %d times per call" % _lib.HKS_TMAX)
+    sel, sel_nodes = [int(v) for v in sel], [int(v) for v in sel_nodes]
+    if len(sel) != len(sel_nodes):
+        raise ValueError("hks_large_batch: sel and sel_nodes differ in length")
+    tot_m = int(edges.shape[0])
+    tot_n = int(total_nodes) if total_nodes is not None else (int(node_ptr[-1]) if B > 0 else 0)
+    if out is None:
+        out = torch.full((T, tot_n), float("nan"), dtype=torch.float64, device=dev)
+    if status is None:
+        status = torch.zeros(max(B, 1), dtype=torch.uint8, device=dev)[:B]
+    if tuple(out.shape) != (T, tot_n) or out.dtype != torch.float64 or not out.is_contiguous() or status.numel() != B or status.dtype != torch.uint8 \
+            or not status.is_contiguous():
+        raise ValueError("hks_large_batch: out should be contiguous float64[%d, %d] and status contiguous uint8[%d]" % (T, tot_n, B))
+    S = len(sel)
+    if S > 0:
+        lo, hi = hks_large_work_bytes(sel_nodes, T)
+        need = max(lo, min(hi, HKS_LARGE_WORK_CAP)) if work_bytes is None else int(work_bytes)
+        work = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+        rc = _lib.lib().tlc_hks_large_batch(_lib.ptr(node_ptr.contiguous()), _lib.ptr(edge_ptr.contiguous()), _lib.ptr(edges.contiguous()),
+                                            C.c_int64(B), C.c_int64(tot_n), C.c_int64(tot_m), (C.c_int64 * S)(*sel), (C.c_int64 * S)(*sel_nodes),
+                                            C.c_int64(S), (C.c_double * T)(*times), C.c_int32(T),
+                                            C.c_uint32(_lib.HKS_NORMALISE if normalise else 0), _lib.ptr(out), _lib.ptr(status), _lib.ptr(work),
+                                            C.c_int64(need), _lib.stream_ptr())
+        _lib.check(rc, "tlc_hks_large_batch")
+    return out, status
+
+
 def struct_kinds(kinds):
     """A name or a sequence of names of _lib.STRUCT_KINDS -> (bit mask, the names in output-row order: degree, centrality, clustering)."""
     names = [kinds] if isinstance(kinds, str) else list(kinds)
