@@ -228,6 +228,43 @@ int tlc_pd_from_filtration(int32_t n_graphs, const int64_t* d_node_offs, const i
                            double* d_pd_up, double* d_pd_down, double* d_pd_one, double* d_ext0,
                            int32_t* d_counts, int32_t* d_edge_rank, void* stream);
 
+/* ---- the same diagrams for a few BIG graphs, on the whole device (csrc/pd_wide.hip) --------------------------
+ * The packed layout, TLC_KEEP_ZERO_PERS / TLC_NO_EXT1 and the output slots of tlc_pd_from_filtration; 32-bit ids, no node cap.
+ * h_sel int64[n_sel] (HOST): the graphs to compute, in any order; they run one after the other on the stream.  The rows and slots
+ * of every other graph are not touched.  d_work: the caller's, at least tlc_pd_wide_work_bytes of the largest selected graph
+ * (host arithmetic, no device needed; 0 for an empty selection); a smaller one is TLC_ERR_INVALID_ARG and the message names the
+ * bytes needed.  The call reads the selected graphs' offsets back once before it launches anything.
+ * Size limit: n >= 0 nodes, m >= 0 edges, n + m <= TLC_PD_WIDE_MAX_ITEMS = 2^27 -- the level loop numbers the copies of up to
+ * 4 m + 4 supernodes in a doubled id space with 32-bit ints, and the sort's positions and payloads are 32-bit.  Beyond it:
+ * TLC_ERR_UNSUPPORTED, nothing launched.  Filtration values of nodes that have an edge lie inside [-1, 101], the domain of the
+ * reference's key perturbation: there every node enters the filtration before its edges, and the edges are sorted without the nodes.
+ * Per-graph refusal (the convention of tlc_struct_batch): offsets out of order or negative, an id outside 0 .. n-1, a self loop, or
+ * an edge with an end whose value is outside [-1, 101] or not a number (the reference's merged order is not computed there)
+ * make that graph's d_counts row TLC_PD_WIDE_BAD_INPUT_ROW in all four entries (TLC_ST_BAD_INPUT; its slots are left untouched, no
+ * other graph is affected).
+ * Among equal descending keys the edge with the higher ascending rank comes first (the contract of fix_desc_ties, for runs of any
+ * length): this may make another one of several equal edges Pos than the reference's stable sort does; the diagrams are the same
+ * multisets.  d_edge_rank (may be NULL) holds the positions in THIS order: a valid permutation, under ties not the reference's.
+ * Points are written by prefix-sum compaction: two runs give the same bits.
+ * TLC_PD_WIDE_FORCE_FALLBACK (debug; tlc_pd_from_filtration refuses it): skip the divide and conquer and take the exact serial
+ * cycle swap that otherwise runs only when the end checks fail.  The fallback walks the Pos edges in this tier's order and compares
+ * fp64 ascending keys, first maximum of the loop, as the reference does.
+ * h_stats int64[TLC_PD_WIDE_N_STATS] (HOST, may be NULL; costs one synchronisation), for the last selected graph: divide-and-conquer
+ * levels, Boruvka rounds in total, kernel launches, 1 if the fallback ran, the graph's TLC_ST_* status. */
+#define TLC_PD_WIDE_MAX_ITEMS       (1ll << 27)
+#define TLC_PD_WIDE_FORCE_FALLBACK  0x40000000u
+#define TLC_PD_WIDE_BAD_INPUT_ROW   (-2)
+#define TLC_PD_WIDE_N_STATS         5
+#define TLC_PD_WIDE_BLOCK           256    /* threads per workgroup of the grid-stride kernels */
+#define TLC_PD_WIDE_SORT_TILE       4096   /* edges per workgroup of a radix pass */
+#define TLC_PD_WIDE_SCAN_CHUNK      2048   /* flags per workgroup of a prefix sum */
+#define TLC_PD_WIDE_LDS_NODES       40000  /* up to this many nodes the union-find array of an elder-rule pass lives in LDS */
+int tlc_pd_wide_work_bytes(const int64_t* h_sel_nodes, const int64_t* h_sel_edges, int64_t n_sel, int64_t* bytes);
+int tlc_pd_wide(int64_t n_graphs, const int64_t* d_node_offs, const int64_t* d_edge_offs, const int32_t* d_edges,
+                const double* d_f, uint32_t flags, const int64_t* h_sel, int64_t n_sel,
+                double* d_pd_up, double* d_pd_down, double* d_pd_one, double* d_ext0, int32_t* d_counts,
+                int32_t* d_edge_rank, void* d_work, int64_t work_bytes, int64_t* h_stats, void* stream);
+
 /* ---- P9: PersistenceImager(resolution=res).transform (sg2dgm/PersistenceImager.pyx:352-388) -------
  * isotropic sigma=1 Gaussian, ranges [0,1]^2, linear-ramp weight (:9-30), birth-death input (skew=True).
  *   d_offs int64[n_dgms+1];  d_pts float64[sum k, 2];  d_out float64[n_dgms, res*res] */

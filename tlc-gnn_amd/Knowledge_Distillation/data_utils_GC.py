@@ -53,7 +53,7 @@ def hks_filtration(n, edges, hks_time):
 
 
 def compute_persistence_image_batch(graphs, filt='degree', filtrations=None, hks_time=0.1, hks_backend='host', struct_backend='host',
-                                    hks_large='host'):
+                                    hks_large='host', pd_large='host'):
     """graphs: list of networkx-like graphs with nodes 0..n-1, or (n, edges[m,2]) tuples.
     Returns a list with the reference's 9-tuple per graph (:166), or (None, None) for graphs without an edge / not
     connected (:101-103).  filt: 'degree' or 'hks' (host side, :114-119); `filtrations` supplies f per graph for anything else.
@@ -67,13 +67,17 @@ def compute_persistence_image_batch(graphs, filt='degree', filtrations=None, hks
     struct_backend='device': filt 'degree', 'centrality' and 'clustering' from `tlc_struct_batch`, one launch for the whole list
     (`data_utils_LP.struct_filtration_device`: the values of `data_utils_LP.structural_filtration`, bit for bit; 'degree' equals the host
     backend's); the same contract on the edges as hks_backend='device'.  With the default 'host', 'centrality' and 'clustering' are not
-    computed here (pass `filtrations`).  It has no effect on 'hks' or on `filtrations`."""
+    computed here (pass `filtrations`).  It has no effect on 'hks' or on `filtrations`.
+    pd_large='device': the diagrams of graphs above _lib.PD_L_NMAX nodes or _lib.PD_L_MMAX edges from `tlc_pd_wide` (the whole device, no
+    node cap) instead of one workgroup of `tlc_pd_from_filtration`, which does not compute a graph above 65 535 nodes at all
+    (`engine.pd_from_filtration`); the same diagrams as multisets, images within the summation order."""
     import torch
     from .data_utils_LP import (STRUCT_DEVICE_FILTS, check_hks_backend, check_hks_large, check_struct_backend, hks_filtration_device,
                                 struct_filtration_device)
     check_hks_backend(hks_backend)
     check_struct_backend(struct_backend)
     check_hks_large(hks_large)
+    engine.check_pd_large(pd_large)
     on_device = filtrations is None and filt in STRUCT_DEVICE_FILTS and struct_backend == 'device'
     if filt not in ('degree', 'hks') and filtrations is None and not on_device:
         raise NotImplementedError("data_utils_GC (HIP): filt='degree' and 'hks' are computed here; pass `filtrations` for anything else")
@@ -104,7 +108,7 @@ def compute_persistence_image_batch(graphs, filt='degree', filtrations=None, hks
         fs = [np.asarray(filtrations[gi], dtype=np.float64) if filtrations is not None else
               (hks_filtration(parsed[gi][0], parsed[gi][1], hks_time) if filt == 'hks' else degree_filtration(*parsed[gi])) for gi in keep]
         d_f = torch.from_numpy(np.concatenate(fs)).to(dev)
-    r = engine.pd_from_filtration(d_node_offs, d_edge_offs, d_edges, d_f, _lib.KEEP_ZERO_PERS, want_rank=False)
+    r = engine.pd_from_filtration(d_node_offs, d_edge_offs, d_edges, d_f, _lib.KEEP_ZERO_PERS, want_rank=False, pd_large=pd_large)
     counts = r["counts"].cpu().numpy()
     up, one = r["up"], r["one"]
     # gather the ragged diagrams: Ord0 of graph k = up[node_offs[k] : +counts[k,0]], Ext1 = one[edge_offs[k] : +counts[k,2]]
@@ -137,18 +141,19 @@ def compute_persistence_image_batch(graphs, filt='degree', filtrations=None, hks
 
 
 def compute_persistence_image(g, filt='hks', hks_time=0.1, hop=2, ricci_curv=None, mode='PI', num_models=5, max_loop_len=10,
-                              cycle_the=2, hks_backend='host', struct_backend='host', hks_large='host'):
+                              cycle_the=2, hks_backend='host', struct_backend='host', hks_large='host', pd_large='host'):
     """Reference signature (:98).  filt='hks' (the default) or 'degree' ('ricci' needs curvatures per graph: pass `filtrations`
     to compute_persistence_image_batch); mode 'PI' -> 9-tuple, 'filtration' -> (filtration_val, edge_index).
     hks_backend (not in the reference): 'host' or 'device', see compute_persistence_image_batch: 'device' wants each undirected edge
     once and raises RuntimeError for a tuple that repeats one; 'host' keeps scipy's multigraph semantics (repeats add up to weights).
     struct_backend (not in the reference): 'host' or 'device': filt='degree' from `tlc_struct_batch` (the same bits, the same contract).
-    hks_large (not in the reference): 'host' or 'device', see compute_persistence_image_batch."""
+    hks_large, pd_large (not in the reference): 'host' or 'device', see compute_persistence_image_batch."""
     import torch
     from .data_utils_LP import check_hks_backend, check_hks_large, check_struct_backend, hks_filtration_device, struct_filtration_device
     check_hks_backend(hks_backend)
     check_struct_backend(struct_backend)
     check_hks_large(hks_large)
+    engine.check_pd_large(pd_large)
     if filt not in ('degree', 'hks'):
         raise NotImplementedError("data_utils_GC (HIP): filt='hks' and 'degree' are implemented; for 'ricci' pass the values as "
                                   "`filtrations` to compute_persistence_image_batch")
@@ -167,7 +172,55 @@ def compute_persistence_image(g, filt='hks', hks_time=0.1, hop=2, ricci_curv=Non
             f = hks_filtration(n, e, hks_time) if filt == 'hks' else degree_filtration(n, e)
         return f.tolist(), torch.from_numpy(e.T.copy()).long()
     return compute_persistence_image_batch([(n, e)], filt=filt, hks_time=hks_time, hks_backend=hks_backend, struct_backend=struct_backend,
-                                           hks_large=hks_large)[0]
+                                           hks_large=hks_large, pd_large=pd_large)[0]
+
+
+def largest_component(n, edges):
+    """:246-248  the largest connected component (the first one among equals), relabelled 0 .. k-1 in the order of the old ids
+    (nx.convert_node_labels_to_integers of the subgraph); self loops dropped (:240), each undirected edge once (nx.Graph)."""
+    import scipy.sparse as sp
+    from scipy.sparse.csgraph import connected_components
+    e = np.asarray(edges, dtype=np.int64).reshape(-1, 2)
+    e = np.unique(np.sort(e[e[:, 0] != e[:, 1]], 1), axis=0)
+    a = sp.coo_matrix((np.ones(len(e), dtype=np.int8), (e[:, 0], e[:, 1])), shape=(n, n))
+    _, lab = connected_components(a, directed=False)
+    keep = lab == np.bincount(lab, minlength=1).argmax()
+    new = np.cumsum(keep) - 1
+    e = e[keep[e[:, 0]]]
+    return int(keep.sum()), new[e]
+
+
+def call(dataset, name, filt='degree', hks_time=10, mode='PI', num_models=5, gn=0, save_dir=None, store=None, hks_backend='host',
+         struct_backend='host', hks_large='host', pd_large='host'):
+    """Reference signature (:228) plus keywords.  For the first `gn` graphs of `dataset` (PyG-like items with num_nodes and edge_index
+    [2, m], or (n, edges[m, 2]) tuples): the largest connected component, relabelled (:246-248), through `compute_persistence_image`.
+    Returns (total_time_PD, total_time_PI) like the reference (the times are 0 here).  The per-graph results go into the dict `store`
+    if one is given, and are pickled to <save_dir>/<name>_<filt>_total_test.pkl if save_dir is given (the reference writes to a fixed
+    path of its authors' machine, :264-266; here nothing is written by default).  The reference runs this on Cora, Citeseer, PubMed and
+    SBM graphs (:324-325): with pd_large='device' such a component's diagrams come from `tlc_pd_wide`, not from one workgroup."""
+    import os
+    import pickle
+    engine.check_pd_large(pd_large)
+    dict_store = {} if store is None else store
+    total_time_PD = total_time_PI = 0
+    for tt in range(gn):
+        data = dataset[tt]
+        if hasattr(data, "edge_index"):
+            n, e = int(data.num_nodes), np.asarray(data.edge_index.cpu()).T
+        else:
+            n, e = _edges_nodes(data)
+        k, ce = largest_component(n, e)
+        print("nodes: {}, edges: {}".format(k, len(ce)))
+        dict_store[tt] = compute_persistence_image((k, ce), filt=filt, hks_time=hks_time, hop=2, ricci_curv=None, mode=mode,
+                                                   num_models=num_models, hks_backend=hks_backend, struct_backend=struct_backend,
+                                                   hks_large=hks_large, pd_large=pd_large)
+        if len(dict_store[tt]) > 2:
+            total_time_PD += dict_store[tt][-2]
+            total_time_PI += dict_store[tt][-1]
+    if save_dir is not None:
+        with open(os.path.join(save_dir, name + '_' + filt + '_total_test.pkl'), 'wb') as f:
+            pickle.dump(dict_store, f, pickle.HIGHEST_PROTOCOL)
+    return total_time_PD, total_time_PI
 
 
 def evaluate_batch(model, samples):

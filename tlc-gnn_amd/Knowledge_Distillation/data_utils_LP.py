@@ -298,14 +298,16 @@ def _vicinities(g, ricci_curv):
 
 
 def compute_persistence_image(g, u, v, filt='hks', hks_time=0.1, hop=2, ricci_curv=None, mode='PI', num_models=5,
-                              max_loop_len=10, cycle_the=2, hks_backend='host', struct_backend='host', hks_large='host'):
+                              max_loop_len=10, cycle_the=2, hks_backend='host', struct_backend='host', hks_large='host', pd_large='host'):
     """Reference signature (:105).  filt='hks' (:128-130), 'degree' (:131-133) or 'ricci'; mode 'filtration' -> (filtration_val
     list, edge_index LongTensor[2,m]) or (None, None); mode 'PI' -> the reference's 9-tuple (times are 0).
-    hks_backend, struct_backend, hks_large (not in the reference): 'host' or 'device', see `Vicinities.batch`."""
+    hks_backend, struct_backend, hks_large (not in the reference): 'host' or 'device', see `Vicinities.batch`.
+    pd_large (not in the reference): 'host' or 'device': a vicinity of the HUGE class through `tlc_pd_wide` (`engine.pd_from_filtration`)."""
     import torch
     check_hks_backend(hks_backend)
     check_struct_backend(struct_backend)
     check_hks_large(hks_large)
+    engine.check_pd_large(pd_large)
     if filt not in ('ricci', 'degree', 'hks'):
         print("Error: 'filt' should be 'hks', 'degree' or 'ricci'! ")          # :152-153
         sys.exit()
@@ -319,18 +321,18 @@ def compute_persistence_image(g, u, v, filt='hks', hks_time=0.1, hop=2, ricci_cu
         return fv.tolist(), edge_index
     if mode != 'PI':
         raise ValueError("mode must be 'PI' or 'filtration'")
-    return diagrams_and_images(b, fv, edge_index)
+    return diagrams_and_images(b, fv, edge_index, pd_large=pd_large)
 
 
-def diagrams_and_images(b, fv, edge_index):
+def diagrams_and_images(b, fv, edge_index, pd_large='host'):
     """mode 'PI' tail shared by the edge- and node-centred vicinities (data_utils_LP.py:178-197, data_utils_NC.py:155-183):
     original_extended_persistence (Knowledge_Distillation fork: zero-persistence pairs kept) -> Ord0, Ext1, then the three
-    images PI(Ord0 ++ Ext1), PI0, PI1; the reference's 9-tuple (times are 0)."""
+    images PI(Ord0 ++ Ext1), PI0, PI1; the reference's 9-tuple (times are 0).  pd_large: see `engine.pd_from_filtration`."""
     import torch
     n, m = len(fv), edge_index.shape[1]
     r = engine.pd_from_filtration(torch.tensor([0, n], dtype=torch.int64, device="cuda"),
                                   torch.tensor([0, m], dtype=torch.int64, device="cuda"),
-                                  b["edges"].contiguous(), b["f"].contiguous(), _lib.KEEP_ZERO_PERS)
+                                  b["edges"].contiguous(), b["f"].contiguous(), _lib.KEEP_ZERO_PERS, pd_large=pd_large)
     c = r["counts"][0].cpu().numpy()
     if c[3] != 1 and int(c[2]) != m - n + int(c[3]):
         # not connected, and a Pos edge lies outside the component of the tree's root: Parent[...] of the reference's walk has no

@@ -27,6 +27,11 @@ STRUCT_KINDS = {"degree": STRUCT_DEGREE, "centrality": STRUCT_CENTRALITY, "clust
 OTD_WAVE_PRODUCT, OTD_WAVE_SUPPORT, OTD_WAVE_DENOM, OTD_MAX_SUPPORT, OTD_LDS_BYTES = 8192, 256, 65535, 12794, 153600   # TLC_OTD_* of include/tlcgnn.h
 KEEP_ZERO_PERS, INCLUDE_ROOTS, NORM_EPS, PI_ORD0_EXT1, NO_EXT1, UNREACHABLE_100 = 0x1, 0x2, 0x4, 0x8, 0x10, 0x20
 DESC_MIN, DESC_MAX, DESC_ROOT1, NO_NORM = 0x40, 0x80, 0xC0, 0x100
+PD_L_NMAX, PD_L_MMAX = 2048, 4096                                   # TLC_L_NMAX / TLC_L_MMAX of csrc/tlc_kernels.h: above either, the HUGE class
+PD_HUGE_NMAX, PD_HUGE_MMAX = 65535, (1 << 24) - 2                   # above either, tlc_pd_from_filtration does not compute the graph
+PD_WIDE_MAX_ITEMS, PD_WIDE_FORCE_FALLBACK, PD_WIDE_BAD_INPUT_ROW, PD_WIDE_N_STATS = 1 << 27, 0x40000000, -2, 5   # TLC_PD_WIDE_* of include/tlcgnn.h
+PD_WIDE_LDS_NODES = 40000                                           # TLC_PD_WIDE_LDS_NODES: comp[] of the elder-rule passes in LDS up to here
+PD_WIDE_BLOCK, PD_WIDE_SORT_TILE, PD_WIDE_SCAN_CHUNK = 256, 4096, 2048   # workgroup width, edges per radix tile, flags per scan chunk (csrc/pd_wide.hip)
 DESCRIPTOR_FLAG = {"sum": 0, "min": DESC_MIN, "max": DESC_MAX}      # the three node values of filtration.build_fv
 
 # every symbol include/tlcgnn.h declares (tests check that the library exports all of them)
@@ -41,7 +46,7 @@ SYMBOLS = [
     "tlc_complement_rows", "tlc_complement_pairs", "tlc_select_rows", "tlc_pack_vicinities", "tlc_stack_batch", "tlc_ollivier_ricci_sinkhorn",
     "tlc_near_pairs", "tlc_w2_partial_matching", "tlc_w2_inference_matching", "tlc_gat_layer_bwd", "tlc_edge_head_bwd", "tlc_pack_offsets", "tlc_vicinity_sizes", "tlc_debug_dc_stats", "tlc_debug_tier_counts", "tlc_debug_chunk_counters", "tlc_debug_phase_profile", "tlc_debug_set_option", "tlc_debug_pair_times",
     "tlc_hks_batch", "tlc_hks_batch_work_bytes", "tlc_hks_large_batch", "tlc_hks_large_work_bytes", "tlc_struct_batch", "tlc_struct_batch_work_bytes",
-    "tlc_ollivier_ricci_otd", "tlc_ollivier_ricci_otd_work_bytes",
+    "tlc_ollivier_ricci_otd", "tlc_ollivier_ricci_otd_work_bytes", "tlc_pd_wide", "tlc_pd_wide_work_bytes",
 ]
 
 
@@ -186,6 +191,9 @@ def lib():
         L.tlc_ollivier_ricci_otd_work_bytes.argtypes = [C.c_int64, C.c_int32, C.c_int64, C.POINTER(C.c_int64)]
         L.tlc_ollivier_ricci_otd.argtypes = ([C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 4
                                              + [C.c_int64, C.c_int32, C.c_int64, C.c_void_p])
+        L.tlc_pd_wide_work_bytes.argtypes = [C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int64, C.POINTER(C.c_int64)]
+        L.tlc_pd_wide.argtypes = ([C.c_int64] + [C.c_void_p] * 4 + [C.c_uint32, C.POINTER(C.c_int64), C.c_int64] + [C.c_void_p] * 7
+                                  + [C.c_int64, C.POINTER(C.c_int64), C.c_void_p])
         L.tlc_debug_set_option.argtypes = [C.c_void_p, C.c_char_p, C.c_int]
         L.tlc_debug_dc_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.tlc_debug_tier_counts.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]

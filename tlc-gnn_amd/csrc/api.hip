@@ -1765,6 +1765,7 @@ extern "C" int tlc_pd_from_filtration(int32_t n_graphs, const int64_t* d_node_of
                                       double* d_pd_down, double* d_pd_one, double* d_ext0, int32_t* d_counts,
                                       int32_t* d_edge_rank, void* stream) {
     TLC_REQUIRE(n_graphs >= 0, "n_graphs < 0");
+    TLC_REQUIRE(!(flags & TLC_PD_WIDE_FORCE_FALLBACK), "TLC_PD_WIDE_FORCE_FALLBACK belongs to tlc_pd_wide");
     if (n_graphs == 0) return TLC_OK;
     TLC_REQUIRE(d_node_offs && d_edge_offs && d_f && d_pd_up && d_pd_down && d_pd_one && d_ext0 && d_counts, "null pointer");
     hipStream_t s = (hipStream_t)stream;

@@ -19,14 +19,12 @@
 // Determinism: no floating-point atomics; the only atomics are LDS integer histogram counts.  The AP sum is a double-double
 // (TwoSum) reduction in an order fixed by the segment's length alone, so a segment gives the same bits alone or in a batch.
 #include "tlc_common.h"
+#include "radix_passes.h"   // RK_BS / RK_IPT / RK_TILE, block_excl_sum, the three kernels of a radix pass
 
 namespace {
 
 #define RK_CAP TLC_RANK_LDS_CAP        // scores per LDS-tier segment
 #define RK_LDS_BS 1024                 // LDS tier: threads per workgroup, RK_CAP / RK_LDS_BS = 16 scores per thread
-#define RK_BS 256                      // radix tier: threads per workgroup
-#define RK_IPT 16                      // scores per thread
-#define RK_TILE (RK_BS * RK_IPT)       // radix tier: scores per tile
 #define RK_MAX_SMALL 64                // LDS-tier segments per launch (kernel argument: 1 KiB)
 
 struct SmallSegs {
@@ -90,34 +88,6 @@ __device__ __forceinline__ DD dd_add(DD a, DD b) {
 }
 
 // ---- block-level scans and reductions in a fixed order ------------------------------------------------------------------
-template <int BS>
-struct BlockScratch {
-    long long w[BS / 64];
-    double h[BS / 64], l[BS / 64];
-};
-
-// exclusive prefix sum over the block (thread order); *total = the block's sum
-template <int BS>
-__device__ long long block_excl_sum(long long v, BlockScratch<BS>& sh, long long* total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    long long inc = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const long long o = __shfl_up(inc, d);
-        if (lane >= d) inc += o;
-    }
-    __syncthreads();
-    if (lane == 63) sh.w[wave] = inc;
-    __syncthreads();
-    long long before = 0, tot = 0;
-    for (int w = 0; w < BS / 64; ++w) {
-        if (w < wave) before += sh.w[w];
-        tot += sh.w[w];
-    }
-    *total = tot;
-    return before + inc - v;
-}
-
 // exclusive max-scan (identity -1) over the block; *total = the block's max
 template <int BS>
 __device__ long long block_excl_max(long long v, BlockScratch<BS>& sh, long long* total) {
@@ -325,92 +295,6 @@ __global__ __launch_bounds__(RK_BS) void rk_keys_kernel(const void* __restrict__
     if (threadIdx.x == 0) blk_flags[blockIdx.x] = f;
 }
 
-// hist[d * nb + b] = scores of tile b with digit d (LDS integer counts: the total does not depend on the order)
-template <typename K>
-__global__ __launch_bounds__(RK_BS) void rk_hist_kernel(const K* __restrict__ keys, long long n, int shift, int* __restrict__ hist) {
-    __shared__ int h[256];
-    h[threadIdx.x] = 0;
-    __syncthreads();
-    const long long t0 = (long long)blockIdx.x * RK_TILE;
-    for (int j = threadIdx.x; j < RK_TILE; j += RK_BS) {
-        const long long i = t0 + j;
-        if (i < n) atomicAdd(&h[(int)(keys[i] >> shift) & 255], 1);
-    }
-    __syncthreads();
-    hist[(long long)threadIdx.x * gridDim.x + blockIdx.x] = h[threadIdx.x];
-}
-
-// row d of hist (nb tiles) -> its exclusive prefix in place; tot[d] = the row's sum.  One workgroup per digit.
-__global__ __launch_bounds__(RK_BS) void rk_scan_rows_kernel(int* __restrict__ hist, int nb, int* __restrict__ tot) {
-    __shared__ BlockScratch<RK_BS> sh;
-    int* row = hist + (long long)blockIdx.x * nb;
-    long long carry = 0;
-    for (int b0 = 0; b0 < nb; b0 += RK_BS) {
-        const int b = b0 + threadIdx.x;
-        const long long v = b < nb ? row[b] : 0;
-        long long t;
-        const long long ex = block_excl_sum<RK_BS>(v, sh, &t);
-        if (b < nb) row[b] = (int)(carry + ex);
-        carry += t;
-    }
-    if (threadIdx.x == 0) tot[blockIdx.x] = (int)carry;
-}
-
-// stable scatter of tile b: rounds of RK_BS consecutive scores; inside a round, ranks within the wavefront from 8 ballots
-template <typename K>
-__global__ __launch_bounds__(RK_BS) void rk_scatter_kernel(const K* __restrict__ kin, const uint8_t* __restrict__ lin, K* __restrict__ kout,
-                                                           uint8_t* __restrict__ lout, long long n, int shift,
-                                                           const int* __restrict__ hist, const int* __restrict__ tot) {
-    __shared__ int off[256];
-    __shared__ int wc[RK_BS / 64][256];
-    __shared__ BlockScratch<RK_BS> sh;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    long long t;
-    const long long dbase = block_excl_sum<RK_BS>(tot[tid], sh, &t);
-    off[tid] = (int)dbase + hist[(long long)tid * gridDim.x + blockIdx.x];
-    const long long t0 = (long long)blockIdx.x * RK_TILE;
-    const unsigned long long lt = (1ull << lane) - 1ull;
-    for (int r = 0; r < RK_IPT; ++r) {
-        const long long i = t0 + (long long)r * RK_BS + tid;
-        const bool valid = i < n;
-        K k = 0;
-        uint8_t l = 0;
-        int d = 0;
-        if (valid) {
-            k = kin[i];
-            l = lin[i];
-            d = (int)(k >> shift) & 255;
-        }
-#pragma unroll
-        for (int w = 0; w < RK_BS / 64; ++w) wc[w][tid] = 0;
-        __syncthreads();
-        unsigned long long m = __ballot(valid);
-#pragma unroll
-        for (int bt = 0; bt < 8; ++bt) {
-            const unsigned long long bb = __ballot((d >> bt) & 1);
-            m &= ((d >> bt) & 1) ? bb : ~bb;
-        }
-        const int rank = __popcll(m & lt);
-        if (valid && rank == 0) wc[wave][d] = __popcll(m);
-        __syncthreads();
-        int run = off[tid];
-#pragma unroll
-        for (int w = 0; w < RK_BS / 64; ++w) {
-            const int c = wc[w][tid];
-            wc[w][tid] = run;
-            run += c;
-        }
-        off[tid] = run;
-        __syncthreads();
-        if (valid) {
-            const int dst = wc[wave][d] + rank;
-            kout[dst] = k;
-            lout[dst] = l;
-        }
-        __syncthreads();
-    }
-}
-
 template <typename K>
 __global__ __launch_bounds__(RK_BS) void rk_tile_summary_kernel(const K* __restrict__ keys, const uint8_t* __restrict__ labs, long long n,
                                                                 long long* __restrict__ tpos, long long* __restrict__ tstart) {
@@ -558,7 +442,7 @@ int radix_segment(const void* scores, int sdt, const void* labels, int ldt, long
     for (int shift = 0; shift < (int)(8 * sizeof(K)); shift += 8) {
         hipLaunchKernelGGL(rk_hist_kernel<K>, dim3(nb), dim3(RK_BS), 0, st, ka, n, shift, hist);
         hipLaunchKernelGGL(rk_scan_rows_kernel, dim3(256), dim3(RK_BS), 0, st, hist, nb, tot);
-        hipLaunchKernelGGL(rk_scatter_kernel<K>, dim3(nb), dim3(RK_BS), 0, st, ka, la, kb, lb, n, shift, hist, tot);
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(rk_scatter_kernel<K, uint8_t>), dim3(nb), dim3(RK_BS), 0, st, ka, la, kb, lb, n, shift, hist, tot);
         K* tk = ka; ka = kb; kb = tk;
         uint8_t* tl = la; la = lb; lb = tl;
     }

@@ -407,30 +407,166 @@ def struct_batch(node_ptr, edge_ptr, edges, kinds, normalise=True, total_nodes=N
     return out, status[:B]
 
 
-@_lib.on_device_of
-def pd_from_filtration(node_offs, edge_offs, edges, f, flags=0, want_rank=True):
-    """Batched perturb_filter_function + Union_find + Accelerate_PD (sg2dgm/accelerated_PD.py:6-178).
+def check_pd_large(pd_large):
+    """'host' (tlc_pd_from_filtration alone: the one-workgroup HUGE tier, and no answer above its cap) or 'device' (the HUGE class and
+    everything above it through tlc_pd_wide)."""
+    if pd_large not in ("host", "device"):
+        raise ValueError("pd_large should be 'host' or 'device', not %r" % (pd_large,))
+    return pd_large
 
-    All arguments CUDA tensors: node_offs/edge_offs int64[B+1], edges int32[sum m,2], f float64[sum n].
-    Returns dict(up, down, one, ext0, counts, edge_rank) of CUDA tensors (layout: include/tlcgnn.h).
-    """
-    torch = _lib.require_gpu()
-    dev = f.device
-    B = node_offs.numel() - 1
-    sn, sm = int(f.numel()), int(edges.shape[0])
+
+def pd_wide_work_bytes(sel_nodes, sel_edges):
+    """Bytes of workspace tlc_pd_wide needs for graphs of these node / edge counts (the largest one's): host arithmetic, no device."""
+    nodes, edges = [int(v) for v in sel_nodes], [int(v) for v in sel_edges]
+    if len(nodes) != len(edges):
+        raise ValueError("pd_wide_work_bytes: sel_nodes and sel_edges differ in length")
+    need = C.c_int64(0)
+    S = len(nodes)
+    _lib.check(_lib.lib().tlc_pd_wide_work_bytes((C.c_int64 * max(S, 1))(*nodes), (C.c_int64 * max(S, 1))(*edges), C.c_int64(S), C.byref(need)),
+               "tlc_pd_wide_work_bytes")
+    return need.value
+
+
+def _pd_outputs(torch, dev, B, sn, sm, want_rank):
     up = torch.zeros((max(sn, 1), 2), dtype=torch.float64, device=dev)
     down = torch.zeros((max(sn, 1), 2), dtype=torch.float64, device=dev)
     one = torch.zeros((max(sm, 1), 2), dtype=torch.float64, device=dev)
     ext0 = torch.zeros((max(B, 1), 2), dtype=torch.float64, device=dev)
     counts = torch.zeros((max(B, 1), 4), dtype=torch.int32, device=dev)
     rank = torch.zeros(max(sm, 1), dtype=torch.int32, device=dev) if want_rank else None
+    return dict(up=up, down=down, one=one, ext0=ext0, counts=counts, edge_rank=rank)
+
+
+def _pd_wide_into(out, node_offs, edge_offs, edges, f, flags, sel, work=None):
+    """tlc_pd_wide on the graphs `sel` (host ints) into the full-size tensors of `out`; returns the stats of the last one.  A graph the
+    entry refuses (TLC_ST_BAD_INPUT) raises RuntimeError after every selected graph has run."""
+    torch = _lib.require_gpu()
+    B = node_offs.numel() - 1
+    sel = [int(g) for g in sel]
+    stats = (C.c_int64 * _lib.PD_WIDE_N_STATS)()
+    if not sel:
+        return [0] * _lib.PD_WIDE_N_STATS
+    if any(g < 0 or g >= B for g in sel):
+        raise ValueError("pd_wide: sel outside 0 .. %d" % (B - 1))
+    idx = torch.tensor(sel, dtype=torch.int64, device=f.device)
+    sizes = torch.stack([node_offs[idx + 1] - node_offs[idx], edge_offs[idx + 1] - edge_offs[idx]]).cpu().clamp_(min=0)
+    need = pd_wide_work_bytes(sizes[0].tolist(), sizes[1].tolist())
+    if work is None:
+        work = torch.empty(max(need, 16), dtype=torch.uint8, device=f.device)
+    rc = _lib.lib().tlc_pd_wide(C.c_int64(B), _lib.ptr(node_offs), _lib.ptr(edge_offs), _lib.ptr(edges), _lib.ptr(f), C.c_uint32(flags),
+                                (C.c_int64 * len(sel))(*sel), C.c_int64(len(sel)), _lib.ptr(out["up"]), _lib.ptr(out["down"]),
+                                _lib.ptr(out["one"]), _lib.ptr(out["ext0"]), _lib.ptr(out["counts"]), _lib.ptr(out["edge_rank"]),
+                                _lib.ptr(work), C.c_int64(work.numel()), stats, _lib.stream_ptr())
+    _lib.check(rc, "tlc_pd_wide")
+    bad = (out["counts"][idx, 0] == _lib.PD_WIDE_BAD_INPUT_ROW).nonzero().flatten().tolist()
+    if bad:
+        raise RuntimeError("pd_wide: graph(s) %s: ST_BAD_INPUT (offsets out of order, an id outside 0 .. n-1 or a self loop); their rows "
+                           "hold %d, every other selected graph is computed" % ([sel[i] for i in bad], _lib.PD_WIDE_BAD_INPUT_ROW))
+    return list(stats)
+
+
+@_lib.on_device_of
+def pd_wide(node_offs, edge_offs, edges, f, flags=0, sel=None, want_rank=False, work=None, out=None):
+    """Extended persistence of big graphs on the whole device (tlc_pd_wide): no node cap, 32-bit ids, n + m up to
+    _lib.PD_WIDE_MAX_ITEMS.  Arguments and the returned dict as `pd_from_filtration`, plus `stats` = [divide-and-conquer levels, Boruvka
+    rounds, kernel launches, fallback ran, status] of the last selected graph.
+
+    sel: the graphs to compute (host ints, any order; None: all); rows and slots of the others keep what `out` held (None: zeros).
+    work: a uint8 CUDA tensor of at least `pd_wide_work_bytes` of the largest selected graph (None: allocated).  edge_rank is in this
+    tier's own descending order: under equal keys a valid permutation, not the reference's.  A refused graph raises RuntimeError."""
+    torch = _lib.require_gpu()
+    B = node_offs.numel() - 1
+    sn, sm = int(f.numel()), int(edges.shape[0])
+    if out is None:
+        out = _pd_outputs(torch, f.device, B, sn, sm, want_rank)
+    node_offs, edge_offs, edges, f = node_offs.contiguous(), edge_offs.contiguous(), edges.contiguous(), f.contiguous()
+    try:
+        stats = _pd_wide_into(out, node_offs, edge_offs, edges, f, flags, range(B) if sel is None else sel, work)
+    except RuntimeError as err:
+        err.partial = out
+        raise
+    rank = out["edge_rank"]
+    return dict(up=out["up"], down=out["down"], one=out["one"], ext0=out["ext0"][:B], counts=out["counts"][:B],
+                edge_rank=None if rank is None else rank[:sm], stats=stats)
+
+
+@_lib.on_device_of
+def pd_from_filtration(node_offs, edge_offs, edges, f, flags=0, want_rank=True, pd_large="host"):
+    """Batched perturb_filter_function + Union_find + Accelerate_PD (sg2dgm/accelerated_PD.py:6-178).
+
+    All arguments CUDA tensors: node_offs/edge_offs int64[B+1], edges int32[sum m,2], f float64[sum n].
+    Returns dict(up, down, one, ext0, counts, edge_rank) of CUDA tensors (layout: include/tlcgnn.h).
+
+    pd_large='host' (default): tlc_pd_from_filtration alone -- a graph above PD_L_NMAX nodes or PD_L_MMAX edges runs in one workgroup, one
+    above 65 535 nodes or 2^24 - 2 edges is not computed (counts row -1).  'device': those graphs (picked from the offsets on the
+    device) go through `pd_wide` instead, the rest through the same launch as before; edge_rank of the rerouted graphs is then in
+    pd_wide's order.
+    """
+    check_pd_large(pd_large)
+    torch = _lib.require_gpu()
+    dev = f.device
+    B = node_offs.numel() - 1
+    sn, sm = int(f.numel()), int(edges.shape[0])
+    out = _pd_outputs(torch, dev, B, sn, sm, want_rank)
+    up, down, one, ext0, counts, rank = out["up"], out["down"], out["one"], out["ext0"], out["counts"], out["edge_rank"]
     edges = edges.contiguous()
-    rc = _lib.lib().tlc_pd_from_filtration(C.c_int32(B), _lib.ptr(node_offs.contiguous()), _lib.ptr(edge_offs.contiguous()),
-                                           _lib.ptr(edges), _lib.ptr(f.contiguous()), C.c_uint32(flags), _lib.ptr(up),
-                                           _lib.ptr(down), _lib.ptr(one), _lib.ptr(ext0), _lib.ptr(counts),
-                                           _lib.ptr(rank), _lib.stream_ptr())
-    _lib.check(rc, "tlc_pd_from_filtration")
+    node_offs, edge_offs, f = node_offs.contiguous(), edge_offs.contiguous(), f.contiguous()
+    wide = []
+    if pd_large == "device" and B > 0:
+        n_g, m_g = node_offs[1:] - node_offs[:-1], edge_offs[1:] - edge_offs[:-1]
+        wide = ((n_g > _lib.PD_L_NMAX) | (m_g > _lib.PD_L_MMAX)).nonzero().flatten().tolist()
+    if wide:
+        # the entry takes consecutive offsets only, so the graphs that stay are gathered into a packed batch of their own, computed
+        # by the same entry, and their slots scattered back (`_pd_from_filtration_subset`); the rerouted ones go through tlc_pd_wide
+        keep = torch.ones(B, dtype=torch.bool, device=dev)
+        keep[torch.tensor(wide, dtype=torch.int64, device=dev)] = False
+        sub = keep.nonzero().flatten()
+        _pd_from_filtration_subset(node_offs, edge_offs, edges, f, flags, sub, out)
+        _pd_wide_into(out, node_offs, edge_offs, edges, f, flags, wide)
+    else:
+        rc = _lib.lib().tlc_pd_from_filtration(C.c_int32(B), _lib.ptr(node_offs), _lib.ptr(edge_offs),
+                                               _lib.ptr(edges), _lib.ptr(f), C.c_uint32(flags), _lib.ptr(up),
+                                               _lib.ptr(down), _lib.ptr(one), _lib.ptr(ext0), _lib.ptr(counts),
+                                               _lib.ptr(rank), _lib.stream_ptr())
+        _lib.check(rc, "tlc_pd_from_filtration")
     return dict(up=up, down=down, one=one, ext0=ext0[:B], counts=counts[:B], edge_rank=None if rank is None else rank[:sm])
+
+
+def _pd_from_filtration_subset(node_offs, edge_offs, edges, f, flags, sub, out):
+    """tlc_pd_from_filtration on the graphs `sub` (int64 CUDA tensor, ascending) of a packed batch, into the full-size tensors of `out`.
+    The entry takes per-graph START offsets only through consecutive arrays, so the kept graphs are gathered into a packed batch of
+    their own with torch ops on the device, computed, and their slots scattered back."""
+    torch = _lib.require_gpu()
+    S = int(sub.numel())
+    if S == 0:
+        return None
+    dev = f.device
+    n_g, m_g = (node_offs[1:] - node_offs[:-1])[sub], (edge_offs[1:] - edge_offs[:-1])[sub]
+    zero = torch.zeros(1, dtype=torch.int64, device=dev)
+    no2, eo2 = torch.cat([zero, n_g.cumsum(0)]), torch.cat([zero, m_g.cumsum(0)])
+    sn2, sm2 = int(no2[-1]), int(eo2[-1])
+    # position i of the gathered batch <- position src[i] of the full one
+    gn = torch.repeat_interleave(torch.arange(S, device=dev), n_g)
+    src_n = torch.arange(sn2, device=dev) - no2[:-1][gn] + node_offs[:-1][sub][gn]
+    ge = torch.repeat_interleave(torch.arange(S, device=dev), m_g)
+    src_e = torch.arange(sm2, device=dev) - eo2[:-1][ge] + edge_offs[:-1][sub][ge]
+    f2 = f[src_n].contiguous()
+    e2 = edges[src_e].contiguous() if sm2 else torch.zeros((1, 2), dtype=torch.int32, device=dev)
+    o2 = _pd_outputs(torch, dev, S, sn2, sm2, out["edge_rank"] is not None)
+    rc = _lib.lib().tlc_pd_from_filtration(C.c_int32(S), _lib.ptr(no2), _lib.ptr(eo2), _lib.ptr(e2), _lib.ptr(f2), C.c_uint32(flags),
+                                           _lib.ptr(o2["up"]), _lib.ptr(o2["down"]), _lib.ptr(o2["one"]), _lib.ptr(o2["ext0"]),
+                                           _lib.ptr(o2["counts"]), _lib.ptr(o2["edge_rank"]), _lib.stream_ptr())
+    _lib.check(rc, "tlc_pd_from_filtration")
+    if sn2:
+        out["up"][src_n] = o2["up"][:sn2]
+        out["down"][src_n] = o2["down"][:sn2]
+    if sm2:
+        out["one"][src_e] = o2["one"][:sm2]
+        if out["edge_rank"] is not None:
+            out["edge_rank"][src_e] = o2["edge_rank"][:sm2]
+    out["ext0"][sub] = o2["ext0"][:S]
+    out["counts"][sub] = o2["counts"][:S]
+    return o2
 
 
 @_lib.on_device_of

@@ -51,15 +51,16 @@ def _unpack(simplex_filter):
     return nodes, edges, f, e
 
 
-def _run(simplex_filter, flags):
+def _run(simplex_filter, flags, pd_large='host'):
     import torch
+    engine.check_pd_large(pd_large)
     nodes, edges, f, e = _unpack(simplex_filter)
-    if len(nodes) > 65535:
-        raise ValueError("graphs with more than 65535 nodes are not supported by the HIP PD kernel")
+    if len(nodes) > 65535 and pd_large != 'device':
+        raise ValueError("graphs with more than 65535 nodes are not supported by the HIP PD kernel (pd_large='device' takes them)")
     dev = "cuda"
     r = engine.pd_from_filtration(torch.tensor([0, len(nodes)], dtype=torch.int64, device=dev),
                                   torch.tensor([0, len(edges)], dtype=torch.int64, device=dev),
-                                  torch.from_numpy(e).to(dev), torch.from_numpy(f).to(dev), flags)
+                                  torch.from_numpy(e).to(dev), torch.from_numpy(f).to(dev), flags, pd_large=pd_large)
     c = r["counts"][0].cpu().numpy()
     out = dict(up=r["up"][:c[0]].cpu().numpy(), down=r["down"][:c[1]].cpu().numpy(), one=r["one"][:c[2]].cpu().numpy(),
                ext0=r["ext0"][0].cpu().numpy(), rank=r["edge_rank"].cpu().numpy(), edges=edges)
@@ -73,9 +74,11 @@ def _pos_neg(res):
     return [[edges[i][0], edges[i][1]] for _, i in pos], [[edges[i][0], edges[i][1]] for _, i in neg]
 
 
-def Union_find(simplex_filter):
-    """:26-113 -> (PD, Pos_edges, Neg_edges); PD = PD_up + [[min,max]] + PD_down + [[max,min]] (:110)."""
-    res = _run(simplex_filter, 0)
+def Union_find(simplex_filter, pd_large='host'):
+    """:26-113 -> (PD, Pos_edges, Neg_edges); PD = PD_up + [[min,max]] + PD_down + [[max,min]] (:110).
+    pd_large (not in the reference): 'host' or 'device', see `engine.pd_from_filtration`; with 'device' a graph of the HUGE class gets
+    its split in tlc_pd_wide's order among equal keys -- hand the same value to Accelerate_PD."""
+    res = _run(simplex_filter, 0, pd_large)
     mn, mx = float(res["ext0"][0]), float(res["ext0"][1])
     PD = res["up"].tolist() + [[mn, mx]] + res["down"].tolist() + [[mx, mn]]
     Pos_edges, Neg_edges = _pos_neg(res)
@@ -95,11 +98,11 @@ def check_split(res, Pos_edges, Neg_edges):
         raise ValueError("Accelerate_PD: Neg_edges is not the spanning tree Union_find yields for this simplex_filter")
 
 
-def Accelerate_PD(Pos_edges, Neg_edges, simplex_filter):
+def Accelerate_PD(Pos_edges, Neg_edges, simplex_filter, pd_large='host'):
     """:115-178 -> PD_one (list of [low, large]).  Pos/Neg must be what Union_find returned for the same
-    simplex_filter (checked: ValueError otherwise)."""
+    simplex_filter and the same pd_large (checked: ValueError otherwise)."""
     if len(Neg_edges) == 0:
         raise IndexError("list index out of range")          # list(Nodes)[0] on an empty graph (:122)
-    res = _run(simplex_filter, 0)
+    res = _run(simplex_filter, 0, pd_large)
     check_split(res, Pos_edges, Neg_edges)
     return res["one"].tolist()
