@@ -265,6 +265,49 @@ int tlc_pd_wide(int64_t n_graphs, const int64_t* d_node_offs, const int64_t* d_e
                 double* d_pd_up, double* d_pd_down, double* d_pd_one, double* d_ext0, int32_t* d_counts,
                 int32_t* d_edge_rank, void* d_work, int64_t work_bytes, int64_t* h_stats, void* stream);
 
+/* ---- d diagram / d filtration of the two entries above (csrc/pd_grad.hip) --------------------------------------
+ * Every coordinate of every point those entries write is a copy of one f[v]: the Jacobian is a 0/1 selection matrix.  They return
+ * the values only; tlc_pd_point_vertices recovers the vertices from them, after the forward, by one rule:
+ *     the vertex of a coordinate c of graph g is the LOWEST local id v in 0 .. n_g-1 with f[node_offs[g] + v] == c
+ * (IEEE ==: -0.0 matches +0.0, a NaN matches nothing).  Where the values of a graph are pairwise distinct this is the critical vertex
+ * of the pairing.  Under ties the map from f to the diagram is not differentiable, and the rule is a fixed CONVENTION: the same in
+ * every size class and for both forward entries, and independent of tlc_pd_wide's own Pos / Neg choice among equal keys.
+ * Both entries take the packed layout and the slots of tlc_pd_from_filtration and its d_counts rows as the source of truth: rows
+ * 0 .. counts[g,k)-1 of a slot are points, the rows behind them are not.
+ *
+ * tlc_pd_point_vertices: d_vert_up / d_vert_down int32[sum n, 2], d_vert_one int32[sum m, 2], d_vert_ext0 int32[n_graphs, 2] (the
+ * vertices of [min f, max f]): local ids in the point rows of every computed graph, -1 in the slot's rows behind the points.
+ * d_status uint8[n_graphs]: TLC_ST_OK; TLC_ST_TOO_LARGE for a d_counts row of -1 (or n + m above TLC_PD_WIDE_MAX_ITEMS), rows
+ * untouched; TLC_ST_BAD_INPUT for a row of TLC_PD_WIDE_BAD_INPUT_ROW, counts that do not fit the slot, offsets out of order or
+ * negative (rows untouched), or a coordinate that no vertex of the graph holds -- a diagram of another f, a NaN -- whose entry is
+ * then -1.  No other graph is affected.  A graph without nodes: TLC_ST_OK, nothing written.
+ *
+ * tlc_pd_filtration_grad: d_grad_f float64[sum n].  Every entry of a graph whose d_status is TLC_ST_OK is written, zeros included;
+ * the slices of the other graphs are left untouched.  grad_f[v] = the sum of the gradients d_g_* (each float64 in the layout of its
+ * slot; NULL = zeros) of the coordinates whose vertex is v, in fp64 from +0.0, left to right in this order: up rows ascending (birth,
+ * then death of a row), then down rows, then one rows, then ext0 (birth, death).  Gradients in rows behind the points are ignored.
+ * No floating-point atomics: the bits of a graph's slice depend neither on the run, nor on the batch around it, nor on d_work.
+ *
+ * Size classes by node count, cut on the device: up to TLC_PD_VERT_WAVE_NMAX one wavefront per graph; up to TLC_PD_VERT_LDS_NMAX
+ * (= the forward's TLC_L_NMAX) one workgroup per graph; above, the whole device, one graph after the other, in d_work.
+ * d_work: tlc_pd_grad_work_bytes(largest node count, largest edge count of the batch) bytes -- host arithmetic, no device; 0 (and
+ * d_work may be NULL) when no graph exceeds TLC_PD_VERT_LDS_NMAX nodes.  Both entries read the batch's offsets back once and
+ * synchronise the stream before they launch anything.
+ * TLC_ERR_INVALID_ARG, nothing launched: null required pointers, n_graphs < 0, work_bytes < 0, or a d_work too small for a graph of
+ * the batch -- the message names the bytes held and the bytes needed.  n_graphs == 0: TLC_OK, nothing read. */
+#define TLC_PD_VERT_WAVE_NMAX  64
+#define TLC_PD_VERT_LDS_NMAX   2048
+int tlc_pd_grad_work_bytes(int64_t max_nodes, int64_t max_edges, int64_t* bytes);
+int tlc_pd_point_vertices(int64_t n_graphs, const int64_t* d_node_offs, const int64_t* d_edge_offs, const double* d_f,
+                          const double* d_pd_up, const double* d_pd_down, const double* d_pd_one, const double* d_ext0,
+                          const int32_t* d_counts, int32_t* d_vert_up, int32_t* d_vert_down, int32_t* d_vert_one,
+                          int32_t* d_vert_ext0, uint8_t* d_status, void* d_work, int64_t work_bytes, void* stream);
+int tlc_pd_filtration_grad(int64_t n_graphs, const int64_t* d_node_offs, const int64_t* d_edge_offs, const int32_t* d_counts,
+                           const int32_t* d_vert_up, const int32_t* d_vert_down, const int32_t* d_vert_one,
+                           const int32_t* d_vert_ext0, const double* d_g_up, const double* d_g_down, const double* d_g_one,
+                           const double* d_g_ext0, const uint8_t* d_status, double* d_grad_f, void* d_work, int64_t work_bytes,
+                           void* stream);
+
 /* ---- P9: PersistenceImager(resolution=res).transform (sg2dgm/PersistenceImager.pyx:352-388) -------
  * isotropic sigma=1 Gaussian, ranges [0,1]^2, linear-ramp weight (:9-30), birth-death input (skew=True).
  *   d_offs int64[n_dgms+1];  d_pts float64[sum k, 2];  d_out float64[n_dgms, res*res] */

@@ -32,7 +32,8 @@ PD_HUGE_NMAX, PD_HUGE_MMAX = 65535, (1 << 24) - 2                   # above eith
 PD_WIDE_MAX_ITEMS, PD_WIDE_FORCE_FALLBACK, PD_WIDE_BAD_INPUT_ROW, PD_WIDE_N_STATS = 1 << 27, 0x40000000, -2, 5   # TLC_PD_WIDE_* of include/tlcgnn.h
 PD_WIDE_LDS_NODES = 40000                                           # TLC_PD_WIDE_LDS_NODES: comp[] of the elder-rule passes in LDS up to here
 PD_WIDE_BLOCK, PD_WIDE_SORT_TILE, PD_WIDE_SCAN_CHUNK = 256, 4096, 2048   # workgroup width, edges per radix tile, flags per scan chunk (csrc/pd_wide.hip)
-DESCRIPTOR_FLAG = {"sum": 0, "min": DESC_MIN, "max": DESC_MAX}      # the three node values of filtration.build_fv
+PD_VERT_WAVE_NMAX, PD_VERT_LDS_NMAX = 64, 2048                       # TLC_PD_VERT_*: the size classes of csrc/pd_grad.hip (wavefront / workgroup per graph)
+DESCRIPTOR_FLAG ={"sum": 0, "min": DESC_MIN, "max": DESC_MAX}      # the three node values of filtration.build_fv
 
 # every symbol include/tlcgnn.h declares (tests check that the library exports all of them)
 SYMBOLS = [
@@ -47,6 +48,7 @@ SYMBOLS = [
     "tlc_near_pairs", "tlc_w2_partial_matching", "tlc_w2_inference_matching", "tlc_gat_layer_bwd", "tlc_edge_head_bwd", "tlc_pack_offsets", "tlc_vicinity_sizes", "tlc_debug_dc_stats", "tlc_debug_tier_counts", "tlc_debug_chunk_counters", "tlc_debug_phase_profile", "tlc_debug_set_option", "tlc_debug_pair_times",
     "tlc_hks_batch", "tlc_hks_batch_work_bytes", "tlc_hks_large_batch", "tlc_hks_large_work_bytes", "tlc_struct_batch", "tlc_struct_batch_work_bytes",
     "tlc_ollivier_ricci_otd", "tlc_ollivier_ricci_otd_work_bytes", "tlc_pd_wide", "tlc_pd_wide_work_bytes",
+    "tlc_pd_grad_work_bytes", "tlc_pd_point_vertices", "tlc_pd_filtration_grad",
 ]
 
 
@@ -194,6 +196,9 @@ def lib():
         L.tlc_pd_wide_work_bytes.argtypes = [C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int64, C.POINTER(C.c_int64)]
         L.tlc_pd_wide.argtypes = ([C.c_int64] + [C.c_void_p] * 4 + [C.c_uint32, C.POINTER(C.c_int64), C.c_int64] + [C.c_void_p] * 7
                                   + [C.c_int64, C.POINTER(C.c_int64), C.c_void_p])
+        L.tlc_pd_grad_work_bytes.argtypes = [C.c_int64, C.c_int64, C.POINTER(C.c_int64)]
+        L.tlc_pd_point_vertices.argtypes = [C.c_int64] + [C.c_void_p] * 14 + [C.c_int64, C.c_void_p]
+        L.tlc_pd_filtration_grad.argtypes = [C.c_int64] + [C.c_void_p] * 14 + [C.c_int64, C.c_void_p]
         L.tlc_debug_set_option.argtypes = [C.c_void_p, C.c_char_p, C.c_int]
         L.tlc_debug_dc_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.tlc_debug_tier_counts.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]

@@ -10,7 +10,7 @@ and there is no CPU path.
 """
 import torch
 
-from . import ops, engine
+from . import _lib, ops, engine
 
 
 class GatLayer(torch.autograd.Function):
@@ -102,6 +102,61 @@ class DiagramImage(torch.autograd.Function):
         pts, offs = ctx.saved_tensors
         g = engine.pi_raster_wgrad(offs, pts, gimg.to(torch.float64), ctx.res)
         return g.to(ctx.dtype), None, None
+
+
+class ExtendedPersistence(torch.autograd.Function):
+    """The exact extended persistence as a differentiable function of the filtration values: (up, down, one, ext0, counts) in the slot
+    layout of `engine.pd_from_filtration`, the same values bit for bit.  Every coordinate is a copy of one f[v], so the backward is a
+    selection: `engine.pd_point_vertices` finds the vertex of every coordinate after the forward (the lowest id with f[v] == c --
+    the critical vertex where a graph's values are distinct, a fixed convention under ties, where the diagram is not differentiable:
+    DESIGN.md 6.6), and one `tlc_pd_filtration_grad` sums the point gradients into grad f in a fixed order.  f may be float32 or
+    float64: the diagrams are computed in float64 and returned in f's dtype, and so is the gradient."""
+
+    @staticmethod
+    def forward(ctx, f, node_offs, edge_offs, edges, flags, pd_large):
+        f64 = f.detach().to(torch.float64).contiguous()
+        pd = engine.pd_from_filtration(node_offs, edge_offs, edges, f64, flags=flags, want_rank=False, pd_large=pd_large)
+        verts = engine.pd_point_vertices(node_offs, edge_offs, f64, pd)
+        bad = verts["status"].nonzero().flatten().tolist()
+        if bad:
+            raise RuntimeError("extended_persistence: graph(s) %s are not computed: status %s (%d = ST_TOO_LARGE: above the cap of "
+                               "pd_large='host'; %d = ST_BAD_INPUT)" % (bad, verts["status"][bad].tolist(), _lib.ST_TOO_LARGE, _lib.ST_BAD_INPUT))
+        ctx.save_for_backward(node_offs, edge_offs, pd["counts"], verts["up"], verts["down"], verts["one"], verts["ext0"], verts["status"])
+        ctx.dtype, ctx.n = f.dtype, f.numel()
+        ctx.mark_non_differentiable(pd["counts"])
+        return tuple(pd[k].to(f.dtype) for k in engine.VERTEX_KEYS) + (pd["counts"],)
+
+    @staticmethod
+    def backward(ctx, g_up, g_down, g_one, g_ext0, _g_counts):
+        node_offs, edge_offs, counts, v_up, v_down, v_one, v_ext0, status = ctx.saved_tensors
+        verts = dict(up=v_up, down=v_down, one=v_one, ext0=v_ext0, status=status)
+        g = engine.pd_filtration_grad(node_offs, edge_offs, counts, verts, g_up, g_down, g_one, g_ext0)
+        return g[:ctx.n].to(ctx.dtype), None, None, None, None, None
+
+
+def extended_persistence(f, node_offs, edge_offs, edges, flags=_lib.KEEP_ZERO_PERS, pd_large="host"):
+    """-> (up, down, one, ext0, counts): the diagrams of `engine.pd_from_filtration` in slot layout, differentiable in f (counts is
+    not).  A graph that is not computed raises RuntimeError naming it."""
+    engine.check_pd_large(pd_large)
+    return ExtendedPersistence.apply(f, node_offs, edge_offs, edges, int(flags), pd_large)
+
+
+def packed_points(points, slot_offs, n_points):
+    """The first n_points[g] rows of every slot of `points` [sum slots, 2] (slot g starts at slot_offs[g]), packed:
+    -> (pts [K, 2], offs int64[B + 1]) -- what `diagram_image` and `diagram_loss` take.  Index ops on the device, no loop over graphs;
+    every row is read once, so the backward (an index_put without duplicates) is deterministic."""
+    return pack_rows(points, slot_offs[:-1], n_points)
+
+
+def pack_rows(points, starts, n_points):
+    """`packed_points` for slots given by their first rows `starts` [S] (any order, not overlapping)."""
+    cnt = n_points.to(torch.int64)
+    offs = torch.zeros(cnt.numel() + 1, dtype=torch.int64, device=points.device)
+    offs[1:] = torch.cumsum(cnt, 0)
+    K = int(offs[-1])
+    owner = torch.repeat_interleave(torch.arange(cnt.numel(), device=points.device), cnt, output_size=K)
+    rows = torch.arange(K, device=points.device) - offs[:-1][owner] + starts.to(torch.int64)[owner]
+    return points[rows], offs
 
 
 def diagram_image(pd_hat, offs=None, res=5):

@@ -569,6 +569,86 @@ def _pd_from_filtration_subset(node_offs, edge_offs, edges, f, flags, sub, out):
     return o2
 
 
+def pd_grad_work_bytes(max_nodes, max_edges):
+    """Bytes of workspace `pd_point_vertices` / `pd_filtration_grad` need for a batch whose largest graph has this many nodes and its
+    largest edge list this many edges (tlc_pd_grad_work_bytes): host arithmetic, no device; 0 up to _lib.PD_VERT_LDS_NMAX nodes."""
+    need = C.c_int64(0)
+    _lib.check(_lib.lib().tlc_pd_grad_work_bytes(C.c_int64(int(max_nodes)), C.c_int64(int(max_edges)), C.byref(need)), "tlc_pd_grad_work_bytes")
+    return need.value
+
+
+def _pd_grad_work(torch, node_offs, edge_offs, work):
+    """(workspace tensor or None, its bytes) for the batch: allocated from the largest node / edge count unless the caller's is given."""
+    if work is not None:
+        return work, int(work.numel())
+    if node_offs.numel() < 2:
+        return None, 0
+    top = torch.stack([(node_offs[1:] - node_offs[:-1]).max(), (edge_offs[1:] - edge_offs[:-1]).max()]).clamp_(min=0).tolist()
+    need = pd_grad_work_bytes(top[0], top[1])
+    return (torch.empty(need, dtype=torch.uint8, device=node_offs.device) if need else None), need
+
+
+VERTEX_KEYS = ("up", "down", "one", "ext0")
+
+
+@_lib.on_device_of
+def pd_point_vertices(node_offs, edge_offs, f, pd, work=None):
+    """The vertex behind every coordinate of the diagrams `pd` (the dict `pd_from_filtration` or `pd_wide` returned for this f):
+    the lowest local id v with f[v] == c (tlc_pd_point_vertices).  Returns dict(up, down int32[sum n, 2], one
+    int32[sum m, 2], ext0 int32[B, 2], status uint8[B]); -1 behind a slot's points.  status: ST_OK, ST_TOO_LARGE (a counts row of -1),
+    ST_BAD_INPUT (a refused graph, or a coordinate no vertex holds: that entry is -1).  work: a uint8 CUDA tensor of
+    `pd_grad_work_bytes` (None: allocated; none is needed up to _lib.PD_VERT_LDS_NMAX nodes)."""
+    torch = _lib.require_gpu()
+    dev = f.device
+    B = node_offs.numel() - 1
+    node_offs, edge_offs, f = node_offs.contiguous(), edge_offs.contiguous(), f.contiguous()
+    up, down, one = pd["up"].contiguous(), pd["down"].contiguous(), pd["one"].contiguous()
+    ext0, counts = pd["ext0"].contiguous(), pd["counts"].contiguous()
+    out = dict(up=torch.full((up.shape[0], 2), -1, dtype=torch.int32, device=dev),
+               down=torch.full((down.shape[0], 2), -1, dtype=torch.int32, device=dev),
+               one=torch.full((one.shape[0], 2), -1, dtype=torch.int32, device=dev),
+               ext0=torch.full((max(B, 1), 2), -1, dtype=torch.int32, device=dev),
+               status=torch.zeros(max(B, 1), dtype=torch.uint8, device=dev))
+    work, nbytes = _pd_grad_work(torch, node_offs, edge_offs, work)
+    rc = _lib.lib().tlc_pd_point_vertices(C.c_int64(B), _lib.ptr(node_offs), _lib.ptr(edge_offs), _lib.ptr(f), _lib.ptr(up), _lib.ptr(down),
+                                          _lib.ptr(one), _lib.ptr(ext0), _lib.ptr(counts), _lib.ptr(out["up"]), _lib.ptr(out["down"]),
+                                          _lib.ptr(out["one"]), _lib.ptr(out["ext0"]), _lib.ptr(out["status"]), _lib.ptr(work),
+                                          C.c_int64(nbytes), _lib.stream_ptr())
+    _lib.check(rc, "tlc_pd_point_vertices")
+    out["ext0"], out["status"] = out["ext0"][:B], out["status"][:B]
+    return out
+
+
+@_lib.on_device_of
+def pd_filtration_grad(node_offs, edge_offs, counts, verts, g_up=None, g_down=None, g_one=None, g_ext0=None, work=None, out=None):
+    """grad_f float64[sum n]: per vertex, the sum of the gradients g_* (float64, each in the layout of its slot; None: zeros) of the
+    coordinates `verts` (the dict of `pd_point_vertices`) assigns to it, in the fixed order of tlc_pd_filtration_grad -- no atomics, the
+    same bits every run.  Slices of graphs whose status is not ST_OK keep what `out` held (None: zeros)."""
+    torch = _lib.require_gpu()
+    dev = node_offs.device
+    B = node_offs.numel() - 1
+    node_offs, edge_offs, counts = node_offs.contiguous(), edge_offs.contiguous(), counts.contiguous()
+    sn = int(verts["up"].shape[0])
+    if out is None:
+        out = torch.zeros(sn, dtype=torch.float64, device=dev)
+    grads = []
+    for key, g in zip(VERTEX_KEYS, (g_up, g_down, g_one, g_ext0)):
+        if g is not None:
+            g = g.to(torch.float64).contiguous()
+            if g.shape[0] < (B if key == "ext0" else verts[key].shape[0]) or g.shape[-1] != 2:
+                raise ValueError("pd_filtration_grad: g_%s has shape %s, its slot %s" % (key, tuple(g.shape), tuple(verts[key].shape)))
+        grads.append(g)
+    work, nbytes = _pd_grad_work(torch, node_offs, edge_offs, work)
+    status = verts["status"].contiguous()
+    rc = _lib.lib().tlc_pd_filtration_grad(C.c_int64(B), _lib.ptr(node_offs), _lib.ptr(edge_offs), _lib.ptr(counts),
+                                           _lib.ptr(verts["up"]), _lib.ptr(verts["down"]), _lib.ptr(verts["one"]), _lib.ptr(verts["ext0"]),
+                                           _lib.ptr(grads[0]), _lib.ptr(grads[1]), _lib.ptr(grads[2]), _lib.ptr(grads[3]),
+                                           _lib.ptr(status) if B > 0 else None, _lib.ptr(out), _lib.ptr(work), C.c_int64(nbytes),
+                                           _lib.stream_ptr())
+    _lib.check(rc, "tlc_pd_filtration_grad")
+    return out
+
+
 @_lib.on_device_of
 def pi_raster(offs, pts, res=5):
     """Batched PersistenceImager(resolution=res).transform (sg2dgm/PersistenceImager.pyx:352-388).

@@ -1,0 +1,62 @@
+"""Topological layers on a LEARNED filtration: the exact extended persistence of a packed batch of graphs as a differentiable
+function of the node values f, composed with the imager and the Wasserstein loss of `autograd`.
+
+    f (an MLP on node features, an HKS time, ...)  ->  diagrams(f, ...)  ->  images(...) / wasserstein_to(...)  ->  loss.backward()
+
+The diagrams are `engine.pd_from_filtration`'s with TLC_KEEP_ZERO_PERS (what `data_utils_GC.compute_persistence_image` computes),
+bit for bit; their gradient is the selection of `autograd.ExtendedPersistence`: each coordinate is a copy of one
+f[v].  All arguments are CUDA tensors in the packed layout of `engine.pd_from_filtration`: node_offs / edge_offs int64[B + 1], edges
+int32[sum m, 2] local ids, f float32 or float64 [sum n]."""
+import torch
+
+from . import _lib, autograd, engine
+
+WHICH = ("ord0+ext1", "ord0", "ext1")
+
+
+def check_which(which):
+    if which not in WHICH:
+        raise ValueError("which should be one of %s, not %r" % (WHICH, which))
+    return which
+
+
+def diagrams(f, node_offs, edge_offs, edges, pd_large="host"):
+    """-> dict(ord0, ord0_offs, rel1, rel1_offs, ext1, ext1_offs, ext0, counts): the three diagrams of every graph packed
+    ([K, 2] points with int64[B + 1] offsets: the input `autograd.diagram_image` and `autograd.diagram_loss` take) and ext0 [B, 2]
+    = [min f, max f], all differentiable in f; counts int32[B, 4] is not."""
+    up, down, one, ext0, counts = autograd.extended_persistence(f, node_offs, edge_offs, edges, _lib.KEEP_ZERO_PERS, pd_large)
+    ord0, o0 = autograd.packed_points(up, node_offs, counts[:, 0])
+    rel1, o1 = autograd.packed_points(down, node_offs, counts[:, 1])
+    ext1, o2 = autograd.packed_points(one, edge_offs, counts[:, 2])
+    return dict(ord0=ord0, ord0_offs=o0, rel1=rel1, rel1_offs=o1, ext1=ext1, ext1_offs=o2, ext0=ext0, counts=counts)
+
+
+def _select(f, node_offs, edge_offs, edges, which, pd_large):
+    """(points, offs) of the diagram `which` of every graph; 'ord0+ext1': a graph's Ord0 points, then its Ext1 points."""
+    up, _, one, _, counts = autograd.extended_persistence(f, node_offs, edge_offs, edges, _lib.KEEP_ZERO_PERS, pd_large)
+    if which == "ord0":
+        return autograd.packed_points(up, node_offs, counts[:, 0])
+    if which == "ext1":
+        return autograd.packed_points(one, edge_offs, counts[:, 2])
+    # two slots per graph in the concatenation of the two slot arrays
+    starts = torch.stack([node_offs[:-1], edge_offs[:-1] + up.shape[0]], 1).flatten()
+    pts, offs = autograd.pack_rows(torch.cat([up, one]), starts, counts[:, [0, 2]].flatten())
+    return pts, offs[::2].contiguous()
+
+
+def images(f, node_offs, edge_offs, edges, which="ord0+ext1", res=5, pd_large="host"):
+    """[B, res * res] persistence images of every graph's diagram `which` -- the three images of
+    `data_utils_GC.compute_persistence_image` (Ord0 ++ Ext1, Ord0, Ext1) -- as a differentiable function of f, through
+    `autograd.diagram_image`.  The imager's gradient is the reference's (pimg.py:354-400): a point's two normal-CDF factors are
+    computed from detached coordinates, so the gradient flows through the point's weight only."""
+    check_which(which)
+    pts, offs = _select(f, node_offs, edge_offs, edges, which, pd_large)
+    return autograd.diagram_image(pts, offs, res)
+
+
+def wasserstein_to(f, node_offs, edge_offs, edges, target_pts, target_offs, which="ord0+ext1", order=2, pd_large="host"):
+    """[B] Wasserstein distances (order `order`, both diagrams may use the diagonal: `autograd.diagram_loss(..., infer=True)`) between
+    every graph's diagram `which` and the fixed target diagrams target_pts [sum k, 2] / target_offs int64[B + 1]; differentiable in f."""
+    check_which(which)
+    pts, offs = _select(f, node_offs, edge_offs, edges, which, pd_large)
+    return autograd.diagram_loss(pts, target_pts.to(pts.dtype), order=order, xoff=offs, yoff=target_offs, infer=True)[0]
