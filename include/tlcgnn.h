@@ -678,6 +678,59 @@ int tlc_w2_inference_matching(int32_t n_problems, const int64_t* d_xoff, const d
                               double* d_wyd, int32_t* d_assign_x, int32_t* d_assign_y, double* d_gradX, uint8_t* d_status,
                               void* stream);
 
+/* ---- The sliced Wasserstein diagram loss and its gradient (csrc/sliced_w.hip) ----------------------------------
+ * `compute_PD_loss(kernel='sliced')` of Knowledge_Distillation/Teacher_model.py:110-124 (the distance of Carriere et al.), at any
+ * diagram size.  The directions and the scale are INPUTS: the reference's angles are made by the caller (ops.sliced_directions).
+ *
+ * THE FUNCTION.  Problem b: diagrams X (n points) and Y (m points), fp64 (birth, death) rows in the packed layout of
+ * tlc_w2_partial_matching; N = n + m.  c(p) = |b + d| * 0.5 is the coordinate of the diagonal projection of point p (= the
+ * reference's sqrt(x**2 / 2) of x = (b + d) / sqrt 2, :111-115).  For direction l = (l0, l1):
+ *     V1 = [ l0 * b + l1 * d  of X's points in order ]  then  [ (l0 + l1) * c(y)  of Y's points in order ]        (N elements)
+ *     V2 = [ l0 * b + l1 * d  of Y's points in order ]  then  [ (l0 + l1) * c(x)  of X's points in order ]
+ * in plain fp64 multiplies and adds (no FMA).  Both lists are sorted ascending by IEEE < (-0.0 equals +0.0); equal keys keep their
+ * listing order (a stable sort).  loss[b] = sum over the directions i ascending, from +0.0, of  scale * r_i,  r_i = sum over the
+ * ranks k of |sort(V1)_k - sort(V2)_k|.  The order inside a rank sum is fixed per size class and depends on the ranks alone:
+ *     N <= TLC_SW_WAVE_NMAX:  the butterfly k ^ 1, k ^ 2, ... k ^ 32 over 64 ranks (absent ranks add +0.0);
+ *     N <= TLC_SW_LDS_NMAX:   thread t of 256 adds its ranks t, t + 256, ... ascending; the butterfly inside each wavefront of 64
+ *                             threads; the four wavefronts ascending;
+ *     above:                  tiles of 1 024 ranks, each summed like the class before; the tiles ascending.
+ * So loss(X, Y) and loss(Y, X) have the same bits.
+ *
+ * THE GRADIENT.  s_k = sign(sort(V1)_k - sort(V2)_k) in {-1, 0, 1}; sA[a] = the s at the rank that listing element a of V1
+ * received, sB[c] the same for V2.  Per direction i:  t_ic = scale * l_ic,  u_i = scale * ((l_i0 + l_i1) * 0.5);  sigma_j =
+ * sign(b_j + d_j) of X's point j (0 at 0), tau_j the same of Y's point j.  For point j of X and component c, from +0.0, over i
+ * ascending:   g += sA_i[j] * t_ic;      g -= sB_i[m + j] * sigma_j * u_i.
+ * For point j of Y:   g -= sB_i[j] * t_ic;      g += sA_i[n + j] * tau_j * u_i.
+ * One owner sums a point in that order; there is no floating-point atomic: the bits of a problem depend on its own inputs alone --
+ * not on the run, the batch around it or the workspace.  Under ties the loss is not differentiable and the stable order with
+ * sign(0) = 0 is the convention.
+ *
+ * Size classes by N, cut on the device: up to TLC_SW_WAVE_NMAX one wavefront per problem (the sort across lanes); up to
+ * TLC_SW_LDS_NMAX one workgroup per problem (both lists in LDS); above, the whole device, one problem after the other: the items of
+ * as many directions as d_work holds (and directions x N <= 2^27) are radix-sorted together with the segment number
+ * 2 * direction + list as the leading digit, sign bytes per (direction, listing position) go to d_work and one kernel sums each
+ * point's directions ascending.
+ *
+ * d_dirs float64[n_dirs, 2], 1 <= n_dirs <= TLC_SW_MAX_DIRS.  d_loss float64[B].  d_gradX float64[sum n, 2] / d_gradY
+ * float64[sum m, 2] (each may be NULL): every row of every problem is written.  d_status uint8[B]: 0 ok (n = 0 and / or m = 0 are
+ * ordinary problems; both empty: loss +0.0); 3 = a NaN / Inf coordinate, decided before any sort: loss NaN, gradients zero (the
+ * device-wide class does not skip its sorts for such a problem: their result is discarded).
+ * max_points: an upper bound of one problem's N.  The entry reads the offsets back once and synchronises the stream before it
+ * launches anything.
+ * tlc_sliced_w_work_bytes (host arithmetic; total_points = sum of N): the d_work that runs all directions of the largest problem at
+ * once; 0 (d_work may be NULL) when max_points <= TLC_SW_LDS_NMAX; -1 for a negative size or n_dirs out of range.  Any d_work of at
+ * least the size reported for ONE direction gives the same bits (the directions then go in groups).
+ * TLC_ERR_INVALID_ARG, nothing launched: negative sizes, null required pointers, n_dirs outside 1 .. TLC_SW_MAX_DIRS, a d_work below
+ * the size for one direction of max_points, offsets that decrease or a problem above max_points.  TLC_ERR_UNSUPPORTED: a problem above
+ * 2^27 points.  n_problems == 0: TLC_OK, nothing read. */
+#define TLC_SW_WAVE_NMAX  64
+#define TLC_SW_LDS_NMAX   2048
+#define TLC_SW_MAX_DIRS   128
+int64_t tlc_sliced_w_work_bytes(int32_t n_problems, int64_t total_points, int64_t max_points, int32_t n_dirs);
+int tlc_sliced_wasserstein(int32_t n_problems, const int64_t* d_xoff, const double* d_X, const int64_t* d_yoff, const double* d_Y,
+                           int32_t n_dirs, const double* d_dirs, double scale, int64_t max_points, double* d_loss, double* d_gradX,
+                           double* d_gradY, uint8_t* d_status, void* d_work, int64_t work_bytes, void* stream);
+
 /* ---- what `loss.backward()` runs through the PDGNN layer and the edge head ---------------------------
  * (Knowledge_Distillation/train_Teacher_Model.py:55-62 through gat_conv.py:113-216 and Teacher_model.py:53-59.)
  * tlc_gat_layer_bwd: gradients of one layer, same operands as tlc_gat_layer_fwd.  Nothing of the forward is kept: the node rows,

@@ -11,9 +11,10 @@ Training: with `compute_loss=True, kernel='wasserstein'`
 (`tlc_w2_partial_matching`; the reference calls POT's ot.emd on the host, wasserstein.py:303) and `loss.backward()` runs
 `tlc_edge_head_bwd` and `tlc_gat_layer_bwd` (autograd.py).  Train mode with dropout > 0 (the shipped script trains with dropout = 0,
 train_Teacher_Model.py:163): torch's F.dropout at the reference's five points (:58, :218-227), on tensors of the same shapes, so a seed
-draws the reference's masks; the edge head then runs unfused (the mask sits between its two GEMMs).  What is NOT here: the 'sliced'
-kernel (the reference's own branch cannot run: it ends in `return loss, ind_tmp_test, loss_xy, ...` with those names never bound,
-:110-123,137, and hands lists of CUDA tensors to scipy's cityblock) and draw_fig.  grad_PI=True (the signature's default; the
+draws the reference's masks; the edge head then runs unfused (the mask sits between its two GEMMs).  kernel='sliced_wasserstein' is the
+reference's 'sliced' branch as a device loss (`tlc_sliced_wasserstein`, any diagram size).  What is NOT here: kernel='sliced' under
+that name (the reference's own branch cannot run: it ends in `return loss, ind_tmp_test, loss_xy, ...` with those names never bound,
+:110-123,139, and hands lists of CUDA tensors to scipy's cityblock) and draw_fig.  grad_PI=True (the signature's default; the
 training script passes False, train_Teacher_Model.py:51): the image of the differentiable imager (pimg.py:354-400) with its gradient
 -- through the points' weights only, because the reference detaches the coordinates inside the normal-CDF factors (:392,395);
 `tlc_pi_raster_wgrad` (autograd.DiagramImage).
@@ -102,6 +103,9 @@ class Teacher_Model(torch.nn.Module):
         loss0 (differentiable), loss_xy0, loss_xd0, loss_yd0 like :63-66.  pair_diagonal=False (training, :64): every target
         point is matched, loss_yd0 is 0 (wasserstein.py:330-372, num_models=1); pair_diagonal=True (evaluation, :66): the
         distance in which both diagrams may use the diagonal, loss_yd0 = the targets left to it.
+        kernel='sliced_wasserstein': the reference's 'sliced' branch (:110-124, the sliced Wasserstein distance over M directions,
+        `tlc_sliced_wasserstein`) with the return repaired: loss0 differentiable, loss_xy0 / loss_xd0 / loss_yd0 zeros (the branch
+        computes no parts); p and pair_diagonal have no effect there.  kernel='sliced' itself (the signature's default) keeps raising.
 
         x0 [n,1] filtration, edge_index0 [2, m+n] with the n self loops LAST (train_Teacher_Model.py:43-44).
         Block-diagonal batches: pass graph_ptr (int64 [B+1] node offsets) and edge_ptr (int64 [B+1] offsets into the
@@ -112,9 +116,10 @@ class Teacher_Model(torch.nn.Module):
         """
         if draw_fig:
             raise NotImplementedError("Teacher_Model (HIP): draw_fig=False only")
-        if compute_loss and kernel != 'wasserstein':
-            raise NotImplementedError("Teacher_Model (HIP): compute_loss needs kernel='wasserstein' (the reference's 'sliced' branch cannot "
-                                      "run either: Teacher_model.py:110-123 ends in names that were never bound, :137)")
+        if compute_loss and kernel not in ('wasserstein', 'sliced_wasserstein'):
+            raise NotImplementedError("Teacher_Model (HIP): compute_loss needs kernel='wasserstein' or kernel='sliced_wasserstein' (the "
+                                      "reference's 'sliced' branch cannot run: Teacher_model.py:110-123 ends in names that were never "
+                                      "bound, :139; kernel='sliced_wasserstein' is that branch with the return repaired)")
         t1 = time.time()
         if not compute_loss and self._one_call_ok(x0, csr):
             # inference: the whole forward is one library call (tlc_pdgnn_forward: the same kernels, submitted natively)
@@ -162,9 +167,13 @@ class Teacher_Model(torch.nn.Module):
                 raise ValueError("Teacher_Model: PD has %d points for %d edges; pass pd_ptr (target offsets per graph)" % (int(PD.shape[0]), m))
             if pd_ptr is not None and (edge_ptr is None or pd_ptr.numel() != edge_ptr.numel()):
                 raise ValueError("Teacher_Model: pd_ptr needs edge_ptr with the same number of graphs")
-            parts = autograd.diagram_loss(x, PD.to(torch.float64), order=p, xoff=xoff, yoff=yoff, infer=bool(pair_diagonal))
-            loss0, loss_xy0, loss_xd0 = parts[0].sum().reshape(1), parts[1].sum().reshape(1), parts[2].sum().reshape(1)
-            loss_yd0 = parts[3].sum().reshape(1) if pair_diagonal else torch.zeros(1, dtype=loss0.dtype, device=loss0.device)
+            if kernel == 'sliced_wasserstein':                                                     # :110-124
+                loss0 = autograd.sliced_diagram_loss(x, PD.to(torch.float64), M=M, xoff=xoff, yoff=yoff).sum().reshape(1)
+                loss_xy0, loss_xd0, loss_yd0 = (torch.zeros(1, dtype=loss0.dtype, device=loss0.device) for _ in range(3))
+            else:
+                parts = autograd.diagram_loss(x, PD.to(torch.float64), order=p, xoff=xoff, yoff=yoff, infer=bool(pair_diagonal))
+                loss0, loss_xy0, loss_xd0 = parts[0].sum().reshape(1), parts[1].sum().reshape(1), parts[2].sum().reshape(1)
+                loss_yd0 = parts[3].sum().reshape(1) if pair_diagonal else torch.zeros(1, dtype=loss0.dtype, device=loss0.device)
         x0_out = x
         offs = torch.tensor([0, m], dtype=torch.int64, device=x.device) if edge_ptr is None else edge_ptr.to(torch.int64)
         if grad_PI:

@@ -33,6 +33,7 @@ PD_WIDE_MAX_ITEMS, PD_WIDE_FORCE_FALLBACK, PD_WIDE_BAD_INPUT_ROW, PD_WIDE_N_STAT
 PD_WIDE_LDS_NODES = 40000                                           # TLC_PD_WIDE_LDS_NODES: comp[] of the elder-rule passes in LDS up to here
 PD_WIDE_BLOCK, PD_WIDE_SORT_TILE, PD_WIDE_SCAN_CHUNK = 256, 4096, 2048   # workgroup width, edges per radix tile, flags per scan chunk (csrc/pd_wide.hip)
 PD_VERT_WAVE_NMAX, PD_VERT_LDS_NMAX = 64, 2048                       # TLC_PD_VERT_*: the size classes of csrc/pd_grad.hip (wavefront / workgroup per graph)
+SW_WAVE_NMAX, SW_LDS_NMAX, SW_MAX_DIRS = 64, 2048, 128              # TLC_SW_*: the size classes of csrc/sliced_w.hip by n + m, and the most directions
 DESCRIPTOR_FLAG ={"sum": 0, "min": DESC_MIN, "max": DESC_MAX}      # the three node values of filtration.build_fv
 
 # every symbol include/tlcgnn.h declares (tests check that the library exports all of them)
@@ -49,6 +50,7 @@ SYMBOLS = [
     "tlc_hks_batch", "tlc_hks_batch_work_bytes", "tlc_hks_large_batch", "tlc_hks_large_work_bytes", "tlc_struct_batch", "tlc_struct_batch_work_bytes",
     "tlc_ollivier_ricci_otd", "tlc_ollivier_ricci_otd_work_bytes", "tlc_pd_wide", "tlc_pd_wide_work_bytes",
     "tlc_pd_grad_work_bytes", "tlc_pd_point_vertices", "tlc_pd_filtration_grad",
+    "tlc_sliced_w_work_bytes", "tlc_sliced_wasserstein",
 ]
 
 
@@ -199,6 +201,10 @@ def lib():
         L.tlc_pd_grad_work_bytes.argtypes = [C.c_int64, C.c_int64, C.POINTER(C.c_int64)]
         L.tlc_pd_point_vertices.argtypes = [C.c_int64] + [C.c_void_p] * 14 + [C.c_int64, C.c_void_p]
         L.tlc_pd_filtration_grad.argtypes = [C.c_int64] + [C.c_void_p] * 14 + [C.c_int64, C.c_void_p]
+        L.tlc_sliced_w_work_bytes.argtypes = [C.c_int32, C.c_int64, C.c_int64, C.c_int32]
+        L.tlc_sliced_w_work_bytes.restype = C.c_int64
+        L.tlc_sliced_wasserstein.argtypes = ([C.c_int32] + [C.c_void_p] * 4 + [C.c_int32, C.c_void_p, C.c_double, C.c_int64] + [C.c_void_p] * 5
+                                             + [C.c_int64, C.c_void_p])
         L.tlc_debug_set_option.argtypes = [C.c_void_p, C.c_char_p, C.c_int]
         L.tlc_debug_dc_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.tlc_debug_tier_counts.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]

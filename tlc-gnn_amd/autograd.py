@@ -4,7 +4,7 @@
 classifier of Knowledge_Distillation/ConvCurv_GIN.py: CurvConv and NcLinear (nc_curv.hip).
 
 torch.autograd only carries the graph: every forward and every backward below is one C-ABI call (`tlc_gat_layer_fwd/_bwd`,
-`tlc_edge_head_fwd/_bwd`, `tlc_w2_partial_matching`, `tlc_pi_raster` / `tlc_pi_raster_wgrad`) or a few (`tlc_gemm_f32` /
+`tlc_edge_head_fwd/_bwd`, `tlc_w2_partial_matching`, `tlc_sliced_wasserstein`, `tlc_pi_raster` / `tlc_pi_raster_wgrad`) or a few (`tlc_gemm_f32` /
 `tlc_spmm_csr_f32` / `tlc_gemm_tn_f32`, `tlc_lp_decode_fused_f32` / `tlc_lp_decode_bwd_f32`); nothing is recomputed with torch ops
 and there is no CPU path.
 """
@@ -83,6 +83,34 @@ class DiagramLoss(torch.autograd.Function):
         cnt = xoff[1:] - xoff[:-1]
         per_point = torch.repeat_interleave(gloss.to(torch.float64), cnt)          # d total / d loss[b] for each predicted point
         return (grad * per_point.unsqueeze(1)).to(ctx.dtype), None, None, None, None, None
+
+
+class SlicedDiagramLoss(torch.autograd.Function):
+    """The sliced Wasserstein distance of one or more (predicted, target) diagram pairs (`compute_PD_loss(kernel='sliced')`,
+    Teacher_model.py:110-124; include/tlcgnn.h defines it) -> loss [B] in pd_hat's dtype.  One `tlc_sliced_wasserstein` call computes
+    the loss and the gradients of both diagrams; the reference's graph reaches the target too (through its projections), so `target`
+    gets its gradient when it requires one."""
+
+    @staticmethod
+    def forward(ctx, pd_hat, xoff, target, yoff, dirs, scale):
+        want = (("x",) if ctx.needs_input_grad[0] else ()) + (("y",) if ctx.needs_input_grad[2] else ())
+        r = ops.sliced_wasserstein(xoff, pd_hat.detach(), yoff, target.detach(), dirs=dirs, scale=scale, want_grad=want)
+        if bool((r["status"] != 0).any()):
+            raise ValueError("sliced diagram loss: status %s (3 = NaN / Inf coordinates)" % r["status"].tolist())
+        ctx.save_for_backward(xoff, yoff, r["grad_x"], r["grad_y"])
+        ctx.dtypes = (pd_hat.dtype, target.dtype)
+        return r["loss"].to(pd_hat.dtype)
+
+    @staticmethod
+    def backward(ctx, gloss):
+        xoff, yoff, gx, gy = ctx.saved_tensors
+        g64 = gloss.to(torch.float64)
+        out = [None, None]
+        for k, (offs, g) in enumerate(((xoff, gx), (yoff, gy))):
+            if g is not None:
+                per_point = torch.repeat_interleave(g64, offs[1:] - offs[:-1])   # d total / d loss[b] for each point of problem b
+                out[k] = (g * per_point.unsqueeze(1)).to(ctx.dtypes[k])
+        return out[0], None, out[1], None, None, None
 
 
 class DiagramImage(torch.autograd.Function):
@@ -181,6 +209,25 @@ def diagram_loss(pd_hat, target, order=2, xoff=None, yoff=None, infer=False):
     if yoff is None:
         yoff = torch.tensor([0, target.shape[0]], dtype=torch.int64, device=dev)
     return DiagramLoss.apply(pd_hat, xoff, target, yoff, int(order), bool(infer))
+
+
+def sliced_diagram_loss(pd_hat, target, M=50, xoff=None, yoff=None, dirs=None, scale=None):
+    """-> loss [B]: the sliced Wasserstein distance between the diagrams pd_hat and target of every problem, over the reference's M
+    directions (`ops.sliced_directions`) or over dirs float64[M, 2] with `scale`.  Differentiable in pd_hat and, when it requires
+    grad, in target; any diagram size.  A NaN / Inf coordinate raises ValueError."""
+    dev = pd_hat.device
+    if xoff is None:
+        xoff = torch.tensor([0, pd_hat.shape[0]], dtype=torch.int64, device=dev)
+    if yoff is None:
+        yoff = torch.tensor([0, target.shape[0]], dtype=torch.int64, device=dev)
+    if dirs is None:
+        d_np, step = ops.sliced_directions(M)
+        dirs = torch.from_numpy(d_np).to(dev)
+        if scale is None:
+            scale = step
+    elif scale is None:
+        raise ValueError("sliced_diagram_loss: dirs without a scale")
+    return SlicedDiagramLoss.apply(pd_hat, xoff, target, yoff, dirs, float(scale))
 
 
 class GcnLayer(torch.autograd.Function):

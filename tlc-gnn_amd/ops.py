@@ -728,6 +728,98 @@ def w2_inference_matching(xoff, X, yoff, Y, order=2, want_grad=False, max_points
                 grad=None if grad is None else grad[:nx], status=status[:B])
 
 
+def sliced_directions(M=50):
+    """The directions and the step of the reference's sliced loss, exactly as Knowledge_Distillation/Teacher_model.py:117-124 makes
+    them: theta starts at 0.5 and accumulates step = 1.0 / M; direction i is (float32(cos(theta pi)), float32(sin(theta pi))) -- the
+    FloatTensor of :120 -- widened to float64.  -> (float64[M, 2] numpy array, scale = step)."""
+    import numpy as np
+    M = int(M)
+    if M < 1:
+        raise ValueError("sliced_directions: M should be at least 1, not %d" % M)
+    dirs = np.empty((M, 2), dtype=np.float64)
+    theta = 0.5
+    step = 1.0 / M
+    for i in range(M):
+        dirs[i, 0] = np.float32(np.cos(theta * np.pi))
+        dirs[i, 1] = np.float32(np.sin(theta * np.pi))
+        theta += step
+    return dirs, step
+
+
+SLICED_W_WORK_CAP = 1 << 30     # what sliced_wasserstein allocates at most by default (unless one direction alone needs more)
+
+
+def sliced_w_work_bytes(n_problems, total_points, max_points, n_dirs):
+    """Bytes of workspace that run all n_dirs directions of the largest problem at once (tlc_sliced_w_work_bytes: host arithmetic);
+    0 when no problem has more than _lib.SW_LDS_NMAX points."""
+    need = _lib.lib().tlc_sliced_w_work_bytes(C.c_int32(int(n_problems)), C.c_int64(int(total_points)), C.c_int64(int(max_points)),
+                                              C.c_int32(int(n_dirs)))
+    if need < 0:
+        _lib.check(1, "tlc_sliced_w_work_bytes")                 # TLC_ERR_INVALID_ARG: the message is the library's
+    return int(need)
+
+
+@_lib.on_device_of
+def sliced_wasserstein(xoff, X, yoff, Y, dirs=None, scale=None, M=50, want_grad=("x",), work_bytes=None):
+    """The sliced Wasserstein distance (Teacher_model.py:110-124 `compute_PD_loss(kernel='sliced')`; include/tlcgnn.h defines it)
+    for a batch of diagram pairs of any size: xoff / yoff int64[B+1] offsets, X / Y float64[., 2] CUDA tensors.  dirs float64[M, 2]
+    and scale default to `sliced_directions(M)`.  want_grad: which of 'x', 'y' get a gradient.  work_bytes: the size of the workspace
+    of the problems above _lib.SW_LDS_NMAX points, allocated per call from torch's caching allocator (a training loop gets the same
+    block back): about 66 B x directions x points of the largest problem to sort all directions at once (290 MB for 88 650 points at
+    M = 50), at least the size of one direction; any size in between gives the same bits, in more launches.  None: all directions at
+    once up to SLICED_W_WORK_CAP bytes, beyond it the cap (or one direction, where that is larger).
+    -> dict(loss[B], grad_x[sum n, 2] or None, grad_y[sum m, 2] or None, status[B]: 0 ok, 3 = NaN / Inf coordinates)."""
+    import torch
+    B = xoff.numel() - 1
+    dev = X.device
+    xoff = xoff.to(torch.int64).contiguous()
+    yoff = yoff.to(torch.int64).contiguous()
+    if yoff.numel() != xoff.numel():
+        raise ValueError("sliced_wasserstein: xoff and yoff describe %d and %d problems" % (B, yoff.numel() - 1))
+    nx, ny = int(X.shape[0]), int(Y.shape[0])
+    max_points = total = 0
+    if B > 0:
+        # (offsets beyond the arrays would be read out of bounds on the device; one host read, with the sizes the entry wants)
+        cnt = (xoff[1:] - xoff[:-1]) + (yoff[1:] - yoff[:-1])
+        ends = torch.stack([xoff[-1], yoff[-1], cnt.max(), cnt.sum()]).tolist()
+        if ends[0] > nx or ends[1] > ny:
+            raise ValueError("sliced_wasserstein: offsets end at (%d, %d) but X / Y hold (%d, %d) points" % (ends[0], ends[1], nx, ny))
+        max_points, total = max(int(ends[2]), 0), max(int(ends[3]), 0)
+    _lib.require_gpu()
+    X = X.to(torch.float64).contiguous()
+    Y = Y.to(torch.float64).contiguous()
+    if dirs is None:
+        d_np, step = sliced_directions(M)
+        dirs = torch.from_numpy(d_np)
+        if scale is None:
+            scale = step
+    elif scale is None:
+        raise ValueError("sliced_wasserstein: dirs without a scale")
+    dirs = torch.as_tensor(dirs, dtype=torch.float64).to(dev).contiguous()
+    if dirs.dim() != 2 or dirs.shape[1] != 2:
+        raise ValueError("sliced_wasserstein: dirs should be [M, 2], not %s" % (tuple(dirs.shape),))
+    n_dirs = int(dirs.shape[0])
+    want = set(want_grad or ())
+    if not want <= {"x", "y"}:
+        raise ValueError("sliced_wasserstein: want_grad holds 'x' and / or 'y', not %r" % (want_grad,))
+    loss = torch.zeros(max(B, 1), dtype=torch.float64, device=dev)
+    gx = torch.zeros((max(nx, 1), 2), dtype=torch.float64, device=dev) if "x" in want else None
+    gy = torch.zeros((max(ny, 1), 2), dtype=torch.float64, device=dev) if "y" in want else None
+    status = torch.zeros(max(B, 1), dtype=torch.uint8, device=dev)
+    L = _lib.lib()
+    if work_bytes is None:
+        work_bytes = L.tlc_sliced_w_work_bytes(C.c_int32(B), C.c_int64(total), C.c_int64(max_points), C.c_int32(n_dirs))
+        work_bytes = max(int(work_bytes), 0)                    # (a refused n_dirs is reported by the call below)
+        if work_bytes > SLICED_W_WORK_CAP:
+            work_bytes = max(SLICED_W_WORK_CAP, int(L.tlc_sliced_w_work_bytes(C.c_int32(B), C.c_int64(total), C.c_int64(max_points), C.c_int32(1))))
+    work = torch.empty(int(work_bytes), dtype=torch.uint8, device=dev) if work_bytes > 0 else None
+    rc = L.tlc_sliced_wasserstein(C.c_int32(B), _lib.ptr(xoff), _lib.ptr(X) if nx else None, _lib.ptr(yoff), _lib.ptr(Y) if ny else None,
+                                  C.c_int32(n_dirs), _lib.ptr(dirs), C.c_double(float(scale)), C.c_int64(max_points), _lib.ptr(loss),
+                                  _lib.ptr(gx), _lib.ptr(gy), _lib.ptr(status), _lib.ptr(work), C.c_int64(int(work_bytes)), _lib.stream_ptr())
+    _lib.check(rc, "tlc_sliced_wasserstein")
+    return dict(loss=loss[:B], grad_x=None if gx is None else gx[:nx], grad_y=None if gy is None else gy[:ny], status=status[:B])
+
+
 def capture(fn, warmup=2):
     """HIP graph of a forward closure: `fn` (C-ABI launches on the current stream, outputs in caller-held or graph-pool buffers,
     no host synchronisation inside) is warmed up on a side stream, captured once, and replayed with `.replay()`.

@@ -1,7 +1,8 @@
 """Topological layers on a LEARNED filtration: the exact extended persistence of a packed batch of graphs as a differentiable
 function of the node values f, composed with the imager and the Wasserstein loss of `autograd`.
 
-    f (an MLP on node features, an HKS time, ...)  ->  diagrams(f, ...)  ->  images(...) / wasserstein_to(...)  ->  loss.backward()
+    f (an MLP on node features, an HKS time, ...)  ->  diagrams(f, ...)  ->  images(...) / wasserstein_to(...) /
+                                                       sliced_wasserstein_to(...)  ->  loss.backward()
 
 The diagrams are `engine.pd_from_filtration`'s with TLC_KEEP_ZERO_PERS (what `data_utils_GC.compute_persistence_image` computes),
 bit for bit; their gradient is the selection of `autograd.ExtendedPersistence`: each coordinate is a copy of one
@@ -60,3 +61,12 @@ def wasserstein_to(f, node_offs, edge_offs, edges, target_pts, target_offs, whic
     check_which(which)
     pts, offs = _select(f, node_offs, edge_offs, edges, which, pd_large)
     return autograd.diagram_loss(pts, target_pts.to(pts.dtype), order=order, xoff=offs, yoff=target_offs, infer=True)[0]
+
+
+def sliced_wasserstein_to(f, node_offs, edge_offs, edges, target_pts, target_offs, which="ord0+ext1", M=50, pd_large="host"):
+    """[B] sliced Wasserstein distances (`autograd.sliced_diagram_loss` over the reference's M directions) between every graph's
+    diagram `which` and the target diagrams target_pts [sum k, 2] / target_offs int64[B + 1]; differentiable in f (and in target_pts
+    when it requires grad).  The sibling of `wasserstein_to` without its cap of 4 096 points: sorts instead of an assignment."""
+    check_which(which)
+    pts, offs = _select(f, node_offs, edge_offs, edges, which, pd_large)
+    return autograd.sliced_diagram_loss(pts, target_pts.to(pts.dtype), M=M, xoff=offs, yoff=target_offs)
