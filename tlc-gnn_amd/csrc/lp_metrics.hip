@@ -19,7 +19,7 @@
 // Determinism: no floating-point atomics; the only atomics are LDS integer histogram counts.  The AP sum is a double-double
 // (TwoSum) reduction in an order fixed by the segment's length alone, so a segment gives the same bits alone or in a batch.
 #include "tlc_common.h"
-#include "radix_passes.h"   // RK_BS / RK_IPT / RK_TILE, block_excl_sum, the three kernels of a radix pass
+#include "radix_passes.h"   // RK_BS / RK_IPT / RK_TILE, block_excl_sum, rk_tiles, rk_sort
 
 namespace {
 
@@ -43,11 +43,8 @@ __device__ __forceinline__ uint32_t key_f32(float x, bool& nonfinite) {
     return ~asc;
 }
 __device__ __forceinline__ uint64_t key_f64(double x, bool& nonfinite) {
-    uint64_t u = (uint64_t)__double_as_longlong(x);
-    nonfinite |= (u & 0x7ff0000000000000ull) == 0x7ff0000000000000ull;
-    if (u == 0x8000000000000000ull) u = 0ull;
-    const uint64_t asc = (u & 0x8000000000000000ull) ? ~u : (u | 0x8000000000000000ull);
-    return ~asc;
+    nonfinite |= ((uint64_t)__double_as_longlong(x) & 0x7ff0000000000000ull) == 0x7ff0000000000000ull;
+    return ~tlc_ord_f64(x);
 }
 template <typename K>
 __device__ __forceinline__ K load_key(const void* scores, int sdt, long long i, bool& nonfinite) {
@@ -384,15 +381,15 @@ struct RadixLayout {
     long long keys_a, keys_b, labs_a, labs_b, hist, tot, flags, tpos, tstart, ccp, cst, tw, tap, info, bytes;
 };
 RadixLayout radix_layout(long long n, int key_bytes) {
-    const long long nb = (n + RK_TILE - 1) / RK_TILE;
+    const long long nb = rk_tiles(n);
     RadixLayout L;
     long long o = 0;
     L.keys_a = o; o += rk_align(n * key_bytes);
     L.keys_b = o; o += rk_align(n * key_bytes);
     L.labs_a = o; o += rk_align(n);
     L.labs_b = o; o += rk_align(n);
-    L.hist = o; o += rk_align(256 * nb * 4);
-    L.tot = o; o += rk_align(256 * 4);
+    L.hist = o; o += rk_align(rk_hist_ints(n) * 4);
+    L.tot = o; o += rk_align(RK_TOT_INTS * 4);
     L.flags = o; o += rk_align(nb * 4);
     L.tpos = o; o += rk_align(nb * 8);
     L.tstart = o; o += rk_align(nb * 8);
@@ -427,7 +424,7 @@ template <typename K>
 int radix_segment(const void* scores, int sdt, const void* labels, int ldt, long long beg, long long n, int s, char* work, double* auc,
                   double* ap, long long* n_pos, long long* n_neg, int* status, hipStream_t st) {
     const RadixLayout L = radix_layout(n, sizeof(K));
-    const int nb = (int)((n + RK_TILE - 1) / RK_TILE);
+    const int nb = (int)rk_tiles(n);
     K* ka = (K*)(work + L.keys_a);
     K* kb = (K*)(work + L.keys_b);
     uint8_t* la = (uint8_t*)(work + L.labs_a);
@@ -439,13 +436,7 @@ int radix_segment(const void* scores, int sdt, const void* labels, int ldt, long
               *cst = (long long*)(work + L.cst), *tw = (long long*)(work + L.tw), *info = (long long*)(work + L.info);
     double* tap = (double*)(work + L.tap);
     hipLaunchKernelGGL(rk_keys_kernel<K>, dim3(nb), dim3(RK_BS), 0, st, scores, sdt, labels, ldt, beg, n, ka, la, fl);
-    for (int shift = 0; shift < (int)(8 * sizeof(K)); shift += 8) {
-        hipLaunchKernelGGL(rk_hist_kernel<K>, dim3(nb), dim3(RK_BS), 0, st, ka, n, shift, hist);
-        hipLaunchKernelGGL(rk_scan_rows_kernel, dim3(256), dim3(RK_BS), 0, st, hist, nb, tot);
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(rk_scatter_kernel<K, uint8_t>), dim3(nb), dim3(RK_BS), 0, st, ka, la, kb, lb, n, shift, hist, tot);
-        K* tk = ka; ka = kb; kb = tk;
-        uint8_t* tl = la; la = lb; lb = tl;
-    }
+    rk_sort<8 * sizeof(K)>(st, n, ka, kb, la, lb, hist, tot);      // (a forced segment of one score: nothing to sort)
     hipLaunchKernelGGL(rk_tile_summary_kernel<K>, dim3(nb), dim3(RK_BS), 0, st, ka, la, n, tpos, tstart);
     hipLaunchKernelGGL(rk_tile_scan_kernel, dim3(1), dim3(RK_SCAN_BS), 0, st, nb, tpos, tstart, fl, ccp, cst, info);
     hipLaunchKernelGGL(rk_tile_reduce_kernel<K>, dim3(nb), dim3(RK_BS), 0, st, ka, la, n, ccp, cst, tw, tap);

@@ -40,12 +40,6 @@ static_assert(PDG_BS == RK_BS, "the radix passes and the kernels here share one 
 static_assert(PDG_WAVE_N == 64, "one lane per node");
 static_assert((PDG_LDS_N & (PDG_LDS_N - 1)) == 0, "the bitonic network sorts a power of two");
 
-__device__ __forceinline__ unsigned long long ord_f64(double x) {
-    unsigned long long u = (unsigned long long)__double_as_longlong(x);
-    if (u == 0x8000000000000000ull) u = 0ull;                      // -0.0 == +0.0
-    return (u & 0x8000000000000000ull) ? ~u : (u | 0x8000000000000000ull);
-}
-
 // what the offsets and the counts row say about graph g
 struct Shape {
     long long no, eo, n, m;
@@ -185,7 +179,7 @@ __device__ __forceinline__ int lower_bound_u64(KeyPtr key, int n, unsigned long 
 template <typename KeyPtr, typename IdPtr>
 __device__ __forceinline__ int find_vertex(KeyPtr key, IdPtr vid, int n, double c) {
     if (c != c) return -1;
-    const unsigned long long kc = ord_f64(c);
+    const unsigned long long kc = tlc_ord_f64(c);
     const int p = lower_bound_u64(key, n, kc);
     return (p < n && key[p] == kc) ? (int)vid[p] : -1;
 }
@@ -214,7 +208,7 @@ __global__ __launch_bounds__(PDG_BS) void pdg_lds_vertices_kernel(VertArgs A) {
         int P = 128;
         while (P < n) P <<= 1;
         for (int i = tid; i < P; i += PDG_BS) {
-            key[i] = i < n ? ord_f64(A.f[s.no + i]) : ~0ull;
+            key[i] = i < n ? tlc_ord_f64(A.f[s.no + i]) : ~0ull;
             vid[i] = i < n ? (unsigned)i : PDG_NOID;
         }
         if (tid == 0) sbad = 0;
@@ -315,7 +309,7 @@ __global__ __launch_bounds__(PDG_BS) void pdgw_keys_kernel(const int* __restrict
                                                            unsigned long long* __restrict__ key, unsigned* __restrict__ val) {
     if (ctl[W_STATUS] != TLC_ST_OK) return;
     PDG_FOR(v, n) {
-        key[v] = ord_f64(f[v]);
+        key[v] = tlc_ord_f64(f[v]);
         val[v] = (unsigned)v;
     }
 }
@@ -389,18 +383,13 @@ struct WLay {
 // workspace of one graph of the third class: the forward sorts n (u64 key, u32 id) pairs, the backward T = 4 n + 2 m + 2 (u32, u32)
 WLay wlayout(long long n, long long m) {
     WLay L;
-    size_t o = 0;
-    auto take = [&](long long count, size_t size) {
-        const size_t at = o;
-        o += (((size_t)(count + 1) * size) + 255) & ~(size_t)255;
-        return at;
-    };
-    const long long T = 4 * n + 2 * m + 2, nb = (T + RK_TILE - 1) / RK_TILE;
-    L.ctl = take(W_INTS, 4);
-    L.key_a = take(T, 4); L.key_b = take(T, 4);          // 4 T >= 8 n bytes: room for the forward's u64 keys
-    L.val_a = take(T, 4); L.val_b = take(T, 4);
-    L.hist = take(256 * nb, 4); L.tot = take(256, 4);
-    L.bytes = o + 256;                                    // room to align the caller's pointer
+    TlcCarver W;
+    const long long T = 4 * n + 2 * m + 2;
+    L.ctl = W.take(W_INTS, 4);
+    L.key_a = W.take(T, 4); L.key_b = W.take(T, 4);      // 4 T >= 8 n bytes: room for the forward's u64 keys
+    L.val_a = W.take(T, 4); L.val_b = W.take(T, 4);
+    L.hist = W.take(rk_hist_ints(T), 4); L.tot = W.take(RK_TOT_INTS, 4);
+    L.bytes = W.bytes();
     return L;
 }
 long long work_need(long long max_nodes, long long max_edges) {
@@ -410,22 +399,7 @@ long long work_need(long long max_nodes, long long max_edges) {
     const long long m = max_edges < TLC_PD_WIDE_MAX_ITEMS - n ? max_edges : TLC_PD_WIDE_MAX_ITEMS - n;
     return (long long)wlayout(n, m).bytes;
 }
-unsigned grid_for(long long count) {
-    const long long b = (count + PDG_BS - 1) / PDG_BS;
-    return (unsigned)(b < 1 ? 1 : b > PDG_MAX_GRID ? PDG_MAX_GRID : b);
-}
-template <typename K>
-void sort_pairs(hipStream_t st, long long n, int bits, K* ka, K* kb, unsigned* va, unsigned* vb, int* hist, int* tot) {
-    if (n < 2) return;
-    const unsigned nb = (unsigned)((n + RK_TILE - 1) / RK_TILE);
-    for (int shift = 0; shift < bits; shift += 8) {        // an even number of passes: the result is back in ka / va
-        hipLaunchKernelGGL(rk_hist_kernel<K>, dim3(nb), dim3(RK_BS), 0, st, ka, n, shift, hist);
-        hipLaunchKernelGGL(rk_scan_rows_kernel, dim3(256), dim3(RK_BS), 0, st, hist, (int)nb, tot);
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(rk_scatter_kernel<K, unsigned>), dim3(nb), dim3(RK_BS), 0, st, ka, va, kb, vb, n, shift, hist, tot);
-        K* tk = ka; ka = kb; kb = tk;
-        unsigned* tv = va; va = vb; vb = tv;
-    }
-}
+unsigned pdg_grid(long long count) { return tlc_grid_for(count, PDG_BS, PDG_MAX_GRID); }
 
 // The offsets of the batch on the host, and what they say about the classes.  large[]: the graphs of the third class that the device
 // may compute (offsets in order, n + m within the limit); the device decides on the counts.
@@ -478,10 +452,6 @@ int check_sizes(const char* who, int64_t n_graphs, const void* d_work, int64_t w
     }
     return TLC_OK;
 }
-char* aligned(void* d_work) {
-    char* w = (char*)d_work;
-    return w + ((256 - ((uintptr_t)w & 255)) & 255);
-}
 
 }  // namespace
 
@@ -506,9 +476,9 @@ extern "C" int tlc_pd_point_vertices(int64_t n_graphs, const int64_t* d_node_off
     if ((rc = check_work(__func__, H, n_graphs, work_bytes)) != TLC_OK) return rc;
     const VertArgs A{n_graphs, d_node_offs, d_edge_offs, d_f, d_pd_up, d_pd_down, d_pd_one, d_ext0, d_counts,
                      d_vert_up, d_vert_down, d_vert_one, d_vert_ext0, d_status};
-    hipLaunchKernelGGL(pdg_wave_vertices_kernel, dim3(grid_for(n_graphs * 64)), dim3(PDG_BS), 0, st, A);
+    hipLaunchKernelGGL(pdg_wave_vertices_kernel, dim3(pdg_grid(n_graphs * 64)), dim3(PDG_BS), 0, st, A);
     if (H.n_lds) hipLaunchKernelGGL(pdg_lds_vertices_kernel, dim3((unsigned)(n_graphs < PDG_MAX_GRID ? n_graphs : PDG_MAX_GRID)), dim3(PDG_BS), 0, st, A);
-    char* w = H.n_large ? aligned(d_work) : nullptr;
+    char* w = H.n_large ? tlc_align256(d_work) : nullptr;
     for (long long i = 0; i < H.n_large; ++i) {
         const long long g = H.large[i], no = H.offs[g], eo = H.offs[n_graphs + 1 + g];
         const long long n = H.offs[g + 1] - no, m = H.offs[n_graphs + 1 + g + 1] - eo;
@@ -517,9 +487,9 @@ extern "C" int tlc_pd_point_vertices(int64_t n_graphs, const int64_t* d_node_off
         unsigned long long *key_a = (unsigned long long*)(w + L.key_a), *key_b = (unsigned long long*)(w + L.key_b);
         unsigned *val_a = (unsigned*)(w + L.val_a), *val_b = (unsigned*)(w + L.val_b);
         hipLaunchKernelGGL(pdgw_ctl_kernel, dim3(1), dim3(64), 0, st, ctl, d_node_offs, d_edge_offs, d_counts, (const uint8_t*)nullptr, g);
-        hipLaunchKernelGGL(pdgw_keys_kernel, dim3(grid_for(n)), dim3(PDG_BS), 0, st, ctl, n, d_f + no, key_a, val_a);
-        sort_pairs<unsigned long long>(st, n, 64, key_a, key_b, val_a, val_b, (int*)(w + L.hist), (int*)(w + L.tot));
-        hipLaunchKernelGGL(pdgw_search_kernel, dim3(grid_for(4 * n + 2 * m + 2)), dim3(PDG_BS), 0, st, ctl, n, m, key_a, val_a, d_pd_up + 2 * no,
+        hipLaunchKernelGGL(pdgw_keys_kernel, dim3(pdg_grid(n)), dim3(PDG_BS), 0, st, ctl, n, d_f + no, key_a, val_a);
+        rk_sort<64>(st, n, key_a, key_b, val_a, val_b, (int*)(w + L.hist), (int*)(w + L.tot));
+        hipLaunchKernelGGL(pdgw_search_kernel, dim3(pdg_grid(4 * n + 2 * m + 2)), dim3(PDG_BS), 0, st, ctl, n, m, key_a, val_a, d_pd_up + 2 * no,
                            d_pd_down + 2 * no, d_pd_one + 2 * eo, d_ext0 + 2 * g, d_vert_up + 2 * no, d_vert_down + 2 * no,
                            d_vert_one + 2 * eo, d_vert_ext0 + 2 * g);
         hipLaunchKernelGGL(pdgw_status_kernel, dim3(1), dim3(64), 0, st, ctl, d_status + g);
@@ -543,9 +513,9 @@ extern "C" int tlc_pd_filtration_grad(int64_t n_graphs, const int64_t* d_node_of
     if ((rc = check_work(__func__, H, n_graphs, work_bytes)) != TLC_OK) return rc;
     const GradArgs A{n_graphs, d_node_offs, d_edge_offs, d_counts, d_vert_up, d_vert_down, d_vert_one, d_vert_ext0,
                      d_g_up, d_g_down, d_g_one, d_g_ext0, d_status, d_grad_f};
-    hipLaunchKernelGGL(pdg_wave_grad_kernel, dim3(grid_for(n_graphs * 64)), dim3(PDG_BS), 0, st, A);
+    hipLaunchKernelGGL(pdg_wave_grad_kernel, dim3(pdg_grid(n_graphs * 64)), dim3(PDG_BS), 0, st, A);
     if (H.n_lds) hipLaunchKernelGGL(pdg_lds_grad_kernel, dim3((unsigned)(n_graphs < PDG_MAX_GRID ? n_graphs : PDG_MAX_GRID)), dim3(PDG_BS), 0, st, A);
-    char* w = H.n_large ? aligned(d_work) : nullptr;
+    char* w = H.n_large ? tlc_align256(d_work) : nullptr;
     for (long long i = 0; i < H.n_large; ++i) {
         const long long g = H.large[i], no = H.offs[g], eo = H.offs[n_graphs + 1 + g];
         const long long n = H.offs[g + 1] - no, m = H.offs[n_graphs + 1 + g + 1] - eo, T = 4 * n + 2 * m + 2;
@@ -554,10 +524,10 @@ extern "C" int tlc_pd_filtration_grad(int64_t n_graphs, const int64_t* d_node_of
         unsigned *key_a = (unsigned*)(w + L.key_a), *key_b = (unsigned*)(w + L.key_b);
         unsigned *val_a = (unsigned*)(w + L.val_a), *val_b = (unsigned*)(w + L.val_b);
         hipLaunchKernelGGL(pdgw_ctl_kernel, dim3(1), dim3(64), 0, st, ctl, d_node_offs, d_edge_offs, d_counts, d_status, g);
-        hipLaunchKernelGGL(pdgw_items_kernel, dim3(grid_for(T)), dim3(PDG_BS), 0, st, ctl, n, m, d_vert_up + 2 * no, d_vert_down + 2 * no,
+        hipLaunchKernelGGL(pdgw_items_kernel, dim3(pdg_grid(T)), dim3(PDG_BS), 0, st, ctl, n, m, d_vert_up + 2 * no, d_vert_down + 2 * no,
                            d_vert_one + 2 * eo, d_vert_ext0 + 2 * g, key_a, val_a);
-        sort_pairs<unsigned>(st, T, 32, key_a, key_b, val_a, val_b, (int*)(w + L.hist), (int*)(w + L.tot));
-        hipLaunchKernelGGL(pdgw_sum_kernel, dim3(grid_for(n)), dim3(PDG_BS), 0, st, ctl, n, m, key_a, val_a, d_g_up ? d_g_up + 2 * no : nullptr,
+        rk_sort<32>(st, T, key_a, key_b, val_a, val_b, (int*)(w + L.hist), (int*)(w + L.tot));
+        hipLaunchKernelGGL(pdgw_sum_kernel, dim3(pdg_grid(n)), dim3(PDG_BS), 0, st, ctl, n, m, key_a, val_a, d_g_up ? d_g_up + 2 * no : nullptr,
                            d_g_down ? d_g_down + 2 * no : nullptr, d_g_one ? d_g_one + 2 * eo : nullptr,
                            d_g_ext0 ? d_g_ext0 + 2 * g : nullptr, d_grad_f + no);
     }

@@ -20,6 +20,7 @@
 // converges to the same minimum by monotonicity of fp64 addition.  Compile with -ffp-contract=off.
 #include "tlc_common.h"
 #include "tlc_kernels.h"
+#include "pd_keys.h"
 
 #define TLC_INF_BITS 0x7FF0000000000000ull
 // diagnostics (make PHASE_DEBUG=1; tools/phase_profile.py): accumulate the cycles thread 0 spent since the previous stamp
@@ -204,19 +205,10 @@ __device__ __forceinline__ double block_min(double v, double* red) {
 }
 
 // monotone map double -> u64 (ascending); ~key gives descending order
+// (not tlc_ord_f64: this one keeps -0.0 below +0.0, and the tie order of the tier kernels depends on that)
 __device__ __forceinline__ ull f64_key(double x) {
     const ull b = (ull)__double_as_longlong(x);
     return b ^ ((b >> 63) ? ~0ull : (1ull << 63));
-}
-
-// perturb_filter_function (accelerated_PD.py:18-21); evaluated in exactly this association, no FMA
-__device__ __forceinline__ double key_asc(double fa, double fb) {
-    const double hi = fa > fb ? fa : fb, lo = fa < fb ? fa : fb;
-    return hi + (lo + 1.0) * 1e-6;
-}
-__device__ __forceinline__ double key_desc(double fa, double fb) {
-    const double hi = fa > fb ? fa : fb, lo = fa < fb ? fa : fb;
-    return lo - (101.0 - hi) * 1e-6;
 }
 
 // ---- Bellman-Ford over the directed entries: dist = min over paths of the fp64 sum accumulated from the source --
@@ -523,7 +515,7 @@ __device__ __forceinline__ void sort_edges(Mem<idx_t>& M, int m) {
         if (e < m) {
             const unsigned ab = M.dir[e];
             const double flo = M.f[ab >> 16], fhi = M.f[ab & 0xffffu];
-            M.keyS[e] = DESC ? ~f64_key(key_desc(flo, fhi)) : f64_key(key_asc(flo, fhi));
+            M.keyS[e] = DESC ? ~f64_key(tlc_key_desc(flo, fhi)) : f64_key(tlc_key_asc(flo, fhi));
         } else {
             M.keyS[e] = ~0ull;
         }

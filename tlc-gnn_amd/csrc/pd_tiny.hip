@@ -18,6 +18,7 @@
 // path only (flags == 0, res == 5): every variant flag goes through the wavefront kernels.  Compile with -ffp-contract=off.
 #include "tlc_common.h"
 #include "tlc_kernels.h"
+#include "pd_keys.h"
 
 namespace {
 
@@ -38,15 +39,6 @@ struct LaneBytes8Slice {
     int off;
     __device__ __forceinline__ unsigned char& operator[](int j) const { return b[off + j]; }
 };
-
-__device__ __forceinline__ double tiny_key_asc(double fa, double fb) {
-    const double hi = fa > fb ? fa : fb, lo = fa < fb ? fa : fb;
-    return hi + (lo + 1.0) * 1e-6;
-}
-__device__ __forceinline__ double tiny_key_desc(double fa, double fb) {
-    const double hi = fa > fb ? fa : fb, lo = fa < fb ? fa : fb;
-    return lo - (101.0 - hi) * 1e-6;
-}
 
 // _norm_cdf on |x| <= 1.2 (all the image stage of a normalised filtration asks for): the 19-term Maclaurin series of erf used by
 // the tier kernels (pd_pipeline.hip, tlc_norm_cdf<true>), same coefficients
@@ -293,7 +285,7 @@ __device__ __forceinline__ void tiny_slot(const TlcPdParams p, unsigned char* ld
         if (status == TLC_ST_OK) {
             // ---- P6 + P7 ascending pass (:27-68): an edge's key exceeds both endpoints' values, so every node is made
             // before any of its edges: only the edges need sorting (stable insertion sort: equal keys keep list order)
-            for (int e = 0; e < m; ++e) { const unsigned ab = eab[e]; key[e] = tiny_key_asc(f[ab >> 8], f[ab & 0xffu]); }
+            for (int e = 0; e < m; ++e) { const unsigned ab = eab[e]; key[e] = tlc_key_asc(f[ab >> 8], f[ab & 0xffu]); }
             for (int e = 0; e < m; ++e) {                  // stable: position = #smaller keys + #equal keys in front
                 const double k = key[e];
                 int r = 0;
@@ -325,7 +317,7 @@ __device__ __forceinline__ void tiny_slot(const TlcPdParams p, unsigned char* ld
             TINY_STAMP(2);
             ptb[npts] = (unsigned char)imin; ptd[npts] = (unsigned char)imax; ++npts;            // [min, max] (:110); [max, min] weighs 0
             // ---- descending pass (:70-109): value descending, stable; Rel1 points weigh 0 in the image ------------------------
-            for (int e = 0; e < m; ++e) { const unsigned ab = eab[e]; key[e] = tiny_key_desc(f[ab >> 8], f[ab & 0xffu]); }
+            for (int e = 0; e < m; ++e) { const unsigned ab = eab[e]; key[e] = tlc_key_desc(f[ab >> 8], f[ab & 0xffu]); }
             for (int e = 0; e < m; ++e) {                  // descending, stable
                 const double k = key[e];
                 int r = 0;
@@ -365,7 +357,7 @@ __device__ __forceinline__ void tiny_slot(const TlcPdParams p, unsigned char* ld
                     }
                     if (!ch) break;
                 }
-                for (int e = 0; e < m; ++e) { const unsigned ab = eab[e]; key[e] = tiny_key_asc(f[ab >> 8], f[ab & 0xffu]); }
+                for (int e = 0; e < m; ++e) { const unsigned ab = eab[e]; key[e] = tlc_key_asc(f[ab >> 8], f[ab & 0xffu]); }
                 for (int t = 0; t < npos; ++t) {
                     const int e = pn[t];
                     const unsigned ab = eab[e];

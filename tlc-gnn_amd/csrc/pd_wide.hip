@@ -24,6 +24,7 @@
 // The host loops are bounded by m alone: ceil(log2 m) levels, ceil(log2 V) rounds per forest; a device flag per round and the
 // device's level count make the surplus launches return at once, so there is no host synchronisation inside or between graphs.
 #include "radix_passes.h"
+#include "pd_keys.h"
 
 #include <limits.h>
 
@@ -55,21 +56,6 @@ __device__ __forceinline__ bool closed(const Gate g) { return g.ctl[C_STATUS] !=
 
 #define PDW_FOR(i, count) for (int i = (int)(blockIdx.x * PDW_BS + threadIdx.x); i < (count); i += (int)(gridDim.x * PDW_BS))
 
-__device__ __forceinline__ unsigned long long ord_f64(double x) {
-    unsigned long long u = (unsigned long long)__double_as_longlong(x);
-    if (u == 0x8000000000000000ull) u = 0ull;
-    return (u & 0x8000000000000000ull) ? ~u : (u | 0x8000000000000000ull);
-}
-// perturb_filter_function (accelerated_PD.py:16-22): two roundings each, never a fused multiply-add
-__device__ __forceinline__ double asc_key(double fa, double fb) {
-    const double hi = fa > fb ? fa : fb, lo = fa < fb ? fa : fb;
-    return __dadd_rn(hi, __dmul_rn(__dadd_rn(lo, 1.0), 1e-6));
-}
-__device__ __forceinline__ double desc_key(double fa, double fb) {
-    const double hi = fa > fb ? fa : fb, lo = fa < fb ? fa : fb;
-    return __dsub_rn(lo, __dmul_rn(__dsub_rn(101.0, hi), 1e-6));
-}
-
 __global__ __launch_bounds__(PDW_BS) void pdw_ctl_kernel(int* __restrict__ ctl, int n, int m) {
     if (threadIdx.x < C_INTS) ctl[threadIdx.x] = threadIdx.x == C_N ? n : threadIdx.x == C_M ? m : threadIdx.x == C_MINID ? INT_MAX : 0;
 }
@@ -87,7 +73,7 @@ __global__ __launch_bounds__(PDW_BS) void pdw_keys_kernel(int* __restrict__ ctl,
             // differs from the edges-only one sorted here -- refused, not answered differently
             const double fu = f[u], fv = f[v];
             if (!(fu >= -1.0 && fu <= 101.0 && fv >= -1.0 && fv <= 101.0)) ctl[C_STATUS] = TLC_ST_BAD_INPUT;
-            k = ord_f64(asc_key(fu, fv));
+            k = tlc_ord_f64(tlc_key_asc(fu, fv));
         }
         key[e] = k;
         val[e] = (unsigned)e;
@@ -103,7 +89,7 @@ __global__ __launch_bounds__(PDW_BS) void pdw_asc_rank_kernel(const int* __restr
         const int e = (int)sorted[r];
         ra[e] = r;
         aperm[r] = e;
-        key[m - 1 - r] = ~ord_f64(desc_key(f[edges[2 * e]], f[edges[2 * e + 1]]));
+        key[m - 1 - r] = ~tlc_ord_f64(tlc_key_desc(f[edges[2 * e]], f[edges[2 * e + 1]]));
         val[m - 1 - r] = (unsigned)e;
     }
 }
@@ -121,9 +107,9 @@ __global__ __launch_bounds__(PDW_BS) void pdw_root_kernel(int* __restrict__ ctl,
                                                           const double* __restrict__ f, const int* __restrict__ dperm) {
     if (ctl[C_STATUS]) return;
     const int e0 = dperm[0];
-    const unsigned long long k0 = ord_f64(desc_key(f[edges[2 * e0]], f[edges[2 * e0 + 1]]));
+    const unsigned long long k0 = tlc_ord_f64(tlc_key_desc(f[edges[2 * e0]], f[edges[2 * e0 + 1]]));
     PDW_FOR(e, m)
-        if (ord_f64(desc_key(f[edges[2 * e]], f[edges[2 * e + 1]])) == k0) atomicMin(&ctl[C_MINID], e);
+        if (tlc_ord_f64(tlc_key_desc(f[edges[2 * e]], f[edges[2 * e + 1]])) == k0) atomicMin(&ctl[C_MINID], e);
 }
 
 // ---- exclusive prefix sum of byte flags -------------------------------------------------------------------------------------
@@ -559,12 +545,12 @@ __global__ __launch_bounds__(PDW_BS) void pdw_fallback_kernel(int* __restrict__ 
         double best_val = 0;
         for (int a = p; a != meet; a = parent[a]) {
             const int t = pedge[a];
-            const double val = asc_key(f[edges[2 * t]], f[edges[2 * t + 1]]);
+            const double val = tlc_key_asc(f[edges[2 * t]], f[edges[2 * t + 1]]);
             if (best < 0 || val > best_val) { best = a; best_val = val; side = 0; }
         }
         for (int a = q; a != meet; a = parent[a]) {
             const int t = pedge[a];
-            const double val = asc_key(f[edges[2 * t]], f[edges[2 * t + 1]]);
+            const double val = tlc_key_asc(f[edges[2 * t]], f[edges[2 * t + 1]]);
             if (best < 0 || val > best_val) { best = a; best_val = val; side = 1; }
         }
         if (best < 0) continue;
@@ -638,31 +624,27 @@ struct Lay {
 };
 Lay layout(long long n, long long m) {
     Lay L;
-    size_t o = 0;
-    auto take = [&](long long count, size_t size) {
-        const size_t at = o;
-        o += (((size_t)(count + 1) * size) + 255) & ~(size_t)255;
-        return at;
-    };
-    const long long idcap = n > 4 * m + 4 ? n : 4 * m + 4, n2 = 2 * idcap, nb = (m + RK_TILE - 1) / RK_TILE;
+    TlcCarver W;
+    const long long idcap = n > 4 * m + 4 ? n : 4 * m + 4, n2 = 2 * idcap;
     L.idcap = idcap;
-    L.ctl = take(C_INTS, 4);
-    L.key_a = take(m, 8); L.key_b = take(m, 8); L.val_a = take(m, 4); L.val_b = take(m, 4);
-    L.hist = take(256 * nb, 4); L.tot = take(256, 4);
-    L.ra = take(m, 4); L.rd = take(m, 4); L.aperm = take(m, 4); L.dperm = take(m, 4);
-    L.in_final = take(m, 1); L.is_neg = take(m, 1); L.tmid = take(2 * m, 1); L.tree2 = take(2 * m, 1);
-    L.f_pos = take(m, 1); L.f_q = take(m, 1); L.f_dy = take(m, 1); L.f_fin = take(m, 1); L.f_pt = take(m, 1);
-    L.pos_idx = take(m, 4); L.q_idx = take(m, 4); L.d_idx = take(m, 4); L.fin_idx = take(m, 4); L.pt_idx = take(m, 4);
-    L.used = take(n2, 1); L.ren = take(n2, 4);
-    L.sums = take((n2 > m ? n2 : m) / PDW_SCAN_CHUNK + 2, 4);
-    L.t_up = take(n, 4); L.t_down = take(n, 4); L.comp_up = take(n, 4); L.comp_down = take(n, 4); L.lab = take(n, 4);
-    L.par = take(n2, 4); L.hk = take(n2, 4); L.best = take(n2, 8);
-    L.ia = take(2 * m, 4); L.ib = take(2 * m, 4); L.iw = take(2 * m, 4);
-    L.pa = take(m, 4); L.pb = take(m, 4); L.pseg = take(m, 4); L.pe = take(m, 4); L.qofp = take(m, 4); L.pw = take(m, 4); L.qw = take(m, 4);
-    L.qa = take(m, 4); L.qb = take(m, 4); L.qseg = take(m, 4); L.qe = take(m, 4); L.qalive = take(m, 1);
-    L.cnt = take(m, 4); L.rem = take(m, 4); L.rem_e = take(m, 4);
-    L.fb = take(7 * n + 8, 4);
-    L.bytes = o + 256;      // room to align the caller's pointer
+    L.ctl = W.take(C_INTS, 4);
+    L.key_a = W.take(m, 8); L.key_b = W.take(m, 8); L.val_a = W.take(m, 4); L.val_b = W.take(m, 4);
+    L.hist = W.take(rk_hist_ints(m), 4); L.tot = W.take(RK_TOT_INTS, 4);
+    L.ra = W.take(m, 4); L.rd = W.take(m, 4); L.aperm = W.take(m, 4); L.dperm = W.take(m, 4);
+    L.in_final = W.take(m, 1); L.is_neg = W.take(m, 1); L.tmid = W.take(2 * m, 1); L.tree2 = W.take(2 * m, 1);
+    L.f_pos = W.take(m, 1); L.f_q = W.take(m, 1); L.f_dy = W.take(m, 1); L.f_fin = W.take(m, 1); L.f_pt = W.take(m, 1);
+    L.pos_idx = W.take(m, 4); L.q_idx = W.take(m, 4); L.d_idx = W.take(m, 4); L.fin_idx = W.take(m, 4); L.pt_idx = W.take(m, 4);
+    L.used = W.take(n2, 1); L.ren = W.take(n2, 4);
+    L.sums = W.take((n2 > m ? n2 : m) / PDW_SCAN_CHUNK + 2, 4);
+    L.t_up = W.take(n, 4); L.t_down = W.take(n, 4); L.comp_up = W.take(n, 4); L.comp_down = W.take(n, 4); L.lab = W.take(n, 4);
+    L.par = W.take(n2, 4); L.hk = W.take(n2, 4); L.best = W.take(n2, 8);
+    L.ia = W.take(2 * m, 4); L.ib = W.take(2 * m, 4); L.iw = W.take(2 * m, 4);
+    L.pa = W.take(m, 4); L.pb = W.take(m, 4); L.pseg = W.take(m, 4); L.pe = W.take(m, 4); L.qofp = W.take(m, 4);
+    L.pw = W.take(m, 4); L.qw = W.take(m, 4);
+    L.qa = W.take(m, 4); L.qb = W.take(m, 4); L.qseg = W.take(m, 4); L.qe = W.take(m, 4); L.qalive = W.take(m, 1);
+    L.cnt = W.take(m, 4); L.rem = W.take(m, 4); L.rem_e = W.take(m, 4);
+    L.fb = W.take(7 * n + 8, 4);
+    L.bytes = W.bytes();
     return L;
 }
 
@@ -671,10 +653,7 @@ int ceil_log2(long long v) {
     while ((1ll << l) < v) ++l;
     return l;
 }
-unsigned grid_for(long long count) {
-    const long long b = (count + PDW_BS - 1) / PDW_BS;
-    return (unsigned)(b < 1 ? 1 : b > PDW_MAX_GRID ? PDW_MAX_GRID : b);
-}
+unsigned pdw_grid(long long count) { return tlc_grid_for(count, PDW_BS, PDW_MAX_GRID); }
 
 struct Run {
     hipStream_t s;
@@ -686,21 +665,8 @@ struct Run {
         (R).launches += 1;                                                                     \
     } while (0)
 
-// keys in ka / values in va, sorted in place (8 passes: back in the first buffers)
-void sort_u64(Run& R, long long m, unsigned long long* ka, unsigned long long* kb, unsigned* va, unsigned* vb, int* hist, int* tot) {
-    if (m < 2) return;
-    const unsigned nb = (unsigned)((m + RK_TILE - 1) / RK_TILE);
-    const auto scatter = rk_scatter_kernel<unsigned long long, unsigned>;
-    for (int shift = 0; shift < 64; shift += 8) {
-        PDW_LAUNCH(R, rk_hist_kernel<unsigned long long>, nb, ka, m, shift, hist);
-        PDW_LAUNCH(R, rk_scan_rows_kernel, 256, hist, (int)nb, tot);
-        PDW_LAUNCH(R, scatter, nb, ka, va, kb, vb, m, shift, hist, tot);
-        unsigned long long* tk = ka; ka = kb; kb = tk;
-        unsigned* tv = va; va = vb; vb = tv;
-    }
-}
 void scan_flags(Run& R, Gate g, const uint8_t* fl, const int* p_count, int mult, long long bound, int* sums, int* out, int* total) {
-    const unsigned grid = grid_for((bound + PDW_SCAN_IPT - 1) / PDW_SCAN_IPT);
+    const unsigned grid = pdw_grid((bound + PDW_SCAN_IPT - 1) / PDW_SCAN_IPT);
     PDW_LAUNCH(R, pdw_scan_sums_kernel, grid, g, fl, p_count, mult, sums);
     PDW_LAUNCH(R, pdw_scan_top_kernel, 1, g, p_count, mult, sums, total);
     PDW_LAUNCH(R, pdw_scan_apply_kernel, grid, g, fl, p_count, mult, sums, out);
@@ -709,7 +675,7 @@ void scan_flags(Run& R, Gate g, const uint8_t* fl, const int* p_count, int mult,
 void msf(Run& R, const Msf& P, long long id_bound, long long item_bound) {
     const long long v = id_bound < 2 * item_bound ? id_bound : 2 * item_bound;   // components that have an item
     const int rounds = v < 2 ? 1 : ceil_log2(v) > 32 ? 32 : ceil_log2(v);
-    const unsigned gi = grid_for(item_bound), gn = grid_for(id_bound);
+    const unsigned gi = pdw_grid(item_bound), gn = pdw_grid(id_bound);
     PDW_LAUNCH(R, msf_init_kernel, gn > gi ? gn : gi, P);
     for (int r = 0; r < rounds; ++r) {
         PDW_LAUNCH(R, msf_pick_kernel, gi, P, r);
@@ -735,16 +701,16 @@ int run_graph(Run& R, char* w, const Lay& L, int n, int m, const int* edges, con
     unsigned long long* best = (unsigned long long*)(w + L.best);
     const Gate open{ctl, -1};
     const int keep0 = (flags & TLC_KEEP_ZERO_PERS) != 0, ext1 = !(flags & TLC_NO_EXT1);
-    const unsigned gm = grid_for(m), gn = grid_for(n);
+    const unsigned gm = pdw_grid(m), gn = pdw_grid(n);
 
     PDW_LAUNCH(R, pdw_ctl_kernel, 1, ctl, n, m);
     *h_levels_bound = 0;
 
     if (m > 0) {
         PDW_LAUNCH(R, pdw_keys_kernel, gm, ctl, n, m, edges, f, key_a, val_a);
-        sort_u64(R, m, key_a, key_b, val_a, val_b, hist, tot);
+        R.launches += rk_sort<64>(R.s, m, key_a, key_b, val_a, val_b, hist, tot);
         PDW_LAUNCH(R, pdw_asc_rank_kernel, gm, ctl, m, edges, f, val_a, ra, aperm, key_b, val_b);
-        sort_u64(R, m, key_b, key_a, val_b, val_a, hist, tot);
+        R.launches += rk_sort<64>(R.s, m, key_b, key_a, val_b, val_a, hist, tot);
         PDW_LAUNCH(R, pdw_desc_rank_kernel, gm, ctl, m, val_b, rd, dperm);
         PDW_LAUNCH(R, pdw_root_kernel, gm, ctl, m, edges, f, dperm);
         // the two forests of the whole graph
@@ -780,14 +746,14 @@ int run_graph(Run& R, char* w, const Lay& L, int n, int m, const int* edges, con
                    f_dy, q_idx, d_idx);
         const int levels = (flags & TLC_PD_WIDE_FORCE_FALLBACK) ? 0 : ceil_log2(m);      // K <= m
         *h_levels_bound = levels;
-        const unsigned gk = grid_for(2ll * m);
+        const unsigned gk = pdw_grid(2ll * m);
         for (int lv = 0; lv < levels; ++lv) {
             const Gate g{ctl, lv};
             const long long ids = lv == 0 ? n : (4ll * m + 4 < L.idcap ? 4ll * m + 4 : L.idcap);
             PDW_LAUNCH(R, dc_items_kernel, gk, D, lv);
             Msf T{g, ia, ib, D.iw, tmid, par, hk, best, ctl + C_TWOK, ctl + C_NS + lv, 1, 1, ctl};
             msf(R, T, ids, 2ll * m);
-            PDW_LAUNCH(R, dc_contract_kernel, grid_for(2 * ids > 2ll * m ? 2 * ids : 2ll * m), D, lv);
+            PDW_LAUNCH(R, dc_contract_kernel, pdw_grid(2 * ids > 2ll * m ? 2 * ids : 2ll * m), D, lv);
             Msf C{g, ia, ib, nullptr, tree2, par, hk, best, ctl + C_TWOK, ctl + C_NS + lv, 1, 2, ctl};
             msf(R, C, 2 * ids, 2ll * m);
             PDW_LAUNCH(R, dc_route_p_kernel, gm, D, lv);
@@ -881,8 +847,7 @@ extern "C" int tlc_pd_wide(int64_t n_graphs, const int64_t* d_node_offs, const i
             return TLC_ERR_INVALID_ARG;
         }
     }
-    char* w = (char*)d_work;
-    w += (256 - ((uintptr_t)w & 255)) & 255;
+    char* w = tlc_align256(d_work);
     for (int64_t i = 0; i < n_sel && rc == TLC_OK; ++i) {
         const int64_t g = h_sel[i], no = offs[4 * i], eo = offs[4 * i + 2];
         const int64_t n = offs[4 * i + 1] - no, m = offs[4 * i + 3] - eo;

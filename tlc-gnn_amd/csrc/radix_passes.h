@@ -1,10 +1,12 @@
-// radix_passes.h -- one pass of the device-wide LSD radix sort (8-bit digits: histogram, per-digit scan, stable scatter), shared by
-// lp_metrics.hip (u32 / u64 keys with a u8 label) and pd_wide.hip (u64 keys with a u32 id).  Positions are ints: fewer than 2^31 items.
-// A pass over n items in nb = ceil(n / RK_TILE) tiles:
+// radix_passes.h -- the device-wide LSD radix sort (8-bit digits; a pass = histogram, per-digit scan, stable scatter) of every
+// "whole device, one item after the other" class: lp_metrics.hip (u32 / u64 keys with a u8 label), pd_wide.hip and pd_grad.hip (u64 / u32
+// keys with a u32 id) and sliced_w.hip (u64 keys with a u64 payload).  Positions are ints: fewer than 2^31 items.
+// A pass over n items in nb = rk_tiles(n) tiles:
 //     rk_hist_kernel<K>      <<<nb, RK_BS>>>   hist[d * nb + b] = items of tile b with digit d
 //     rk_scan_rows_kernel    <<<256, RK_BS>>>  each digit's row -> its exclusive prefix; tot[d] = the row's sum
 //     rk_scatter_kernel<K,L> <<<nb, RK_BS>>>   stable scatter of keys and payloads
-// hist holds 256 * nb ints, tot 256.  The only atomics are LDS integer counts, so the result does not depend on the scheduling.
+// hist holds rk_hist_ints(n) ints, tot RK_TOT_INTS: the layout functions size them with the names rk_pass launches by.  The only
+// atomics are LDS integer counts, so the result does not depend on the scheduling.  Host side: rk_pass (one pass), rk_sort<BITS> (BITS / 8 of them).
 #pragma once
 #include "tlc_common.h"
 
@@ -127,6 +129,32 @@ __global__ __launch_bounds__(RK_BS) void rk_scatter_kernel(const K* __restrict__
         }
         __syncthreads();
     }
+}
+
+// ---- host side ------------------------------------------------------------------------------------------------------------
+#define RK_TOT_INTS 256                                                       // ints of tot
+inline long long rk_tiles(long long n) { return (n + RK_TILE - 1) / RK_TILE; }
+inline long long rk_hist_ints(long long n) { return 256 * rk_tiles(n); }      // ints of hist for passes over n items
+
+// one pass on the digit at `shift`: (kin, lin) -> (kout, lout), three kernels
+template <typename K, typename L>
+void rk_pass(hipStream_t st, long long n, int shift, const K* kin, const L* lin, K* kout, L* lout, int* hist, int* tot) {
+    const unsigned nb = (unsigned)rk_tiles(n);
+    hipLaunchKernelGGL(rk_hist_kernel<K>, dim3(nb), dim3(RK_BS), 0, st, kin, n, shift, hist);
+    hipLaunchKernelGGL(rk_scan_rows_kernel, dim3(256), dim3(RK_BS), 0, st, hist, (int)nb, tot);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(rk_scatter_kernel<K, L>), dim3(nb), dim3(RK_BS), 0, st, kin, lin, kout, lout, n, shift, hist, tot);
+}
+// the low BITS of the keys, ascending and stable: BITS / 8 passes that ping-pong between (ka, la) and (kb, lb) -- an even number, so
+// the result is back in ka / la, as it is for n < 2, where nothing is launched.  Returns the kernels launched.
+template <int BITS, typename K, typename L>
+int rk_sort(hipStream_t st, long long n, K* ka, K* kb, L* la, L* lb, int* hist, int* tot) {
+    static_assert(BITS % 16 == 0 && BITS <= 8 * (int)sizeof(K), "an even number of passes over digits the key has");
+    if (n < 2) return 0;
+    for (int shift = 0; shift < BITS; shift += 16) {
+        rk_pass(st, n, shift, ka, la, kb, lb, hist, tot);
+        rk_pass(st, n, shift + 8, kb, lb, ka, la, hist, tot);
+    }
+    return 3 * (BITS / 8);
 }
 
 }  // namespace

@@ -46,12 +46,7 @@ static_assert((SW_LDS_N & (SW_LDS_N - 1)) == 0 && SW_LDS_N >= 2048 && SW_LDS_N <
 static_assert(2 * TLC_SW_MAX_DIRS <= 256, "the segment number is one radix digit");
 static_assert(SW_TILE % SW_BS == 0, "whole rounds");
 
-// order-preserving image of a finite double (IEEE <  ==  unsigned <), -0.0 onto +0.0; and back
-__device__ __forceinline__ unsigned long long sw_ord(double x) {
-    unsigned long long u = (unsigned long long)__double_as_longlong(x);
-    if (u == 0x8000000000000000ull) u = 0ull;
-    return (u & 0x8000000000000000ull) ? ~u : (u | 0x8000000000000000ull);
-}
+// tlc_ord_f64 back to the double (-0.0 comes back as +0.0)
 __device__ __forceinline__ double sw_val(unsigned long long k) {
     return __longlong_as_double((long long)((k & 0x8000000000000000ull) ? (k ^ 0x8000000000000000ull) : ~k));
 }
@@ -159,8 +154,8 @@ __global__ __launch_bounds__(SW_BS) void sw_wave_kernel(SwArgs A) {
             unsigned long long k1 = ~0ull, k2 = ~0ull;
             unsigned i1 = (unsigned)lane, i2 = (unsigned)lane;
             if (has) {
-                k1 = sw_ord(p_is_x ? P.proj(l0, l1) : P.diag(l0, l1));
-                k2 = sw_ord(q_is_y ? Q.proj(l0, l1) : Q.diag(l0, l1));
+                k1 = tlc_ord_f64(p_is_x ? P.proj(l0, l1) : P.diag(l0, l1));
+                k2 = tlc_ord_f64(q_is_y ? Q.proj(l0, l1) : Q.diag(l0, l1));
             }
             sw_wave_sort2(k1, i1, k2, i2, lane);
             // lane = rank now; the absent elements (index >= N, key ~0 or not: the index breaks the tie) fill the ranks N .. 63
@@ -243,8 +238,8 @@ __global__ __launch_bounds__(SW_BS) void sw_lds_kernel(SwArgs A) {
                     const bool is_x = a < n;
                     const int o = sw_other(a, n, m);
                     const double pr = pt[q].proj(l0, l1), dg = pt[q].diag(l0, l1);
-                    key1[a] = sw_ord(is_x ? pr : dg); idx1[a] = (unsigned short)a;
-                    key2[o] = sw_ord(is_x ? dg : pr); idx2[o] = (unsigned short)o;
+                    key1[a] = tlc_ord_f64(is_x ? pr : dg); idx1[a] = (unsigned short)a;
+                    key2[o] = tlc_ord_f64(is_x ? dg : pr); idx2[o] = (unsigned short)o;
                 } else if (a < P2) {
                     key1[a] = ~0ull; idx1[a] = (unsigned short)a;
                     key2[a] = ~0ull; idx2[a] = (unsigned short)a;
@@ -346,9 +341,9 @@ __global__ __launch_bounds__(SW_BS) void sww_keys_kernel(SwWide W, int d0, int G
             const double l0 = W.dirs[2 * (d0 + g)], l1 = W.dirs[2 * (d0 + g) + 1];
             const double pr = P.proj(l0, l1), dg = P.diag(l0, l1);
             const long long s1 = 2 * g, s2 = 2 * g + 1;
-            key[s1 * N + a] = sw_ord(is_x ? pr : dg);
+            key[s1 * N + a] = tlc_ord_f64(is_x ? pr : dg);
             pay[s1 * N + a] = ((unsigned long long)s1 << 32) | (unsigned long long)a;
-            key[s2 * N + o] = sw_ord(is_x ? dg : pr);
+            key[s2 * N + o] = tlc_ord_f64(is_x ? dg : pr);
             pay[s2 * N + o] = ((unsigned long long)s2 << 32) | (unsigned long long)o;
         }
     }
@@ -427,20 +422,14 @@ struct SwLay {
 // workspace of a group of G directions with T = 2 * G * N items: a function of (T, G) alone, growing in both
 SwLay sw_layout(long long T, int G) {
     SwLay L;
-    size_t o = 0;
-    auto take = [&](long long count, size_t size) {
-        const size_t at = o;
-        o += (((size_t)(count + 1) * size) + 255) & ~(size_t)255;
-        return at;
-    };
-    const long long nb = (T + RK_TILE - 1) / RK_TILE;
-    L.ctl = take(1, sizeof(SwCtl));
-    L.key_a = take(T, 8); L.key_b = take(T, 8);
-    L.pay_a = take(T, 8); L.pay_b = take(T, 8);
-    L.signs = take(T, 1);
-    L.hist = take(256 * nb, 4); L.tot = take(256, 4);
-    L.partial = take(T / (2 * SW_TILE) + G + 1, 8);          // >= G * ceil(N / SW_TILE)
-    L.bytes = o + 256;                                       // room to align the caller's pointer
+    TlcCarver W;
+    L.ctl = W.take(1, sizeof(SwCtl));
+    L.key_a = W.take(T, 8); L.key_b = W.take(T, 8);
+    L.pay_a = W.take(T, 8); L.pay_b = W.take(T, 8);
+    L.signs = W.take(T, 1);
+    L.hist = W.take(rk_hist_ints(T), 4); L.tot = W.take(RK_TOT_INTS, 4);
+    L.partial = W.take(T / (2 * SW_TILE) + G + 1, 8);        // >= G * ceil(N / SW_TILE)
+    L.bytes = W.bytes();
     return L;
 }
 // the size that runs n_dirs directions of a problem of N points at once (as many as fit SW_WIDE_MAX_ITEMS)
@@ -451,12 +440,7 @@ long long sw_work_need(long long N, int n_dirs) {
     if (T > 2 * SW_WIDE_MAX_ITEMS) T = 2 * SW_WIDE_MAX_ITEMS;
     return (long long)sw_layout(T, n_dirs).bytes;
 }
-unsigned sw_grid_for(long long count) {
-    const long long b = (count + SW_BS - 1) / SW_BS;
-    return (unsigned)(b < 1 ? 1 : b > SW_MAX_GRID ? SW_MAX_GRID : b);
-}
-template <typename T>
-void sw_swap(T*& a, T*& b) { T* t = a; a = b; b = t; }
+unsigned sw_grid(long long count) { return tlc_grid_for(count, SW_BS, SW_MAX_GRID); }
 
 // One problem of the third class: 1 + groups x 31 kernel launches (the coordinate check; per group of directions the keys, 9 radix
 // passes of 3 kernels, the signs, the loss and -- where a gradient is wanted -- the point sums).
@@ -478,27 +462,17 @@ int sw_run_wide(const SwArgs& A, long long p, long long x0, long long y0, long l
         double* partial = (double*)(w + L.partial);
         if (d0 == 0) {
             if (hipMemsetAsync(W.ctl, 0, sizeof(SwCtl), st) != hipSuccess) return TLC_ERR_HIP;       // status 0, loss +0.0
-            hipLaunchKernelGGL(sww_begin_kernel, dim3(sw_grid_for(N)), dim3(SW_BS), 0, st, W);
+            hipLaunchKernelGGL(sww_begin_kernel, dim3(sw_grid(N)), dim3(SW_BS), 0, st, W);
         }
-        hipLaunchKernelGGL(sww_keys_kernel, dim3(sw_grid_for(N)), dim3(SW_BS), 0, st, W, d0, Gc, ka, pa);
-        const unsigned nb = (unsigned)((T + RK_TILE - 1) / RK_TILE);
-        for (int shift = 0; shift < 64; shift += 8) {        // the values, stable
-            hipLaunchKernelGGL(rk_hist_kernel<unsigned long long>, dim3(nb), dim3(RK_BS), 0, st, ka, T, shift, hist);
-            hipLaunchKernelGGL(rk_scan_rows_kernel, dim3(256), dim3(RK_BS), 0, st, hist, (int)nb, tot);
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(rk_scatter_kernel<unsigned long long, unsigned long long>), dim3(nb), dim3(RK_BS), 0, st, ka, pa,
-                               kb, pb, T, shift, hist, tot);
-            sw_swap(ka, kb); sw_swap(pa, pb);
-        }
+        hipLaunchKernelGGL(sww_keys_kernel, dim3(sw_grid(N)), dim3(SW_BS), 0, st, W, d0, Gc, ka, pa);
+        rk_sort<64>(st, T, ka, kb, pa, pb, hist, tot);       // the values, stable (T >= 2: the class starts above SW_LDS_N points)
         // the leading digit: the segment number, bits 32 .. 39 of the payload -- the payload is this pass's key
-        hipLaunchKernelGGL(rk_hist_kernel<unsigned long long>, dim3(nb), dim3(RK_BS), 0, st, pa, T, 32, hist);
-        hipLaunchKernelGGL(rk_scan_rows_kernel, dim3(256), dim3(RK_BS), 0, st, hist, (int)nb, tot);
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(rk_scatter_kernel<unsigned long long, unsigned long long>), dim3(nb), dim3(RK_BS), 0, st, pa, ka, pb,
-                           kb, T, 32, hist, tot);
+        rk_pass(st, T, 32, pa, ka, pb, kb, hist, tot);
         hipLaunchKernelGGL(sww_signs_kernel, dim3((unsigned)n_tiles, (unsigned)Gc), dim3(SW_BS), 0, st, N, n_tiles, kb, pb, signs, partial);
         hipLaunchKernelGGL(sww_loss_kernel, dim3(1), dim3(TLC_SW_MAX_DIRS), 0, st, W.ctl, Gc, n_tiles, partial, A.scale,
                            (int)(d0 + Gc == A.n_dirs), A.loss + p, A.status + p);
         if (A.gradX || A.gradY)
-            hipLaunchKernelGGL(sww_grad_kernel, dim3(sw_grid_for(N)), dim3(SW_BS), 0, st, W, d0, Gc, signs, A.gradX, A.gradY);
+            hipLaunchKernelGGL(sww_grad_kernel, dim3(sw_grid(N)), dim3(SW_BS), 0, st, W, d0, Gc, signs, A.gradX, A.gradY);
     }
     return TLC_OK;
 }
@@ -555,11 +529,10 @@ extern "C" int tlc_sliced_wasserstein(int32_t n_problems, const int64_t* d_xoff,
         else ++n_wide;
     }
     SwArgs A{n_problems, (const long long*)d_xoff, (const long long*)d_yoff, d_X, d_Y, n_dirs, d_dirs, scale, d_loss, d_gradX, d_gradY, d_status};
-    if (n_wave) hipLaunchKernelGGL(sw_wave_kernel, dim3(sw_grid_for((long long)n_problems * 64)), dim3(SW_BS), 0, st, A);
+    if (n_wave) hipLaunchKernelGGL(sw_wave_kernel, dim3(sw_grid((long long)n_problems * 64)), dim3(SW_BS), 0, st, A);
     if (n_lds) hipLaunchKernelGGL(sw_lds_kernel, dim3((unsigned)(n_problems < SW_MAX_GRID ? n_problems : SW_MAX_GRID)), dim3(SW_BS), 0, st, A);
     if (n_wide) {
-        char* w = (char*)d_work;
-        w += (256 - ((uintptr_t)w & 255)) & 255;
+        char* w = tlc_align256(d_work);
         for (size_t p = 0; p < B; ++p) {
             const long long n = xo[p + 1] - xo[p], m = yo[p + 1] - yo[p];
             if (n + m > SW_LDS_N && sw_run_wide(A, (long long)p, xo[p], yo[p], n, m, w, work_bytes, st) != TLC_OK) {

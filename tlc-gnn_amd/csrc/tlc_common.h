@@ -55,6 +55,25 @@ struct TlcDeviceScope {
         return TLC_ERR_HIP;                                                                                  \
     }
 
+// ---- workspace carving and grid sizes of the whole-device classes (pd_wide.hip, pd_grad.hip, sliced_w.hip) -----------------------
+// take(count, size): the offset of an array of count + 1 elements, each array on a multiple of 256 bytes; bytes(): the whole
+// workspace, with room for tlc_align256 of the caller's pointer.
+struct TlcCarver {
+    size_t o = 0;
+    size_t take(long long count, size_t size) {
+        const size_t at = o;
+        o += (((size_t)(count + 1) * size) + 255) & ~(size_t)255;
+        return at;
+    }
+    size_t bytes() const { return o + 256; }
+};
+inline char* tlc_align256(void* p) { return (char*)p + ((256 - ((uintptr_t)p & 255)) & 255); }
+// workgroups of `block` threads for a grid-stride kernel over count items: at least one, at most cap
+inline unsigned tlc_grid_for(long long count, int block, int cap) {
+    const long long b = (count + block - 1) / block;
+    return (unsigned)(b < 1 ? 1 : b > cap ? cap : b);
+}
+
 // ---- device helpers ---------------------------------------------------------------------------------
 #ifdef __HIPCC__
 __device__ __forceinline__ int tlc_lane() { return (int)(threadIdx.x & 63); }
@@ -133,4 +152,10 @@ __device__ __forceinline__ int tlc_wave_iscan_i32(int v) {
 }
 // value of a wavefront-uniform lane
 __device__ __forceinline__ int tlc_bcast_i32(int v, int src_lane) { return __builtin_amdgcn_readlane(v, src_lane); }
+// order-preserving image of a double (IEEE < == unsigned <, NaNs at the two ends), -0.0 onto +0.0; ~key: descending
+__device__ __forceinline__ unsigned long long tlc_ord_f64(double x) {
+    unsigned long long u = (unsigned long long)__double_as_longlong(x);
+    if (u == 0x8000000000000000ull) u = 0ull;
+    return (u & 0x8000000000000000ull) ? ~u : (u | 0x8000000000000000ull);
+}
 #endif
