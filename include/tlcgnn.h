@@ -356,8 +356,11 @@ int tlc_renorm_rows_f32(int32_t n_rows, int32_t k, float* d_emb, void* stream);
 
 /* Net.encode in eval mode (baselines/TLCGNN.py:19-26: conv1 -> ReLU -> conv2 on the normalised adjacency of tlc_gcn_norm_csr)
  * as ONE call: tlc_gemm_f32, tlc_spmm_csr_f32 (+ b1, ReLU), tlc_gemm_f32, tlc_spmm_csr_f32 (+ b2; `flags` bit 0 = ReLU, bit 1 =
- * the emb.renorm_(2, 0, 1) of TLCGNN.py:48) submitted back to back.  d_ws: scratch of (2 * hidden + out_dim) * n_nodes + 12
- * floats; d_emb: [n_nodes, out_dim].  hidden, out_dim <= 128. */
+ * the emb.renorm_(2, 0, 1) of TLCGNN.py:48) submitted back to back.  d_ws: float32[tlc_gcn2_encode_work_floats(n_nodes, hidden,
+ * out_dim)] scratch; d_emb: [n_nodes, out_dim].  hidden, out_dim <= 128.
+ * The tlc_*_work_floats / tlc_*_work_ints functions of this header are host arithmetic (no device needed): the element count of the
+ * scratch their entry takes as a bare pointer, -1 for a negative size.  The entry writes nowhere behind that count. */
+int64_t tlc_gcn2_encode_work_floats(int32_t n_nodes, int32_t hidden, int32_t out_dim);
 int tlc_gcn2_encode_f32(int32_t n_nodes, const int32_t* d_rowptr, const int32_t* d_col, const float* d_val,
                         const float* d_x, int32_t f_in, const float* d_w1, const float* d_b1, int32_t hidden,
                         const float* d_w2, const float* d_b2, int32_t out_dim, int flags, float* d_ws, float* d_emb, void* stream);
@@ -401,7 +404,8 @@ int tlc_gcn_norm_csr_t(int32_t n_nodes, int64_t n_edges, const int64_t* d_edge_i
 
 /* C[M,N] = A[K,M]^T @ B[K,N], row-major, fp32 on the f32 MFMA: dW = X^T d(XW) of GCNConv.  Split-K (at most 32 splits) with
  * the partials added in split order.  d_A NULL with M = 1: C = the column sums of B (bias gradients).  M, N >= 1, K >= 0 (K = 0:
- * zeros).  d_work float32[32 * M * N] scratch. */
+ * zeros).  d_work float32[tlc_gemm_tn_work_floats(M, N)] scratch. */
+int64_t tlc_gemm_tn_work_floats(int32_t M, int32_t N);
 int tlc_gemm_tn_f32(int32_t M, int32_t N, int64_t K, const float* d_A, const float* d_B, float* d_C, float* d_work, void* stream);
 
 /* Backward of tlc_lp_decode_fused_f32 and of the emb.renorm_(2, 0, 1) in front of it (TLCGNN.py:48-61), emb_dim 16 / pi_dim 25
@@ -409,7 +413,8 @@ int tlc_gemm_tn_f32(int32_t M, int32_t N, int64_t K, const float* d_A, const flo
  * d_pi f32[n_pairs,25]; d_gprob f32[n_pairs] = d loss / d prob.  The pair endpoints grouped by node, in the order their
  * contributions are added: d_node_ptr int32[n_nodes+1], d_node_slots int32[2 n_pairs] (slot 2 i = pair i's first endpoint,
  * 2 i + 1 its second).  Out: d_gemb f32[n_nodes,16] = d loss / d emb_pre; d_gw f32[1076] = dW1 [25][41] | db1 [25] | dW2 [25] |
- * db2 [1].  d_work float32[16 n_pairs + 1076 * 512] scratch (16-byte aligned, like d_emb). */
+ * db2 [1].  d_work float32[tlc_lp_decode_bwd_work_floats(n_pairs)] scratch (16-byte aligned, like d_emb). */
+int64_t tlc_lp_decode_bwd_work_floats(int64_t n_pairs);
 int tlc_lp_decode_bwd_f32(int64_t n_pairs, const int32_t* d_pairs, const float* d_emb_pre, const float* d_emb, int32_t n_nodes,
                           int32_t emb_dim, const float* d_pi, int32_t pi_dim, const float* d_W1, const float* d_b1,
                           const float* d_W2, const float* d_b2, const float* d_gprob, const int32_t* d_node_ptr,
@@ -436,7 +441,8 @@ int tlc_nc_group(int32_t n_nodes, int64_t n_edges, const int64_t* d_edge_index, 
 int tlc_nc_linear_f32(int32_t M, int32_t N, int32_t K, const float* d_x, const float* d_w, const float* d_b, float* d_y, void* stream);
 
 /* Backward of tlc_nc_linear_f32 for d_gy f32[M,N]: d_gw f32[N,K] = gy^T x, d_gb f32[N] = column sums of gy (NULL: skipped), d_gx f32[M,K]
- * = gy W (NULL: skipped).  Sums over M as fixed-order split-K products.  d_work float32[32 N max(K, 1)] scratch. */
+ * = gy W (NULL: skipped).  Sums over M as fixed-order split-K products.  d_work float32[tlc_nc_linear_bwd_work_floats(N, K)] scratch. */
+int64_t tlc_nc_linear_bwd_work_floats(int32_t N, int32_t K);
 int tlc_nc_linear_bwd_f32(int32_t M, int32_t N, int32_t K, const float* d_x, const float* d_w, const float* d_gy, float* d_gx,
                           float* d_gw, float* d_gb, float* d_work, void* stream);
 
@@ -585,9 +591,10 @@ int tlc_struct_batch(const int64_t* d_node_ptr, const int64_t* d_edge_ptr, const
  *   m = leaky_relu(Wij @ [x_i || x_j]) * a;  out_i = [ sum m || (min m + max m) ] + bias  (:166-172,202-216)
  *   d_X float32[n, c_in]; d_Wl float32[c_out, c_in]; d_att float32[c_out]; d_Wij float32[c_out, 2*c_out];
  *   d_bias float32[2*c_out]; d_out float32[n, 2*c_out]; prelu_slope < 0 disables the fused PReLU.
- *   d_work float32[n * (3*c_out + 4) + c_in*c_out + c_out*(2*c_out + 4)]: caller-provided scratch (per node: x_l, the two
+ *   d_work float32[tlc_gat_layer_fwd_work_floats(n, c_in, c_out)]: caller-provided scratch (per node: x_l, the two
  *   lin_ij half-projections, alpha; then the layer's weights packed for the MFMA GEMM).
  *   c_out in {8,16,32,64}. */
+int64_t tlc_gat_layer_fwd_work_floats(int32_t n_nodes, int32_t c_in, int32_t c_out);
 int tlc_gat_layer_fwd(int32_t n_nodes, const int32_t* d_rowptr, const int32_t* d_src,
                       const float* d_X, int32_t c_in, int32_t c_out,
                       const float* d_Wl, const float* d_att, const float* d_Wij, const float* d_bias,
@@ -597,8 +604,9 @@ int tlc_gat_layer_fwd(int32_t n_nodes, const int32_t* d_rowptr, const int32_t* d
  * node's own tile (a batch of small graphs cut at positions no edge crosses: Knowledge_Distillation/gat_conv.py, GraphBatch).  The node
  * rows [P | Q | alpha] are computed on the f32 MFMA into LDS and aggregated from there: they never reach HBM.  c_in = 1 or 64 with
  * c_out = 32 or 16 (the PDGNN layers of Teacher_model.py:182-189); other shapes: TLC_ERR_UNSUPPORTED (take tlc_gat_layer_fwd).
- * d_work: float32[c_in*c_out + c_out*(2*c_out + 4) + c_in*(2*c_out + 4) + 2*c_out + 8].  Results equal tlc_gat_layer_fwd's up to the
- * rounding of fp32 sums. */
+ * d_work: float32[tlc_gat_layer_tiled_fwd_work_floats(c_in, c_out)].  Results equal tlc_gat_layer_fwd's up to the rounding of fp32
+ * sums. */
+int64_t tlc_gat_layer_tiled_fwd_work_floats(int32_t c_in, int32_t c_out);
 int tlc_gat_layer_tiled_fwd(int32_t n_nodes, const int32_t* d_rowptr, const int32_t* d_src, int32_t n_tiles,
                             const int32_t* d_tile_ptr, const float* d_X, int32_t c_in, int32_t c_out,
                             const float* d_Wl, const float* d_att, const float* d_Wij, const float* d_bias,
@@ -609,7 +617,10 @@ int tlc_gat_layer_tiled_fwd(int32_t n_nodes, const int32_t* d_rowptr, const int3
  * the CSR (rows = targets, d_col = sources) crosses; with `gap` the largest distance between two such positions next to each other,
  * the first of them at or behind every multiple of tile_nodes - gap starts a tile.  *n_tiles (HOST int; the call waits for the
  * stream) = 0 when 2 gap > tile_nodes -- one big graph: the two-kernel layer (tlc_gat_layer_fwd) serves it.
- * d_work: int32[n_nodes / 32 + 6]; d_tile_ptr: room for 2 n_nodes / tile_nodes + 3 entries. */
+ * d_work: int32[tlc_gat_tile_cut_work_ints(n_nodes)]; d_tile_ptr: room for tlc_gat_tile_cut_max_tiles(n_nodes, tile_nodes) entries
+ * (-1 for n_nodes < 0 or tile_nodes < 1). */
+int64_t tlc_gat_tile_cut_work_ints(int32_t n_nodes);
+int64_t tlc_gat_tile_cut_max_tiles(int32_t n_nodes, int32_t tile_nodes);
 int tlc_gat_tile_cut(int32_t n_nodes, const int32_t* d_rowptr, const int32_t* d_col, int32_t tile_nodes, int32_t* d_work,
                      int32_t* d_tile_ptr, int32_t* n_tiles, void* stream);
 
@@ -617,7 +628,8 @@ int tlc_gat_tile_cut(int32_t n_nodes, const int32_t* d_rowptr, const int32_t* d_
 /* remove_self_loops + add_self_loops + grouping by target (gat_conv.py:146-152), the structure alone and per BATCH: what
  * tlc_gcn_norm_csr builds without its values, with the caller's temporaries -- nothing is allocated, nothing waits for the stream.
  *   d_rowptr int32[n_nodes+1]; d_col int32[n_edges+n_nodes] (sources ascending inside a row); d_nnz int32[1];
- *   d_work int32[3 n_nodes + n_edges]. */
+ *   d_work int32[tlc_csr_by_target_work_ints(n_nodes, n_edges)]. */
+int64_t tlc_csr_by_target_work_ints(int32_t n_nodes, int64_t n_edges);
 int tlc_csr_by_target(int32_t n_nodes, int64_t n_edges, const int64_t* d_edge_index, int32_t* d_rowptr, int32_t* d_col,
                       int32_t* d_nnz, int32_t* d_work, void* stream);
 
@@ -739,8 +751,9 @@ int tlc_sliced_wasserstein(int32_t n_problems, const int64_t* d_xoff, const doub
  *   d_out  float32[n, 2*c_out]: the forward's output, read only when prelu_slope >= 0 (sign of the pre-activation); else may be NULL
  *   d_gout float32[n, 2*c_out]: d loss / d out
  *   d_gX   float32[n, c_in] or NULL (first layer);  d_gWl [c_out, c_in], d_gatt [c_out], d_gWij [c_out, 2*c_out], d_gbias [2*c_out]:
- *   OVERWRITTEN.   d_work float32[n * (8*c_out + 5) + 2*c_out*c_out + c_in*c_out + 4 + c_out*(2*c_out + 4)] scratch.   c_out in {8,16,32,64}, c_in <= 64.
+ *   OVERWRITTEN.   d_work float32[tlc_gat_layer_bwd_work_floats(n, c_in, c_out)] scratch.   c_out in {8,16,32,64}, c_in <= 64.
  * Float atomics towards the sources of the edges and in the weight reductions: the summation order is not fixed. */
+int64_t tlc_gat_layer_bwd_work_floats(int32_t n_nodes, int32_t c_in, int32_t c_out);
 int tlc_gat_layer_bwd(int32_t n_nodes, const int32_t* d_rowptr, const int32_t* d_src, const float* d_X, int32_t c_in,
                       int32_t c_out, const float* d_Wl, const float* d_att, const float* d_Wij, float prelu_slope,
                       const float* d_out, const float* d_gout, float* d_gX, float* d_gWl, float* d_gatt, float* d_gWij,
@@ -748,7 +761,8 @@ int tlc_gat_layer_bwd(int32_t n_nodes, const int32_t* d_rowptr, const int32_t* d
 
 /* tlc_edge_head_bwd: gradients of tlc_edge_head_fwd.  d_gpd float32[n_edges, 2] = d loss / d pd.
  *   d_gX float32[n_nodes, c] is ADDED to (the caller zeroes it); d_gW5 [hidden, 2c], d_gb5 [hidden], d_gW6 [2, hidden], d_gb6 [2]:
- *   OVERWRITTEN.   d_work float32[n_edges * (2*c + 2*hidden)] scratch.   hidden in {16,32,64}. */
+ *   OVERWRITTEN.   d_work float32[tlc_edge_head_bwd_work_floats(n_edges, c, hidden)] scratch.   hidden in {16,32,64}. */
+int64_t tlc_edge_head_bwd_work_floats(int64_t n_edges, int32_t c, int32_t hidden);
 int tlc_edge_head_bwd(int64_t n_edges, const int32_t* d_src, const int32_t* d_dst, const float* d_X, int32_t c,
                       const float* d_W5, const float* d_b5, int32_t hidden, float prelu_slope, const float* d_W6,
                       const float* d_gpd, float* d_gX, float* d_gW5, float* d_gb5, float* d_gW6, float* d_gb6,
@@ -763,8 +777,9 @@ int tlc_scatter_f32(int64_t n_src, const int64_t* d_index, const float* d_src, i
 
 /* Edge head of Teacher_Model.forward (Teacher_model.py:54-59): for every non-self-loop edge e=(s,t):
  *   pd[e] = W6 @ prelu(W5 @ [x[s] || x[t]] + b5) + b6   -> float32[n_edges,2]
- * d_work (optional, float32[(n_nodes + c) * 2 * hidden]): with it the first layer is computed per node on the MFMA GEMM
- * (W5[:, :c] x_s + W5[:, c:] x_t) and only gathered per edge; NULL: one 2c x hidden product per edge. */
+ * d_work (optional, float32[tlc_edge_head_fwd_work_floats(n_nodes, c, hidden)]): with it the first layer is computed per node on the
+ * MFMA GEMM (W5[:, :c] x_s + W5[:, c:] x_t) and only gathered per edge; NULL: one 2c x hidden product per edge. */
+int64_t tlc_edge_head_fwd_work_floats(int32_t n_nodes, int32_t c, int32_t hidden);
 int tlc_edge_head_fwd(int64_t n_edges, const int32_t* d_src, const int32_t* d_dst, const float* d_X,
                       int32_t c, const float* d_W5, const float* d_b5, int32_t hidden, float prelu_slope,
                       const float* d_W6, const float* d_b6, float* d_pd, int32_t n_nodes, float* d_work, void* stream);

@@ -51,6 +51,9 @@ SYMBOLS = [
     "tlc_ollivier_ricci_otd", "tlc_ollivier_ricci_otd_work_bytes", "tlc_pd_wide", "tlc_pd_wide_work_bytes",
     "tlc_pd_grad_work_bytes", "tlc_pd_point_vertices", "tlc_pd_filtration_grad",
     "tlc_sliced_w_work_bytes", "tlc_sliced_wasserstein",
+    "tlc_gcn2_encode_work_floats", "tlc_gemm_tn_work_floats", "tlc_lp_decode_bwd_work_floats", "tlc_nc_linear_bwd_work_floats",
+    "tlc_gat_layer_fwd_work_floats", "tlc_gat_layer_tiled_fwd_work_floats", "tlc_gat_tile_cut_work_ints", "tlc_gat_tile_cut_max_tiles",
+    "tlc_csr_by_target_work_ints", "tlc_gat_layer_bwd_work_floats", "tlc_edge_head_fwd_work_floats", "tlc_edge_head_bwd_work_floats",
 ]
 
 
@@ -111,59 +114,54 @@ def lib():
         L.tlc_pd_from_filtration.argtypes = [C.c_int32] + [C.c_void_p] * 4 + [C.c_uint32] + [C.c_void_p] * 7
         L.tlc_pi_raster.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         L.tlc_pi_raster_wgrad.argtypes = [C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
-        if hasattr(L, "tlc_gcn_norm_csr"):
-            L.tlc_gcn_norm_csr.argtypes = [C.c_int32, C.c_int64] + [C.c_void_p] * 6
-            L.tlc_gemm_f32.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
-                                       C.c_void_p, C.c_void_p]
-            L.tlc_spgemm_csr_dense_f32.argtypes = [C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 5 + [C.c_int, C.c_void_p, C.c_void_p]
-            L.tlc_spmm_csr_f32.argtypes = [C.c_int32] + [C.c_void_p] * 4 + [C.c_int32, C.c_void_p, C.c_int, C.c_void_p,
-                                                                            C.c_void_p]
-            L.tlc_renorm_rows_f32.argtypes = [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
-            L.tlc_gcn2_encode_f32.argtypes = ([C.c_int32] + [C.c_void_p] * 4 + [C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
+        L.tlc_gcn_norm_csr.argtypes = [C.c_int32, C.c_int64] + [C.c_void_p] * 6
+        L.tlc_gemm_f32.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                   C.c_void_p, C.c_void_p]
+        L.tlc_spgemm_csr_dense_f32.argtypes = [C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 5 + [C.c_int, C.c_void_p, C.c_void_p]
+        L.tlc_spmm_csr_f32.argtypes = [C.c_int32] + [C.c_void_p] * 4 + [C.c_int32, C.c_void_p, C.c_int, C.c_void_p,
+                                                                        C.c_void_p]
+        L.tlc_renorm_rows_f32.argtypes = [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
+        L.tlc_gcn2_encode_f32.argtypes = ([C.c_int32] + [C.c_void_p] * 4 + [C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
+                                          C.c_void_p, C.c_int32, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p])
+        L.tlc_gcn2_encode_csr_f32.argtypes = ([C.c_int32] + [C.c_void_p] * 6 + [C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
                                               C.c_void_p, C.c_int32, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p])
-            L.tlc_gcn2_encode_csr_f32.argtypes = ([C.c_int32] + [C.c_void_p] * 6 + [C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
-                                                  C.c_void_p, C.c_int32, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p])
-            L.tlc_lp_decode_fused.argtypes = [C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
-                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-            L.tlc_lp_decode_fused_f32.argtypes = L.tlc_lp_decode_fused.argtypes
-        if hasattr(L, "tlc_gemm_tn_f32"):
-            L.tlc_gcn_norm_csr_t.argtypes = [C.c_int32, C.c_int64] + [C.c_void_p] * 7
-            L.tlc_gemm_tn_f32.argtypes = [C.c_int32, C.c_int32, C.c_int64] + [C.c_void_p] * 5
-            L.tlc_lp_decode_bwd_f32.argtypes = ([C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32]
-                                                + [C.c_void_p] * 10)
-        if hasattr(L, "tlc_binary_rank_metrics"):
-            L.tlc_binary_rank_metrics_work_bytes.argtypes = [C.c_void_p, C.c_int32, C.c_int, C.c_uint32]
-            L.tlc_binary_rank_metrics_work_bytes.restype = C.c_int64
-            L.tlc_binary_rank_metrics.argtypes = ([C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int32, C.c_uint32]
-                                                  + [C.c_void_p] * 6 + [C.c_int64, C.c_void_p])
-        if hasattr(L, "tlc_nc_group"):
-            L.tlc_nc_group_work_ints.argtypes = [C.c_int32, C.c_int64]
-            L.tlc_nc_group_work_ints.restype = C.c_int64
-            L.tlc_nc_group.argtypes = [C.c_int32, C.c_int64] + [C.c_void_p] * 5
-            L.tlc_nc_linear_f32.argtypes = [C.c_int32] * 3 + [C.c_void_p] * 5
-            L.tlc_nc_linear_bwd_f32.argtypes = [C.c_int32] * 3 + [C.c_void_p] * 8
-            L.tlc_nc_curv_work_bytes.argtypes = [C.c_int32, C.c_int64, C.c_int32, C.c_int32]
-            L.tlc_nc_curv_work_bytes.restype = C.c_int64
-            L.tlc_nc_curv_fwd_f32.argtypes = [C.c_int32, C.c_int64, C.c_int32, C.c_int32] + [C.c_void_p] * 10
-            L.tlc_nc_curv_bwd_f32.argtypes = [C.c_int32, C.c_int64, C.c_int32, C.c_int32] + [C.c_void_p] * 14 + [C.c_int64, C.c_void_p]
-        if hasattr(L, "tlc_gat_layer_fwd"):
-            L.tlc_gat_layer_fwd.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
-                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p,
-                                            C.c_void_p, C.c_void_p]
-            L.tlc_csr_by_target.argtypes = [C.c_int32, C.c_int64] + [C.c_void_p] * 6
-            L.tlc_pdgnn_forward_work_bytes.argtypes = [C.c_int32, C.c_int64, C.c_int32]
-            L.tlc_pdgnn_forward_work_bytes.restype = C.c_int64
-            L.tlc_pdgnn_forward.argtypes = [C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32,
-                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
-            L.tlc_gat_tile_cut.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_void_p]
-            L.tlc_gat_layer_tiled_fwd.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
-                                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p,
-                                                  C.c_void_p, C.c_void_p]
-            L.tlc_scatter_f32.argtypes = [C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_int, C.c_int32, C.c_void_p,
-                                          C.c_void_p, C.c_void_p]
-            L.tlc_edge_head_fwd.argtypes = [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
-                                            C.c_void_p, C.c_int32, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p,
-                                            C.c_int32, C.c_void_p, C.c_void_p]
+        L.tlc_lp_decode_fused.argtypes = [C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.tlc_lp_decode_fused_f32.argtypes = L.tlc_lp_decode_fused.argtypes
+        L.tlc_gcn_norm_csr_t.argtypes = [C.c_int32, C.c_int64] + [C.c_void_p] * 7
+        L.tlc_gemm_tn_f32.argtypes = [C.c_int32, C.c_int32, C.c_int64] + [C.c_void_p] * 5
+        L.tlc_lp_decode_bwd_f32.argtypes = ([C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32]
+                                            + [C.c_void_p] * 10)
+        L.tlc_binary_rank_metrics_work_bytes.argtypes = [C.c_void_p, C.c_int32, C.c_int, C.c_uint32]
+        L.tlc_binary_rank_metrics_work_bytes.restype = C.c_int64
+        L.tlc_binary_rank_metrics.argtypes = ([C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int32, C.c_uint32]
+                                              + [C.c_void_p] * 6 + [C.c_int64, C.c_void_p])
+        L.tlc_nc_group_work_ints.argtypes = [C.c_int32, C.c_int64]
+        L.tlc_nc_group_work_ints.restype = C.c_int64
+        L.tlc_nc_group.argtypes = [C.c_int32, C.c_int64] + [C.c_void_p] * 5
+        L.tlc_nc_linear_f32.argtypes = [C.c_int32] * 3 + [C.c_void_p] * 5
+        L.tlc_nc_linear_bwd_f32.argtypes = [C.c_int32] * 3 + [C.c_void_p] * 8
+        L.tlc_nc_curv_work_bytes.argtypes = [C.c_int32, C.c_int64, C.c_int32, C.c_int32]
+        L.tlc_nc_curv_work_bytes.restype = C.c_int64
+        L.tlc_nc_curv_fwd_f32.argtypes = [C.c_int32, C.c_int64, C.c_int32, C.c_int32] + [C.c_void_p] * 10
+        L.tlc_nc_curv_bwd_f32.argtypes = [C.c_int32, C.c_int64, C.c_int32, C.c_int32] + [C.c_void_p] * 14 + [C.c_int64, C.c_void_p]
+        L.tlc_gat_layer_fwd.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
+                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p,
+                                        C.c_void_p, C.c_void_p]
+        L.tlc_csr_by_target.argtypes = [C.c_int32, C.c_int64] + [C.c_void_p] * 6
+        L.tlc_pdgnn_forward_work_bytes.argtypes = [C.c_int32, C.c_int64, C.c_int32]
+        L.tlc_pdgnn_forward_work_bytes.restype = C.c_int64
+        L.tlc_pdgnn_forward.argtypes = [C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32,
+                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.tlc_gat_tile_cut.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_void_p]
+        L.tlc_gat_layer_tiled_fwd.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
+                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p,
+                                              C.c_void_p, C.c_void_p]
+        L.tlc_scatter_f32.argtypes = [C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_int, C.c_int32, C.c_void_p,
+                                      C.c_void_p, C.c_void_p]
+        L.tlc_edge_head_fwd.argtypes = [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
+                                        C.c_void_p, C.c_int32, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_int32, C.c_void_p, C.c_void_p]
         L.tlc_complement_rows.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.tlc_complement_pairs.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64,
                                            C.c_void_p, C.c_void_p]
@@ -205,6 +203,15 @@ def lib():
         L.tlc_sliced_w_work_bytes.restype = C.c_int64
         L.tlc_sliced_wasserstein.argtypes = ([C.c_int32] + [C.c_void_p] * 4 + [C.c_int32, C.c_void_p, C.c_double, C.c_int64] + [C.c_void_p] * 5
                                              + [C.c_int64, C.c_void_p])
+        # the scratch sizes of the entries that take a bare d_work (csrc/scratch_layouts.h)
+        for name, args in (("tlc_gcn2_encode_work_floats", [C.c_int32] * 3), ("tlc_gemm_tn_work_floats", [C.c_int32] * 2),
+                           ("tlc_lp_decode_bwd_work_floats", [C.c_int64]), ("tlc_nc_linear_bwd_work_floats", [C.c_int32] * 2),
+                           ("tlc_gat_layer_fwd_work_floats", [C.c_int32] * 3), ("tlc_gat_layer_tiled_fwd_work_floats", [C.c_int32] * 2),
+                           ("tlc_gat_tile_cut_work_ints", [C.c_int32]), ("tlc_gat_tile_cut_max_tiles", [C.c_int32] * 2),
+                           ("tlc_csr_by_target_work_ints", [C.c_int32, C.c_int64]), ("tlc_gat_layer_bwd_work_floats", [C.c_int32] * 3),
+                           ("tlc_edge_head_fwd_work_floats", [C.c_int32] * 3), ("tlc_edge_head_bwd_work_floats", [C.c_int64, C.c_int32, C.c_int32])):
+            fn = getattr(L, name)
+            fn.argtypes, fn.restype = args, C.c_int64
         L.tlc_debug_set_option.argtypes = [C.c_void_p, C.c_char_p, C.c_int]
         L.tlc_debug_dc_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.tlc_debug_tier_counts.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]

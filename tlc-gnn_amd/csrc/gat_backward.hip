@@ -13,6 +13,7 @@
 // products: one reduction kernel (tlc_xty) with per-workgroup partial sums and float atomics.
 // fp32 throughout, like the forward; FMA contraction welcome (Makefile).
 #include "tlc_common.h"
+#include "scratch_layouts.h"
 
 extern "C" int tlc_gemm_f32(int32_t M, int32_t N, int32_t K, const float* d_A, const float* d_B, const float* d_bias, int relu,
                             float* d_C, void* stream);
@@ -265,20 +266,12 @@ template <int C>
 static int launch_gat_bwd(int n, const int* rowptr, const int* src, const float* X, int c_in, const float* Wl, const float* att,
                           const float* Wij, float prelu_slope, const float* out, const float* G, float* gX, float* gWl, float* gAtt,
                           float* gWij, float* gBias, float* work, hipStream_t s) {
-    // work: xl [n,C] | pqa [n,2C+4] | gP [n,C] | gQ [n,C] | gxl [n,C] | Gz [n,2C] | tmp [2,C,C] | Bt1 [c_in,C] | Bt2 [C,2C+4] | gAlpha [n]
-    // (S = 2C + 4 when the rows come from the MFMA product -- the forward's layout -- else 2C + 1)
+    // (the pqa rows have stride S = 2C + 4 when they come from the MFMA product -- the forward's layout -- else 2C + 1)
     const bool by_gemm = 2 * C + 4 <= 128;
     const int S = by_gemm ? 2 * C + 4 : 2 * C + 1;
-    float* xl = work;
-    float* pqa = xl + (size_t)n * C;
-    float* gP = pqa + (size_t)n * (2 * C + 4);
-    float* gQ = gP + (size_t)n * C;
-    float* gxl = gQ + (size_t)n * C;
-    float* Gz = gxl + (size_t)n * C;
-    float* tmp0 = Gz + (size_t)n * 2 * C;
-    float* Bt1 = tmp0 + (size_t)2 * C * C;
-    float* Bt2 = Bt1 + (((size_t)c_in * C + 3) & ~(size_t)3);
-    float* gAl = Bt2 + (size_t)C * (2 * C + 4);              // (last: n floats would put what follows off its 16-byte alignment)
+    const TlcGatLayerBwdScratch L(n, c_in, C);
+    float *xl = work + L.xl, *pqa = work + L.pqa, *gP = work + L.gp, *gQ = work + L.gq, *gxl = work + L.gxl, *Gz = work + L.gz;
+    float *tmp0 = work + L.tmp, *Bt1 = work + L.bt1, *Bt2 = work + L.bt2, *gAl = work + L.gal;
     TLC_HIP_CHECK(hipMemsetAsync(gQ, 0, (size_t)n * C * sizeof(float), s));
     TLC_HIP_CHECK(hipMemsetAsync(gAl, 0, (size_t)n * sizeof(float), s));
     TLC_HIP_CHECK(hipMemsetAsync(gWl, 0, (size_t)C * c_in * sizeof(float), s));
@@ -373,8 +366,13 @@ __global__ __launch_bounds__(128) void edge_head_bwd_kernel(long long n_edges, c
 
 }  // namespace
 
-// d_work: float32[n * (8 * c_out + 5) + 2 * c_out * c_out + c_in * c_out + 4 + c_out * (2 * c_out + 4)] scratch, 16-byte aligned.  d_out: the layer's forward output (only read when prelu_slope >= 0: the sign of the
-// output is the sign of the pre-activation).  d_gX may be null (first layer: the input is data).
+extern "C" int64_t tlc_gat_layer_bwd_work_floats(int32_t n_nodes, int32_t c_in, int32_t c_out) {
+    if (n_nodes < 0 || c_in < 0 || c_out < 0) return -1;
+    return TlcGatLayerBwdScratch(n_nodes, c_in, c_out).total;
+}
+
+// d_work: tlc_gat_layer_bwd_work_floats of scratch, 16-byte aligned.  d_out: the layer's forward output (only read when prelu_slope >= 0:
+// the sign of the output is the sign of the pre-activation).  d_gX may be null (first layer: the input is data).
 extern "C" int tlc_gat_layer_bwd(int32_t n_nodes, const int32_t* d_rowptr, const int32_t* d_src, const float* d_X, int32_t c_in,
                                  int32_t c_out, const float* d_Wl, const float* d_att, const float* d_Wij, float prelu_slope,
                                  const float* d_out, const float* d_gout, float* d_gX, float* d_gWl, float* d_gatt, float* d_gWij,
@@ -400,7 +398,12 @@ extern "C" int tlc_gat_layer_bwd(int32_t n_nodes, const int32_t* d_rowptr, const
     }
 }
 
-// d_work: float32[n_edges * (2 * c + 2 * hidden)] scratch.  d_gX [n_nodes, c] is ADDED to (zero it first).
+extern "C" int64_t tlc_edge_head_bwd_work_floats(int64_t n_edges, int32_t c, int32_t hidden) {
+    if (n_edges < 0 || c < 0 || hidden < 0) return -1;
+    return TlcEdgeHeadBwdScratch(n_edges, c, hidden).total;
+}
+
+// d_work: tlc_edge_head_bwd_work_floats of scratch.  d_gX [n_nodes, c] is ADDED to (zero it first).
 extern "C" int tlc_edge_head_bwd(int64_t n_edges, const int32_t* d_src, const int32_t* d_dst, const float* d_X, int32_t c,
                                  const float* d_W5, const float* d_b5, int32_t hidden, float prelu_slope, const float* d_W6,
                                  const float* d_gpd, float* d_gX, float* d_gW5, float* d_gb5, float* d_gW6, float* d_gb6,
@@ -415,9 +418,8 @@ extern "C" int tlc_edge_head_bwd(int64_t n_edges, const int32_t* d_src, const in
     TLC_HIP_CHECK(hipMemsetAsync(d_gb6, 0, (size_t)2 * sizeof(float), s));
     if (n_edges == 0) return TLC_OK;
     TLC_REQUIRE(d_src && d_dst && d_X && d_W5 && d_b5 && d_W6 && d_gpd && d_gX && d_work, "null pointer");
-    float* cat = d_work;
-    float* hbuf = cat + (size_t)n_edges * 2 * c;
-    float* gpre = hbuf + (size_t)n_edges * hidden;
+    const TlcEdgeHeadBwdScratch L(n_edges, c, hidden);
+    float *cat = d_work + L.cat, *hbuf = d_work + L.hbuf, *gpre = d_work + L.gpre;
     const size_t lds = ((size_t)hidden * 2 * c + 3 * (size_t)hidden) * sizeof(float);
     TLC_REQUIRE(lds <= 64 * 1024, "edge head weights do not fit LDS");
     const dim3 grid((unsigned)((n_edges + 127) / 128));

@@ -15,6 +15,7 @@
 
 #include "tlc_common.h"
 #include "gat_internal.h"
+#include "scratch_layouts.h"
 
 namespace {
 
@@ -417,9 +418,10 @@ int launch_gat(int n, const int* rowptr, const int* src, const float* X, int c_i
     const unsigned agrid = (unsigned)(((size_t)n * C + 255) / 256);
     constexpr int NPG = 2;                                   // nodes per lane group in the aggregation (4: 321 us, 1: 336 us, 2: 243 us)
     const unsigned agrid2 = (unsigned)((((size_t)n + NPG - 1) / NPG * C + 255) / 256);
+    const TlcGatLayerFwdScratch L(n, c_in, C);
     if (c_in == 1) {
         // the first PDGNN layer: rows are f_i * v (see gat_aggregate_kernel, RANK1)
-        float* vec = work;                                   // [2C + 1]
+        float* vec = work + L.vec;
         hipLaunchKernelGGL(gat_rank1_vec_kernel, dim3(1), dim3(256), 0, s, C, Wl, att, Wij, vec);
         hipLaunchKernelGGL((gat_aggregate_kernel<C, NPG, true>), dim3(agrid2), dim3(256), 0, s, n, rowptr, src, X, 1, bias, slope, out,
                            (const float*)vec);
@@ -429,10 +431,10 @@ int launch_gat(int n, const int* rowptr, const int* src, const float* X, int c_i
     if (2 * C + 4 <= 128 && C % 4 == 0) {
         // x_l = X Wl^T and [P | Q | alpha] = x_l [Wij_t^T | Wij_s^T | att] as two products on the f32 MFMA (per node on the
         // vector ALU this was 95 us of a layer; the products are 2 x ~15 us)
-        float* XL = work;
-        float* PQA = work + (size_t)n * C;
-        float* Bt1 = work + (size_t)n * (3 * C + 4);
-        float* Bt2 = Bt1 + (size_t)c_in * C;
+        float* XL = work + L.xl;
+        float* PQA = work + L.pqa;
+        float* Bt1 = work + L.bt1;
+        float* Bt2 = work + L.bt2;
         const int N2 = 2 * C + 4;
         const int np = std::max(c_in * C, C * N2);
         hipLaunchKernelGGL(gat_pack_kernel, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, s, C, c_in, Wl, att, Wij, Bt1, Bt2);
@@ -463,8 +465,9 @@ int launch_gat(int n, const int* rowptr, const int* src, const float* X, int c_i
     constexpr int NPB = 256 / C;
     int grid = (n + NPB - 1) / NPB;
     if (grid > 4096) grid = 4096;
-    hipLaunchKernelGGL(gat_node_kernel<C>, dim3(grid), dim3(256), lds, s, n, X, c_in, Wl, att, Wij, work);
-    hipLaunchKernelGGL((gat_aggregate_kernel<C, NPG, false>), dim3(agrid2), dim3(256), 0, s, n, rowptr, src, (const float*)(work + C), 3 * C + 1, bias,
+    float* rows = work + L.rows;
+    hipLaunchKernelGGL(gat_node_kernel<C>, dim3(grid), dim3(256), lds, s, n, X, c_in, Wl, att, Wij, rows);
+    hipLaunchKernelGGL((gat_aggregate_kernel<C, NPG, false>), dim3(agrid2), dim3(256), 0, s, n, rowptr, src, (const float*)(rows + C), 3 * C + 1, bias,
                        slope, out, (const float*)nullptr);
     TLC_HIP_CHECK(hipGetLastError());
     return TLC_OK;
@@ -796,6 +799,11 @@ extern "C" int tlc_scatter_f32(int64_t n_src, const int64_t* d_index, const floa
     return TLC_OK;
 }
 
+extern "C" int64_t tlc_gat_layer_fwd_work_floats(int32_t n_nodes, int32_t c_in, int32_t c_out) {
+    if (n_nodes < 0 || c_in < 0 || c_out < 0) return -1;
+    return TlcGatLayerFwdScratch(n_nodes, c_in, c_out).total;
+}
+
 extern "C" int tlc_gat_layer_fwd(int32_t n_nodes, const int32_t* d_rowptr, const int32_t* d_src, const float* d_X, int32_t c_in,
                                  int32_t c_out, const float* d_Wl, const float* d_att, const float* d_Wij, const float* d_bias,
                                  float prelu_slope, float* d_work, float* d_out, void* stream) {
@@ -829,9 +837,10 @@ static int edge_head_fwd_impl(int64_t n_edges, const IT* d_src, const IT* d_dst,
         return TLC_OK;
     }
     if (d_work && n_nodes > 0 && hidden % 4 == 0 && 2 * hidden <= 128) {
-        // per-node projections U | V (work[0 .. n_nodes * 2 * hidden)) on the MFMA GEMM, then the per-edge gather
-        float* d_UV = d_work;
-        float* d_Bt = d_work + (size_t)n_nodes * 2 * hidden;
+        // per-node projections U | V on the MFMA GEMM, then the per-edge gather
+        const TlcEdgeHeadFwdScratch L(n_nodes, c, hidden);
+        float* d_UV = d_work + L.uv;
+        float* d_Bt = d_work + L.bt;
         hipLaunchKernelGGL(edge_head_pack_kernel, dim3((unsigned)((c * 2 * hidden + 255) / 256)), dim3(256), 0, (hipStream_t)stream, c,
                            hidden, d_W5, d_Bt);
         TLC_HIP_CHECK(hipGetLastError());
@@ -867,6 +876,11 @@ static int edge_head_fwd_impl(int64_t n_edges, const IT* d_src, const IT* d_dst,
     return TLC_ERR_UNSUPPORTED;
 }
 
+extern "C" int64_t tlc_edge_head_fwd_work_floats(int32_t n_nodes, int32_t c, int32_t hidden) {
+    if (n_nodes < 0 || c < 0 || hidden < 0) return -1;
+    return TlcEdgeHeadFwdScratch(n_nodes, c, hidden).total;
+}
+
 extern "C" int tlc_edge_head_fwd(int64_t n_edges, const int32_t* d_src, const int32_t* d_dst, const float* d_X, int32_t c,
                                  const float* d_W5, const float* d_b5, int32_t hidden, float prelu_slope, const float* d_W6,
                                  const float* d_b6, float* d_pd, int32_t n_nodes, float* d_work, void* stream) {
@@ -883,9 +897,13 @@ int tlc_edge_head_fwd_i64(int64_t n_edges, const long long* d_src, const long lo
 // One PDGNN layer on a block-diagonal batch cut into self-contained tiles (see gat_tile_kernel): d_tile_ptr int32[n_tiles + 1], node
 // offsets of tiles of at most 192 consecutive nodes such that every in-edge of a tile's node has its source in the same tile (the
 // caller's business: Knowledge_Distillation/gat_conv.py, GraphBatch).  c_in = 1 or 64 with c_out = 32, 16 (the PDGNN layers); any
-// other shape: TLC_ERR_UNSUPPORTED (the caller takes tlc_gat_layer_fwd).  d_work: float32[c_in * c_out + c_out * (2 c_out + 4) +
-// c_in * (2 c_out + 4) + 2 c_out + 8] of scratch for the packed and combined weights.  Same results as tlc_gat_layer_fwd up to the
-// rounding of the node rows' fp32 sums.
+// other shape: TLC_ERR_UNSUPPORTED (the caller takes tlc_gat_layer_fwd).  d_work: tlc_gat_layer_tiled_fwd_work_floats of scratch for
+// the combined weights.  Same results as tlc_gat_layer_fwd up to the rounding of the node rows' fp32 sums.
+extern "C" int64_t tlc_gat_layer_tiled_fwd_work_floats(int32_t c_in, int32_t c_out) {
+    if (c_in < 0 || c_out < 0) return -1;
+    return TlcGatLayerTiledFwdScratch(c_in, c_out).total;
+}
+
 extern "C" int tlc_gat_layer_tiled_fwd(int32_t n_nodes, const int32_t* d_rowptr, const int32_t* d_src, int32_t n_tiles,
                                        const int32_t* d_tile_ptr, const float* d_X, int32_t c_in, int32_t c_out, const float* d_Wl,
                                        const float* d_att, const float* d_Wij, const float* d_bias, float prelu_slope, float* d_work,
@@ -895,10 +913,11 @@ extern "C" int tlc_gat_layer_tiled_fwd(int32_t n_nodes, const int32_t* d_rowptr,
     TLC_REQUIRE(d_rowptr && d_src && d_tile_ptr && d_X && d_Wl && d_att && d_Wij && d_bias && d_work && d_out, "null pointer");
     if (!((c_in == 1 || c_in == 64) && (c_out == 32 || c_out == 16))) { tlc_set_error("tlc_gat_layer_tiled_fwd: c_in %d / c_out %d not built", c_in, c_out); return TLC_ERR_UNSUPPORTED; }
     hipStream_t s = (hipStream_t)stream;
-    const TlcGatPrepLayer layer = {c_in, c_out, d_Wl, d_att, d_Wij, d_work};
+    float* prep = d_work + TlcGatLayerTiledFwdScratch(c_in, c_out).prep;
+    const TlcGatPrepLayer layer = {c_in, c_out, d_Wl, d_att, d_Wij, prep};
     const int rc = tlc_gat_tiled_prepare(1, &layer, s);
     if (rc != TLC_OK) return rc;
-    return tlc_gat_tiled_run(n_tiles, d_tile_ptr, d_rowptr, d_src, d_X, c_in, c_out, d_work, d_bias, prelu_slope, d_out, s);
+    return tlc_gat_tiled_run(n_tiles, d_tile_ptr, d_rowptr, d_src, d_X, c_in, c_out, prep, d_bias, prelu_slope, d_out, s);
 }
 
 // The combined weights of up to four tiled layers, one workgroup per layer (see gat_internal.h).  The products are 64 x 68 x 32 at
@@ -961,6 +980,7 @@ int tlc_gat_tiled_run(int n_tiles, const int* tile_ptr, const int* rowptr, const
 //   of step starts a tile (pick): consecutive picks are less than step + gap = tile_nodes apart.  No cut when 2 gap > tile_nodes.
 namespace {
 enum { TC_BAD = 0, TC_GAP = 1, TC_NT = 2, TC_HEAD = 4 };
+static_assert(TC_HEAD == TlcGatTileCutScratch::HEAD, "the state words of scratch_layouts.h");
 constexpr int TC_HALF_MAX = 512;                               // tile_nodes <= 1024
 // 256 rows per workgroup: their forbidden positions lie within `half` of the rows, so they are OR-ed in LDS first and go out as one
 // atomic per touched word (one atomic per row and word made 80 us of same-address traffic on a million molecule nodes)
@@ -1026,6 +1046,14 @@ __global__ void tile_cut_pick_kernel(int n, int tile_nodes, const unsigned* __re
     else if (f / step > pf / step) tiles[f / step] = f;
 }
 }  // namespace
+extern "C" int64_t tlc_gat_tile_cut_work_ints(int32_t n_nodes) {
+    if (n_nodes < 0) return -1;
+    return TlcGatTileCutScratch(n_nodes).total;
+}
+extern "C" int64_t tlc_gat_tile_cut_max_tiles(int32_t n_nodes, int32_t tile_nodes) {
+    if (n_nodes < 0 || tile_nodes < 1) return -1;
+    return TlcGatTileCutScratch::max_tiles(n_nodes, tile_nodes);
+}
 extern "C" int tlc_gat_tile_cut(int32_t n_nodes, const int32_t* d_rowptr, const int32_t* d_col, int32_t tile_nodes, int32_t* d_work,
                                 int32_t* d_tile_ptr, int32_t* n_tiles, void* stream) {
     TLC_REQUIRE(n_nodes >= 0 && tile_nodes >= 2 && tile_nodes <= 2 * TC_HALF_MAX && n_tiles, "bad sizes");
@@ -1033,10 +1061,10 @@ extern "C" int tlc_gat_tile_cut(int32_t n_nodes, const int32_t* d_rowptr, const 
     if (n_nodes == 0) return TLC_OK;
     TLC_REQUIRE(d_rowptr && d_col && d_work && d_tile_ptr, "null pointer");
     hipStream_t s = (hipStream_t)stream;
-    int* st = d_work;
-    unsigned* bits = (unsigned*)(d_work + TC_HEAD);
-    const size_t words = (size_t)n_nodes / 32 + 2;
-    TLC_HIP_CHECK(hipMemsetAsync(d_work, 0, (TC_HEAD + words) * sizeof(int), s));
+    const TlcGatTileCutScratch L(n_nodes);
+    int* st = d_work + L.st;
+    unsigned* bits = (unsigned*)(d_work + L.bits);
+    TLC_HIP_CHECK(hipMemsetAsync(d_work, 0, (size_t)L.total * sizeof(int), s));
     const unsigned g = (unsigned)((n_nodes + 1 + 255) / 256);
     hipLaunchKernelGGL(tile_cut_mark_kernel, dim3(g), dim3(256), 0, s, n_nodes, tile_nodes / 2, d_rowptr, d_col, bits, st);
     hipLaunchKernelGGL(tile_cut_gap_kernel, dim3((unsigned)(n_nodes / TC_GAP_PER_WG + 1)), dim3(256), 0, s, n_nodes, tile_nodes / 2, bits, st);

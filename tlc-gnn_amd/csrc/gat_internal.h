@@ -4,7 +4,7 @@
 #include "tlc_common.h"
 
 // one layer's combined weights: c_in == 1: prep[0 .. 2C] = Wl[:, 0]^T [Wij_t^T | Wij_s^T | att]; c_in == 64: prep[c_in][2C + 4] = Wl^T
-// [Wij_t^T | Wij_s^T | att | 0 0 0].  prep: float32[c_in * (2 c_out + 4)] of the caller's scratch.
+// [Wij_t^T | Wij_s^T | att | 0 0 0].  prep: float32[TlcGatLayerTiledFwdScratch(c_in, c_out).prep_floats] of the caller's scratch.
 struct TlcGatPrepLayer {
     int c_in, c_out;
     const float *Wl, *att, *Wij;

@@ -9,6 +9,7 @@
 // bit-identical gradients on every call.  (A^T G of the GCN layer is tlc_spmm_csr_f32 over the transposed operator,
 // tlc_gcn_norm_csr_t, which lives next to the forward operator's build in lp_forward.hip.)
 #include "tlc_common.h"
+#include "scratch_layouts.h"
 
 namespace {
 
@@ -131,7 +132,7 @@ __global__ __launch_bounds__(256) void gemm_tn_kernel(int M, int N, long long K,
 
 // splits of tlc_gemm_tn_f32: enough workgroups to cover the CUs twice over (512), at least 256 rows of K per split, at most
 // TN_MAX_SPLITS (the scratch the caller provides)
-#define TN_MAX_SPLITS 32
+constexpr int TN_MAX_SPLITS = TlcGemmTnScratch::MAX_SPLITS;
 int gemm_tn_splits(int M, int N, long long K) {
     const long long tiles = (long long)((M + TN_BM - 1) / TN_BM) * ((N + TN_BN - 1) / TN_BN);
     long long s = (512 + tiles - 1) / tiles;
@@ -158,7 +159,8 @@ constexpr int DB_ED = 16, DB_PD = 25, DB_IN = DB_ED + DB_PD;
 constexpr int DB_NW = DB_PD * DB_IN + 2 * DB_PD + 1;             // 1076
 constexpr int DB_T = 128, DB_S = DB_T + 1;                        // pairs per tile; LDS row stride (rows on distinct banks)
 constexpr int DB_Q = (DB_NW + DB_T - 1) / DB_T;                   // outputs per thread
-#define DB_MAX_WG 512
+constexpr int DB_MAX_WG = TlcLpDecodeBwdScratch::MAX_WG;
+static_assert(DB_ED == TlcLpDecodeBwdScratch::ED && DB_NW == TlcLpDecodeBwdScratch::NW, "the row widths of scratch_layouts.h");
 
 __global__ __launch_bounds__(DB_T) void lp_decode_bwd_kernel(long long n_pairs, const int* __restrict__ pairs, const float* __restrict__ emb,
                                                              const float* __restrict__ pi, const float* __restrict__ W1,
@@ -335,6 +337,11 @@ __global__ __launch_bounds__(256) void lp_node_grad_kernel(int n_nodes, const in
 // ======================================================================================================================
 // C ABI
 // ======================================================================================================================
+extern "C" int64_t tlc_gemm_tn_work_floats(int32_t M, int32_t N) {
+    if (M < 0 || N < 0) return -1;
+    return TlcGemmTnScratch(M, N).total;
+}
+
 extern "C" int tlc_gemm_tn_f32(int32_t M, int32_t N, int64_t K, const float* d_A, const float* d_B, float* d_C, float* d_work,
                                void* stream) {
     TLC_REQUIRE(M >= 1 && N >= 1 && K >= 0, "bad sizes");
@@ -346,16 +353,22 @@ extern "C" int tlc_gemm_tn_f32(int32_t M, int32_t N, int64_t K, const float* d_A
     TLC_REQUIRE(S == 1 || d_work, "null scratch");
     const long long kps = S == 1 ? (K > 0 ? K : 1) : (K + S - 1) / S;
     const dim3 grid((M + TN_BM - 1) / TN_BM, (N + TN_BN - 1) / TN_BN, S);
-    float* dst = S == 1 ? d_C : d_work;
+    float* part = S == 1 ? nullptr : d_work + TlcGemmTnScratch(M, N).part;
+    float* dst = S == 1 ? d_C : part;
     if (d_A) hipLaunchKernelGGL(gemm_tn_kernel<false>, grid, dim3(256), 0, s, M, N, (long long)K, kps, d_A, d_B, dst);
     else hipLaunchKernelGGL(gemm_tn_kernel<true>, grid, dim3(256), 0, s, M, N, (long long)K, kps, d_A, d_B, dst);
     if (S > 1) {
         const long long n_out = (long long)M * N;
         hipLaunchKernelGGL(sum_partials_kernel, dim3((unsigned)((n_out + 63) / 64)), dim3(64 * SP_R), 0, s, n_out, S,
-                           (const float*)d_work, d_C);
+                           (const float*)part, d_C);
     }
     TLC_HIP_CHECK(hipGetLastError());
     return TLC_OK;
+}
+
+extern "C" int64_t tlc_lp_decode_bwd_work_floats(int64_t n_pairs) {
+    if (n_pairs < 0) return -1;
+    return TlcLpDecodeBwdScratch(n_pairs).total;
 }
 
 extern "C" int tlc_lp_decode_bwd_f32(int64_t n_pairs, const int32_t* d_pairs, const float* d_emb_pre, const float* d_emb, int32_t n_nodes,
@@ -372,8 +385,8 @@ extern "C" int tlc_lp_decode_bwd_f32(int64_t n_pairs, const int32_t* d_pairs, co
     TLC_REQUIRE(n_pairs == 0 || (d_pairs && d_emb && d_pi && d_W1 && d_b1 && d_W2 && d_b2 && d_gprob && d_node_slots), "null pointer");
     TLC_REQUIRE((reinterpret_cast<uintptr_t>(d_emb) & 15) == 0 && (reinterpret_cast<uintptr_t>(d_work) & 15) == 0, "emb / work not 16-byte aligned");
     hipStream_t s = (hipStream_t)stream;
-    float* gpair = d_work;                                           // [n_pairs][16]
-    float* part = d_work + (size_t)n_pairs * DB_ED;                  // [wg][DB_NW]
+    const TlcLpDecodeBwdScratch L(n_pairs);
+    float *gpair = d_work + L.gpair, *part = d_work + L.part;
     if (n_pairs == 0) {
         TLC_HIP_CHECK(hipMemsetAsync(d_gw, 0, DB_NW * sizeof(float), s));
     } else {

@@ -13,6 +13,7 @@
 // gather over a CSR sorted by target so that every output row has one owner: no atomics, bitwise
 // reproducible, and the bias/activation fuse into the same pass.
 #include "tlc_common.h"
+#include "scratch_layouts.h"
 #include <stdlib.h>
 
 
@@ -1161,27 +1162,28 @@ __global__ __launch_bounds__(256) void lp_decode_generic_kernel(long long n_pair
 // ======================================================================================================================
 // C ABI
 // ======================================================================================================================
-// the launches of the CSR-by-target build; tmp int32[3 n + E] = [cnt n | cursor n | unsorted col E + n]; d_val NULL: structure only
+// the launches of the CSR-by-target build; tmp: int32[TlcCsrByTargetScratch.total]; d_val NULL: structure only
 static int gcn_csr_launch(int32_t n_nodes, int64_t n_edges, const int64_t* d_edge_index, int32_t* d_rowptr, int32_t* d_col, float* d_val,
                           int32_t* d_nnz, int* tmp, hipStream_t s) {
-    // tmp: [n] counts | [n] unused | [E + n] entries as they arrive.  The counts are dead once the row pointers exist: their words
-    // then hold the list of the rows above GCN_SHORT_ROW entries (word 0: how many; zeroed by the fill kernel, which runs behind
-    // the scans and ahead of the kernel that appends).  An edge's place in its row (what its counting atomic returned: E words)
-    // waits in d_col from word n on (d_col has E + n words and is written for good only by the finish kernels; its head is the
-    // scan's scratch).
-    if (hipMemsetAsync(tmp, 0, (size_t)n_nodes * sizeof(int), s) != hipSuccess) return TLC_ERR_HIP;
-    int* long_rows = tmp;
+    // The counts are dead once the row pointers exist: their words then hold the list of the rows above GCN_SHORT_ROW entries
+    // (word 0: how many; zeroed by the fill kernel, which runs behind the scans and ahead of the kernel that appends).  An edge's
+    // place in its row (what its counting atomic returned: E words) waits in d_col from word n on (d_col has E + n words and is
+    // written for good only by the finish kernels; its head is the scan's scratch).
+    const TlcCsrByTargetScratch L(n_nodes, n_edges);
+    int* cnt = tmp + L.cnt;
+    if (hipMemsetAsync(cnt, 0, (size_t)n_nodes * sizeof(int), s) != hipSuccess) return TLC_ERR_HIP;
+    int* long_rows = cnt;
     const int long_cap = n_nodes - 1;
-    int* raw = tmp + 2 * (size_t)n_nodes;
+    int* raw = tmp + L.raw;
     int* place = d_col + n_nodes;                             // (E words behind the scan's scratch: d_col holds E + n)
     const int eb = (int)((n_edges + 255) / 256), nb = (n_nodes + 255) / 256;
-    if (n_edges) hipLaunchKernelGGL(gcn_count_kernel, dim3(eb), dim3(256), 0, s, (long long)n_edges, (const long long*)d_edge_index, n_nodes, tmp, place);
+    if (n_edges) hipLaunchKernelGGL(gcn_count_kernel, dim3(eb), dim3(256), 0, s, (long long)n_edges, (const long long*)d_edge_index, n_nodes, cnt, place);
     if (n_nodes <= 8192) {
-        hipLaunchKernelGGL(gcn_scan_kernel, dim3(1), dim3(1024), 0, s, n_nodes, (const int*)tmp, d_rowptr, d_nnz);
+        hipLaunchKernelGGL(gcn_scan_kernel, dim3(1), dim3(1024), 0, s, n_nodes, (const int*)cnt, d_rowptr, d_nnz);
     } else {
         // block totals in the head of d_col (written for good only by gcn_finish_kernel, after the fill)
         const int sb = (n_nodes + 1023) / 1024;
-        hipLaunchKernelGGL(gcn_scan_block_kernel, dim3(sb), dim3(1024), 0, s, n_nodes, (const int*)tmp, d_rowptr, d_col);
+        hipLaunchKernelGGL(gcn_scan_block_kernel, dim3(sb), dim3(1024), 0, s, n_nodes, (const int*)cnt, d_rowptr, d_col);
         hipLaunchKernelGGL(gcn_scan_top_kernel, dim3(1), dim3(1024), 0, s, sb, d_col, d_rowptr, d_nnz);
         hipLaunchKernelGGL(gcn_scan_add_kernel, dim3(sb), dim3(1024), 0, s, n_nodes, d_rowptr, (const int*)d_col);
     }
@@ -1199,7 +1201,7 @@ extern "C" int tlc_gcn_norm_csr(int32_t n_nodes, int64_t n_edges, const int64_t*
     TLC_REQUIRE(d_rowptr && d_col && d_val && (n_edges == 0 || d_edge_index), "null pointer");
     hipStream_t s = (hipStream_t)stream;
     int* tmp = nullptr;
-    TLC_HIP_CHECK(hipMalloc(&tmp, (3 * (size_t)n_nodes + (size_t)n_edges) * sizeof(int)));
+    TLC_HIP_CHECK(hipMalloc(&tmp, (size_t)TlcCsrByTargetScratch(n_nodes, n_edges).total * sizeof(int)));
     const int rc = gcn_csr_launch(n_nodes, n_edges, d_edge_index, d_rowptr, d_col, d_val, d_nnz, tmp, s);
     hipStreamSynchronize(s);      // cached=True: one-off preprocessing; the temporaries must outlive the kernels
     hipFree(tmp);
@@ -1209,6 +1211,11 @@ extern "C" int tlc_gcn_norm_csr(int32_t n_nodes, int64_t n_edges, const int64_t*
 
 // The structure alone, per BATCH (Knowledge_Distillation/gat_conv.py:146-152 runs remove_self_loops + add_self_loops on every forward):
 // the caller brings the temporaries, nothing is allocated and nothing waits for the stream.
+extern "C" int64_t tlc_csr_by_target_work_ints(int32_t n_nodes, int64_t n_edges) {
+    if (n_nodes < 0 || n_edges < 0) return -1;
+    return TlcCsrByTargetScratch(n_nodes, n_edges).total;
+}
+
 extern "C" int tlc_csr_by_target(int32_t n_nodes, int64_t n_edges, const int64_t* d_edge_index, int32_t* d_rowptr, int32_t* d_col,
                                  int32_t* d_nnz, int32_t* d_work, void* stream) {
     TLC_REQUIRE(n_nodes > 0 && n_edges >= 0, "bad sizes");
@@ -1248,7 +1255,7 @@ extern "C" int tlc_gcn_norm_csr_t(int32_t n_nodes, int64_t n_edges, const int64_
     TLC_REQUIRE(d_rowptr && d_rowptr_t && d_col_t && d_val_t && d_nnz && (n_edges == 0 || d_edge_index), "null pointer");
     hipStream_t s = (hipStream_t)stream;
     int* tmp = nullptr;
-    const size_t tmp_ints = 3 * (size_t)n_nodes + (size_t)n_edges, flip_ints = 4 * (size_t)n_edges;      // (int64 pairs: 4 ints per edge)
+    const size_t tmp_ints = (size_t)TlcCsrByTargetScratch(n_nodes, n_edges).total, flip_ints = 4 * (size_t)n_edges;      // (int64 pairs: 4 ints per edge)
     TLC_HIP_CHECK(hipMalloc(&tmp, (tmp_ints + flip_ints + 2) * sizeof(int)));
     long long* flip = reinterpret_cast<long long*>(tmp + ((tmp_ints + 1) & ~(size_t)1));
     if (n_edges) hipLaunchKernelGGL(flip_edges_kernel, dim3((unsigned)((n_edges + 255) / 256)), dim3(256), 0, s, (long long)n_edges,
@@ -1578,22 +1585,25 @@ extern "C" int tlc_renorm_rows_f32(int32_t n_rows, int32_t k, float* d_emb, void
     return TLC_OK;
 }
 
+extern "C" int64_t tlc_gcn2_encode_work_floats(int32_t n_nodes, int32_t hidden, int32_t out_dim) {
+    if (n_nodes < 0 || hidden < 0 || out_dim < 0) return -1;
+    return TlcGcn2EncodeScratch(n_nodes, hidden, out_dim).total;
+}
+
 // The whole two-layer encoder of Net.encode in eval mode (baselines/TLCGNN.py:19-26: conv1 -> ReLU -> conv2, dropout off) behind
 // ONE call: x@W1, aggregate + b1 + ReLU, h@W2, aggregate + b2 with `flags` as in tlc_spmm_csr_f32 (bit 0 ReLU, bit 1 the renorm_ of
 // TLCGNN.py:48) submitted back to back, without five trips through the caller's language between them (a Python host needs ~70 us
 // to submit what the device runs in 79 us).  For out_dim == 16 (TLCGNN) the second and third step are ONE kernel (spmm_w2_kernel:
 // h@W2 in the aggregate's epilogue, fp32 sums in another order than the separate product's); otherwise the four kernels of the
 // separate calls.
-// d_ws: (2 * hidden + out_dim) * n floats (+ 12) of scratch.
+// d_ws: tlc_gcn2_encode_work_floats of scratch.
 static int gcn2_encode_impl(int32_t n_nodes, const int32_t* d_rowptr, const int32_t* d_col, const float* d_val,
                             const float* d_x, const int32_t* d_xs_rowptr, const int32_t* d_xs_col, const float* d_xs_val,
                             int32_t f_in, const float* d_w1, const float* d_b1, int32_t hidden,
                             const float* d_w2, const float* d_b2, int32_t out_dim, int flags, float* d_ws, float* d_emb,
                             void* stream) {
-    auto pad4 = [](size_t v) { return (v + 3) & ~(size_t)3; };
-    float* t1 = d_ws;
-    float* t2 = t1 + pad4((size_t)n_nodes * hidden);
-    float* t3 = t2 + pad4((size_t)n_nodes * hidden);
+    const TlcGcn2EncodeScratch L(n_nodes, hidden, out_dim);
+    float *t1 = d_ws + L.t1, *t2 = d_ws + L.t2, *t3 = d_ws + L.t3;
     int rc;
     if (d_x) rc = tlc_gemm_f32(n_nodes, hidden, f_in, d_x, d_w1, nullptr, 0, t1, stream);
     else rc = tlc_spgemm_csr_dense_f32(n_nodes, f_in, hidden, d_xs_rowptr, d_xs_col, d_xs_val, d_w1, nullptr, 0, t1, stream);

@@ -13,6 +13,7 @@
 // No floating-point atomics anywhere: every sum runs in an order fixed by the graph and the shapes, so the same inputs give the same
 // bits on every call.  Edges are kept exactly as given (duplicates and self loops stay); E * C is indexed in 64 bits.
 #include "tlc_common.h"
+#include "scratch_layouts.h"
 
 namespace {
 
@@ -534,13 +535,19 @@ extern "C" int tlc_nc_linear_f32(int32_t M, int32_t N, int32_t K, const float* d
     return TLC_OK;
 }
 
+extern "C" int64_t tlc_nc_linear_bwd_work_floats(int32_t N, int32_t K) {
+    if (N < 0 || K < 0) return -1;
+    return TlcNcLinearBwdScratch(N, K).total;
+}
+
 extern "C" int tlc_nc_linear_bwd_f32(int32_t M, int32_t N, int32_t K, const float* d_x, const float* d_w, const float* d_gy, float* d_gx,
                                      float* d_gw, float* d_gb, float* d_work, void* stream) {
     TLC_REQUIRE(M >= 0 && N >= 1 && K >= 1, "bad sizes");
     TLC_REQUIRE(d_w && d_gw && d_work && (M == 0 || (d_x && d_gy)), "null pointer");
-    int rc = tlc_gemm_tn_f32(N, K, M, d_gy, d_x, d_gw, d_work, stream);                              // dW[n][k] = sum_m dy[m][n] x[m][k]
+    float* tn = d_work + TlcNcLinearBwdScratch(N, K).tn;
+    int rc = tlc_gemm_tn_f32(N, K, M, d_gy, d_x, d_gw, tn, stream);                                  // dW[n][k] = sum_m dy[m][n] x[m][k]
     if (rc != TLC_OK) return rc;
-    if (d_gb && (rc = tlc_gemm_tn_f32(1, N, M, nullptr, d_gy, d_gb, d_work, stream)) != TLC_OK) return rc;
+    if (d_gb && (rc = tlc_gemm_tn_f32(1, N, M, nullptr, d_gy, d_gb, tn, stream)) != TLC_OK) return rc;
     if (d_gx) TLC_HIP_CHECK(nc_gemm_launch(false, M, K, N, d_gy, d_w, nullptr, d_gx, (hipStream_t)stream));
     return TLC_OK;
 }
@@ -548,8 +555,7 @@ extern "C" int tlc_nc_linear_bwd_f32(int32_t M, int32_t N, int32_t K, const floa
 extern "C" int64_t tlc_nc_curv_work_bytes(int32_t n_nodes, int64_t n_edges, int32_t C, int32_t D) {
     if (n_nodes < 1 || n_edges < 0 || C < 1 || C > NC_MAX_C || D < 1 || D > NC_MAX_D) return -1;
     const long long tiles = (n_edges + NC_T - 1) / NC_T;
-    const long long mx = (long long)C * (C > D ? C : D);
-    return 4 * (3 * n_edges * C + tiles * C + 32 * mx);
+    return 4 * (3 * n_edges * C + tiles * C + TlcGemmTnScratch(C, C > D ? C : D).total);      // (tn: the largest of its four products)
 }
 
 static int nc_check_shape(const char* fn, int32_t n_nodes, int64_t n_edges, int32_t C, int32_t D) {

@@ -12,30 +12,32 @@
 #include <algorithm>
 
 #include "tlc_common.h"
+#include "scratch_layouts.h"
 #include "gat_internal.h"
 
 namespace {
-inline size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
-
+// the steps' scratch (scratch_layouts.h) and the forward's own arrays, each on a multiple of 256 bytes.  (Not TlcCarver: its
+// count + 1 elements per array and its alignment slack would change what tlc_pdgnn_forward_work_bytes returns.)
 struct PdgnnWork {
-    size_t rowptr, col, nnz, csr_tmp, cut_work, tiles, h0, h1, layer, prep, head, pts, total;
+    size_t rowptr, col, nnz, csr_tmp, cut_work, tiles, h0, h1, layer, prep, prep_stride, head, pts, total;
     PdgnnWork(long long n, long long E, int hidden, int tile_nodes) {
-        const long long m = E - n, C = hidden, N2 = 2 * C + 4, cin = 2 * C;
+        const long long m = E - n, C = hidden, cin = 2 * C;        // the widest layer: 2C channels in, C out
         size_t o = 0;
-        auto take = [&](size_t bytes) { const size_t at = o; o += up256(bytes); return at; };
-        rowptr = take((size_t)(n + 1) * 4);
-        col = take((size_t)(E + n) * 4);
-        nnz = take(4);
-        csr_tmp = take((size_t)(3 * n + E) * 4);
-        cut_work = take((size_t)(n / 32 + 6) * 4);
-        tiles = take((size_t)(2 * n / tile_nodes + 3) * 4);
-        h0 = take((size_t)n * 2 * C * 4);
-        h1 = take((size_t)n * 2 * C * 4);
-        const size_t tiled = (size_t)(cin * C + C * N2 + cin * N2 + 2 * C + 8), plain = (size_t)n * (3 * C + 4) + cin * C + C * (2 * C + 4);
-        layer = take(std::max(tiled, plain) * 4);
-        prep = take((size_t)TLC_GAT_PREP_MAX * cin * N2 * 4);
-        head = take((size_t)(n + C) * 2 * hidden * 4);            // conv3 gives C = hidden channels per node
-        pts = take((size_t)std::max(m, 1ll) * 2 * 8);
+        auto take = [&](long long count, size_t size) { const size_t at = o; o += ((size_t)count * size + 255) & ~(size_t)255; return at; };
+        rowptr = take(n + 1, 4);
+        col = take(E + n, 4);
+        nnz = take(1, 4);
+        csr_tmp = take(TlcCsrByTargetScratch(n, E).total, 4);
+        cut_work = take(TlcGatTileCutScratch(n).total, 4);
+        tiles = take(TlcGatTileCutScratch::max_tiles(n, tile_nodes), 4);
+        h0 = take(n * 2 * C, 4);
+        h1 = take(n * 2 * C, 4);
+        const TlcGatLayerTiledFwdScratch tiled(cin, C);
+        layer = take(std::max(tiled.total, TlcGatLayerFwdScratch(n, cin, C).total), 4);
+        prep_stride = (size_t)tiled.prep_floats;
+        prep = take(TLC_GAT_PREP_MAX * tiled.prep_floats, 4);
+        head = take(TlcEdgeHeadFwdScratch(n, C, hidden).total, 4);    // conv3 gives C = hidden channels per node
+        pts = take(std::max(m, 1ll) * 2, 8);
         total = o;
     }
 };
@@ -67,7 +69,7 @@ extern "C" int tlc_pdgnn_forward(int32_t n_nodes, int64_t n_edges, const int64_t
     const float* in = d_x;
     float* bufs[2] = {(float*)(base + w.h0), (float*)(base + w.h1)};
     float* prep = (float*)(base + w.prep);
-    const size_t prep_stride = (size_t)2 * C * (2 * C + 4);
+    const size_t prep_stride = w.prep_stride;
     // first what needs no structure -- the combined weights of the four (tiled) layers in one launch -- so that the device has work
     // while the host waits for the tile count
     if (!d_rowptr || n_tiles > 0) {

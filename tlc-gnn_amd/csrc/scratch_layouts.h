@@ -1,0 +1,98 @@
+// scratch_layouts.h -- the layout of every caller-sized scratch buffer of the link-prediction and PDGNN entry points, once.
+// Host arithmetic only.  A struct is built from its entry's size arguments and holds the offset of every sub-array and `total`, in
+// elements of the scratch's type (float32 or int32).  The exported tlc_*_work_floats / tlc_*_work_ints return `total`, the launch code
+// takes its pointers from the same struct (work + L.pqa), and PdgnnWork (pdgnn_forward.hip) composes them: a size has one definition.
+// These entries take a bare d_work without its size, so a `total` below what the launch writes is an out-of-bounds device write.
+#pragma once
+#include <stdint.h>
+
+#include <algorithm>
+
+inline int64_t tlc_up4(int64_t v) { return (v + 3) & ~(int64_t)3; }      // float counts whose successor stays 16-byte aligned
+
+// tlc_gemm_tn_f32: the split-K partials [splits <= MAX_SPLITS][M][N]; one split writes d_C directly
+struct TlcGemmTnScratch {
+    static constexpr int MAX_SPLITS = 32;
+    int64_t part = 0, total;
+    TlcGemmTnScratch(int64_t M, int64_t N) : total(MAX_SPLITS * M * N) {}
+};
+
+// tlc_nc_linear_bwd_f32: its two tlc_gemm_tn_f32 products (dW [N,K], db [1,N]) one after the other in the same scratch
+struct TlcNcLinearBwdScratch {
+    int64_t tn = 0, total;
+    TlcNcLinearBwdScratch(int64_t N, int64_t K) : total(std::max(TlcGemmTnScratch(N, K).total, TlcGemmTnScratch(1, N).total)) {}
+};
+
+// tlc_lp_decode_bwd_f32: d e_u per pair [n_pairs][ED] | the workgroups' weight-gradient partials [MAX_WG][NW]
+struct TlcLpDecodeBwdScratch {
+    static constexpr int ED = 16, NW = 1076, MAX_WG = 512;
+    int64_t gpair = 0, part, total;
+    explicit TlcLpDecodeBwdScratch(int64_t n_pairs) : part(n_pairs * ED), total(part + (int64_t)NW * MAX_WG) {}
+};
+
+// tlc_gcn2_encode_f32 / _csr_f32: x W1 [n][hidden] | conv1's output [n][hidden] | its projection [n][out_dim], each on a multiple of
+// four floats.  The 12 floats behind them cover the two roundings (at most 3 floats each).
+struct TlcGcn2EncodeScratch {
+    int64_t t1 = 0, t2, t3, total;
+    TlcGcn2EncodeScratch(int64_t n, int64_t hidden, int64_t out_dim)
+        : t2(tlc_up4(n * hidden)), t3(t2 + tlc_up4(n * hidden)), total((2 * hidden + out_dim) * n + 12) {}
+};
+
+// tlc_csr_by_target (and the one-off builds of tlc_gcn_norm_csr / _t): the rows' counts [n], later the list of the long rows |
+// [n] unused | the entries as they arrive [n_edges + n]
+struct TlcCsrByTargetScratch {
+    int64_t cnt = 0, raw, total;
+    TlcCsrByTargetScratch(int64_t n, int64_t n_edges) : raw(2 * n), total(raw + n_edges + n) {}
+};
+
+// tlc_gat_tile_cut: the state words [HEAD] | the bitmap of the forbidden positions 0 .. n, [n / 32 + 2] words
+struct TlcGatTileCutScratch {
+    static constexpr int HEAD = 4;
+    int64_t st = 0, bits = HEAD, words, total;
+    explicit TlcGatTileCutScratch(int64_t n) : words(n / 32 + 2), total(bits + words) {}
+    // room of d_tile_ptr: one tile start per multiple of tile_nodes - gap >= tile_nodes / 2, and the end
+    static int64_t max_tiles(int64_t n, int64_t tile_nodes) { return 2 * n / tile_nodes + 3; }
+};
+
+// tlc_gat_layer_fwd.  On the f32 MFMA (c_out <= 32): x_l [n][C] | [P | Q | alpha | 0 0 0] [n][2C + 4] | Bt1 = Wl^T [c_in][C] |
+// Bt2 [C][2C + 4]; with fused weights Wf [c_in][2C + 4] lies where x_l would (launch_gat takes that path only when it fits).
+// c_in == 1 writes vec [2C + 1] only, c_out == 64 the node rows [n][3C + 1] only: both lie inside the x_l and pqa regions.
+struct TlcGatLayerFwdScratch {
+    int64_t xl = 0, vec = 0, rows = 0, pqa, bt1, bt2, total;
+    TlcGatLayerFwdScratch(int64_t n, int64_t c_in, int64_t C)
+        : pqa(xl + n * C), bt1(pqa + n * (2 * C + 4)), bt2(bt1 + c_in * C), total(bt2 + C * (2 * C + 4)) {}
+};
+
+// tlc_gat_layer_tiled_fwd.  Only the combined weights prep [c_in][2C + 4] (TlcGatPrepLayer of gat_internal.h) are written; `total`
+// still counts the packed Wl^T, Bt2 and att / bias rows of the layer's earlier two-product form, because callers and
+// tlc_pdgnn_forward_work_bytes size by it.
+struct TlcGatLayerTiledFwdScratch {
+    int64_t prep = 0, prep_floats, total;
+    TlcGatLayerTiledFwdScratch(int64_t c_in, int64_t C)
+        : prep_floats(c_in * (2 * C + 4)), total(c_in * C + C * (2 * C + 4) + prep_floats + 2 * C + 8) {}
+};
+
+// tlc_gat_layer_bwd: x_l [n][C] | pqa [n][2C + 4] | gP, gQ, gxl [n][C] each | Gz [n][2C] | tmp [2][C][C] | Bt1 [c_in][C], rounded
+// up to four floats so that Bt2 [C][2C + 4] stays 16-byte aligned | gAlpha [n] (last: n floats would misalign what follows).
+// `total` leaves the whole 4 floats of the contract for that rounding.
+struct TlcGatLayerBwdScratch {
+    int64_t xl = 0, pqa, gp, gq, gxl, gz, tmp, bt1, bt2, gal, total;
+    TlcGatLayerBwdScratch(int64_t n, int64_t c_in, int64_t C)
+        : pqa(xl + n * C), gp(pqa + n * (2 * C + 4)), gq(gp + n * C), gxl(gq + n * C), gz(gxl + n * C), tmp(gz + n * 2 * C),
+          bt1(tmp + 2 * C * C), bt2(bt1 + tlc_up4(c_in * C)), gal(bt2 + C * (2 * C + 4)),
+          total(gal + n + (c_in * C + 4 - tlc_up4(c_in * C))) {}
+};
+
+// tlc_edge_head_fwd (optional): the per-node projections U | V [n_nodes][2 hidden] | W5 packed for the GEMM [c][2 hidden].  The MFMA
+// kernel (c = hidden = 32) and the per-edge kernel (d_work NULL) use none of it.
+struct TlcEdgeHeadFwdScratch {
+    int64_t uv = 0, bt, total;
+    TlcEdgeHeadFwdScratch(int64_t n_nodes, int64_t c, int64_t hidden) : bt(n_nodes * 2 * hidden), total(bt + c * 2 * hidden) {}
+};
+
+// tlc_edge_head_bwd: [x_s || x_t] [n_edges][2c] | h [n_edges][hidden] | d pre [n_edges][hidden]
+struct TlcEdgeHeadBwdScratch {
+    int64_t cat = 0, hbuf, gpre, total;
+    TlcEdgeHeadBwdScratch(int64_t n_edges, int64_t c, int64_t hidden)
+        : hbuf(n_edges * 2 * c), gpre(hbuf + n_edges * hidden), total(gpre + n_edges * hidden) {}
+};

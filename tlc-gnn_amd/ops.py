@@ -14,6 +14,16 @@ def _f32(t):
     return t.contiguous()
 
 
+def _scratch(size_fn, sizes, dtype, device, extra=0):
+    """The scratch of an entry that takes a bare d_work: `size_fn` (its tlc_*_work_floats / tlc_*_work_ints, host arithmetic over
+    csrc/scratch_layouts.h, the layout the launch carves) gives the element count (tlc_gat_tile_cut_max_tiles: of an output's room); `extra` elements of the caller's own behind it."""
+    import torch
+    count = getattr(_lib.lib(), size_fn)(*map(int, sizes))
+    if count < 0:
+        raise ValueError("%s%r: negative size" % (size_fn, tuple(sizes)))
+    return torch.empty(count + extra, dtype=dtype, device=device)
+
+
 @_lib.on_device_of
 def gcn_norm_csr(edge_index, num_nodes):
     """gcn_norm of GCNConv(cached=True) (Knowledge_Distillation/PD_conv.py:35-70) as CSR by target.
@@ -47,9 +57,9 @@ def csr_by_target(edge_index, num_nodes):
     E, dev = ei.shape[1], ei.device
     rowptr = torch.empty(num_nodes + 1, dtype=torch.int32, device=dev)
     col = torch.empty(E + num_nodes, dtype=torch.int32, device=dev)
-    work = torch.empty(3 * num_nodes + E + 1, dtype=torch.int32, device=dev)             # [temporaries | nnz]
+    work = _scratch("tlc_csr_by_target_work_ints", (num_nodes, E), torch.int32, dev, extra=1)          # [temporaries | nnz]
     rc = _lib.lib().tlc_csr_by_target(C.c_int32(num_nodes), C.c_int64(E), _lib.ptr(ei), _lib.ptr(rowptr), _lib.ptr(col),
-                                      _lib.ptr(work[3 * num_nodes + E:]), _lib.ptr(work), _lib.stream_ptr())
+                                      _lib.ptr(work[-1:]), _lib.ptr(work), _lib.stream_ptr())
     _lib.check(rc, "tlc_csr_by_target")
     return rowptr, col
 
@@ -199,7 +209,7 @@ def gcn2_encode(rowptr, col, val, x, w1, b1, w2, b2, relu=True, renorm=False, ou
     if ws is None:
         if len(_GCN2_WS) >= 4:
             _GCN2_WS.clear()
-        ws = _GCN2_WS[key] = torch.empty(((2 * hidden + d) * n + 12,), dtype=torch.float32, device=dev)
+        ws = _GCN2_WS[key] = _scratch("tlc_gcn2_encode_work_floats", (n, hidden, d), torch.float32, dev)
     if out is None:
         out = torch.empty((n, d), dtype=torch.float32, device=dev)
     flags = C.c_int((1 if relu else 0) | (2 if renorm else 0))
@@ -267,9 +277,6 @@ def gcn_norm_csr_t(edge_index, num_nodes, rowptr):
     return rowptr_t, col_t[:k].contiguous(), val_t[:k].contiguous()
 
 
-GEMM_TN_MAX_SPLITS = 32          # include/tlcgnn.h: tlc_gemm_tn_f32's scratch is 32 * M * N floats
-
-
 @_lib.on_device_of
 def gemm_tn(a, b, out=None):
     """C = A^T @ B for A [K,M], B [K,N] float32 CUDA (tlc_gemm_tn_f32: split-K on the f32 MFMA, partials added in a fixed order).
@@ -285,7 +292,7 @@ def gemm_tn(a, b, out=None):
         M = 1
     if out is None:
         out = torch.empty((M, N), dtype=torch.float32, device=b.device)
-    work = torch.empty(GEMM_TN_MAX_SPLITS * M * N, dtype=torch.float32, device=b.device)
+    work = _scratch("tlc_gemm_tn_work_floats", (M, N), torch.float32, b.device)
     rc = _lib.lib().tlc_gemm_tn_f32(C.c_int32(M), C.c_int32(N), C.c_int64(K), _lib.ptr(a), _lib.ptr(b), _lib.ptr(out), _lib.ptr(work),
                                     _lib.stream_ptr())
     _lib.check(rc, "tlc_gemm_tn_f32")
@@ -295,9 +302,6 @@ def gemm_tn(a, b, out=None):
 def colsum(b):
     """Column sums of b [K,N] -> [N] (the bias gradient of a layer), tlc_gemm_tn_f32 with a column of ones."""
     return gemm_tn(None, b).reshape(-1)
-
-
-LP_DECODE_BWD_WG = 512           # include/tlcgnn.h: tlc_lp_decode_bwd_f32's scratch is 16 n_pairs + 1076 * 512 floats
 
 
 def endpoint_groups(pairs, num_nodes):
@@ -325,7 +329,7 @@ def lp_decode_bwd(pairs, emb_pre, emb, pi, w1, b1, w2, b2, gprob, groups=None):
     node_ptr, slots = endpoint_groups(pairs, n) if groups is None else groups
     gemb = torch.empty((n, emb_pre.shape[1]), dtype=torch.float32, device=dev)
     gw = torch.empty(1076, dtype=torch.float32, device=dev)
-    work = torch.empty(16 * E + 1076 * LP_DECODE_BWD_WG, dtype=torch.float32, device=dev)
+    work = _scratch("tlc_lp_decode_bwd_work_floats", (E,), torch.float32, dev)
     pairs_c = pairs.contiguous()
     rc = _lib.lib().tlc_lp_decode_bwd_f32(C.c_int64(E), _lib.ptr(pairs_c), _lib.ptr(_f32(emb_pre)), _lib.ptr(_f32(emb)), C.c_int32(n),
                                           C.c_int32(emb_pre.shape[1]), _lib.ptr(pi.contiguous()), C.c_int32(pi.shape[1]),
@@ -385,7 +389,7 @@ def nc_linear_bwd(x, w, gy, need_gx=True):
     gx = torch.empty((M, K), dtype=torch.float32, device=dev) if need_gx else None
     gw = torch.empty((N, K), dtype=torch.float32, device=dev)
     gb = torch.empty(N, dtype=torch.float32, device=dev)
-    work = torch.empty(GEMM_TN_MAX_SPLITS * N * max(K, 1), dtype=torch.float32, device=dev)
+    work = _scratch("tlc_nc_linear_bwd_work_floats", (N, K), torch.float32, dev)
     rc = _lib.lib().tlc_nc_linear_bwd_f32(C.c_int32(M), C.c_int32(N), C.c_int32(K), _lib.ptr(x), _lib.ptr(w), _lib.ptr(gy), _lib.ptr(gx),
                                           _lib.ptr(gw), _lib.ptr(gb), _lib.ptr(work), _lib.stream_ptr())
     _lib.check(rc, "tlc_nc_linear_bwd_f32")
@@ -514,7 +518,7 @@ def gat_layer(rowptr, src, x, wl, att, wij, bias, prelu_slope=-1.0, out=None):
     c_out = wl.shape[0]
     if out is None:
         out = torch.empty((n, 2 * c_out), dtype=torch.float32, device=x.device)
-    work = torch.empty(max(n, 1) * (3 * c_out + 4) + c_in * c_out + c_out * (2 * c_out + 4), dtype=torch.float32, device=x.device)
+    work = _scratch("tlc_gat_layer_fwd_work_floats", (max(n, 1), c_in, c_out), torch.float32, x.device)
     rc = _lib.lib().tlc_gat_layer_fwd(C.c_int32(n), _lib.ptr(rowptr), _lib.ptr(src), _lib.ptr(x), C.c_int32(c_in),
                                       C.c_int32(c_out), _lib.ptr(_f32(wl)), _lib.ptr(_f32(att).reshape(-1)), _lib.ptr(_f32(wij)),
                                       _lib.ptr(_f32(bias)), C.c_float(prelu_slope), _lib.ptr(work), _lib.ptr(out),
@@ -538,8 +542,8 @@ def gat_tiles(rowptr, col, n, tile_nodes=GAT_TILE_NODES):
     if n == 0:
         return None
     dev = rowptr.device
-    work = torch.empty(n // 32 + 6, dtype=torch.int32, device=dev)
-    tiles = torch.empty(2 * n // tile_nodes + 3, dtype=torch.int32, device=dev)
+    work = _scratch("tlc_gat_tile_cut_work_ints", (n,), torch.int32, dev)
+    tiles = _scratch("tlc_gat_tile_cut_max_tiles", (n, tile_nodes), torch.int32, dev)
     nt = C.c_int32(0)
     with torch.cuda.device(dev):
         _lib.check(_lib.lib().tlc_gat_tile_cut(C.c_int32(n), _lib.ptr(rowptr), _lib.ptr(col), C.c_int32(tile_nodes), _lib.ptr(work),
@@ -557,8 +561,7 @@ def gat_layer_tiled(rowptr, src, tiles, x, wl, att, wij, bias, prelu_slope=-1.0,
     c_out = wl.shape[0]
     if out is None:
         out = torch.empty((n, 2 * c_out), dtype=torch.float32, device=x.device)
-    n2 = 2 * c_out + 4
-    work = torch.empty(c_in * c_out + c_out * n2 + c_in * n2 + 2 * c_out + 8, dtype=torch.float32, device=x.device)
+    work = _scratch("tlc_gat_layer_tiled_fwd_work_floats", (c_in, c_out), torch.float32, x.device)
     rc = _lib.lib().tlc_gat_layer_tiled_fwd(C.c_int32(n), _lib.ptr(rowptr), _lib.ptr(src), C.c_int32(tiles.numel() - 1), _lib.ptr(tiles),
                                             _lib.ptr(x), C.c_int32(c_in), C.c_int32(c_out), _lib.ptr(_f32(wl)),
                                             _lib.ptr(_f32(att).reshape(-1)), _lib.ptr(_f32(wij)), _lib.ptr(_f32(bias)),
@@ -580,7 +583,7 @@ def edge_head(src, dst, x, w5, b5, prelu_slope, w6, b6, out=None):
     if out is None:
         out = torch.empty((E, 2), dtype=torch.float32, device=x.device)
     n, c, hidden = x.shape[0], x.shape[1], w5.shape[0]
-    work = torch.empty((n + c) * 2 * hidden, dtype=torch.float32, device=x.device)      # per-node projections + packed W5
+    work = _scratch("tlc_edge_head_fwd_work_floats", (n, c, hidden), torch.float32, x.device)
     rc = _lib.lib().tlc_edge_head_fwd(C.c_int64(E), _lib.ptr(src), _lib.ptr(dst), _lib.ptr(x), C.c_int32(c),
                                       _lib.ptr(_f32(w5)), _lib.ptr(_f32(b5)), C.c_int32(hidden), C.c_float(prelu_slope),
                                       _lib.ptr(_f32(w6)), _lib.ptr(_f32(b6)), _lib.ptr(out), C.c_int32(n), _lib.ptr(work),
@@ -603,7 +606,7 @@ def gat_layer_bwd(rowptr, src, x, wl, att, wij, prelu_slope, out, gout, need_gx=
     gatt = torch.empty(c_out, dtype=torch.float32, device=dev)
     gwij = torch.empty((c_out, 2 * c_out), dtype=torch.float32, device=dev)
     gbias = torch.empty(2 * c_out, dtype=torch.float32, device=dev)
-    work = torch.empty(max(n, 1) * (8 * c_out + 5) + 2 * c_out * c_out + c_in * c_out + 4 + c_out * (2 * c_out + 4), dtype=torch.float32, device=dev)
+    work = _scratch("tlc_gat_layer_bwd_work_floats", (max(n, 1), c_in, c_out), torch.float32, dev)
     rc = _lib.lib().tlc_gat_layer_bwd(C.c_int32(n), _lib.ptr(rowptr), _lib.ptr(src), _lib.ptr(x), C.c_int32(c_in), C.c_int32(c_out),
                                       _lib.ptr(_f32(wl)), _lib.ptr(_f32(att).reshape(-1)), _lib.ptr(_f32(wij)), C.c_float(prelu_slope),
                                       _lib.ptr(_f32(out)) if out is not None else None, _lib.ptr(_f32(gout)), _lib.ptr(gx),
@@ -625,7 +628,7 @@ def edge_head_bwd(src, dst, x, w5, b5, prelu_slope, w6, gpd):
     gb5 = torch.empty(hidden, dtype=torch.float32, device=dev)
     gw6 = torch.empty((2, hidden), dtype=torch.float32, device=dev)
     gb6 = torch.empty(2, dtype=torch.float32, device=dev)
-    work = torch.empty(max(E, 1) * (2 * c + 2 * hidden), dtype=torch.float32, device=dev)
+    work = _scratch("tlc_edge_head_bwd_work_floats", (max(E, 1), c, hidden), torch.float32, dev)
     rc = _lib.lib().tlc_edge_head_bwd(C.c_int64(E), _lib.ptr(src), _lib.ptr(dst), _lib.ptr(x), C.c_int32(c), _lib.ptr(_f32(w5)),
                                       _lib.ptr(_f32(b5)), C.c_int32(hidden), C.c_float(prelu_slope), _lib.ptr(_f32(w6)),
                                       _lib.ptr(_f32(gpd)), _lib.ptr(gx), _lib.ptr(gw5), _lib.ptr(gb5), _lib.ptr(gw6), _lib.ptr(gb6),
