@@ -743,6 +743,59 @@ int tlc_sliced_wasserstein(int32_t n_problems, const int64_t* d_xoff, const doub
                            int32_t n_dirs, const double* d_dirs, double scale, int64_t max_points, double* d_loss, double* d_gradX,
                            double* d_gradY, uint8_t* d_status, void* d_work, int64_t work_bytes, void* stream);
 
+/* ---- The general persistence imager and its gradient (csrc/pi_general.hip) --------------------------------------
+ * PersistenceImager.transform of Knowledge_Distillation/pimg.py:354-414 (= sg2dgm/PersistenceImager.pyx:352-403) for any grid, ramp
+ * and Gaussian kernel; tlc_pi_raster stays the kernel of the one configuration the TLC-GNN pipeline uses.
+ *
+ * THE SPECIFICATION (host memory, one per call):
+ *   res_b, res_p   1 .. TLC_PI_MAX_RES pixels along birth and persistence
+ *   h_bpnts float64[res_b + 1], h_ppnts float64[res_p + 1]: the grid lines, strictly increasing -- the imager object's own arrays
+ *                  (its linspace bits); no uniform step is assumed
+ *   h_ramp  float64[4] = (low, high, start, end), end > start: weight low below start, high above end, the line between
+ *   h_sigma float64[3] = (var_b, var_p, cov): positive definite, and |r| < 0.925 for r = cov / sqrt(var_b var_p)
+ *   skew           nonzero: rows of d_pts are (birth, death) and x = death - birth; zero: rows are (birth, x)
+ * THE FUNCTION.  Phi = the standard normal CDF, 0.5 erfc(-z / sqrt 2).  For point i with weight w_i (d_weights[i] where d_weights is
+ * given -- it overrides the ramp --, else the ramp at x_i):
+ *   cov == 0:  image[rb, rp] = sum_i w_i dPhi_b(i, rb) dPhi_p(i, rp),   dPhi_b(i, rb) = Phi((bpnts[rb + 1] - b_i) / sd_b) -
+ *              Phi((bpnts[rb] - b_i) / sd_b), dPhi_p alike in x_i and sd_p (sd = sqrt var): equal or unequal variances;
+ *   cov != 0:  image[rb, rp] = sum_i w_i (F_i(rb + 1, rp + 1) - F_i(rb, rp + 1) - F_i(rb + 1, rp) + F_i(rb, rp)), F_i the bivariate
+ *              normal CDF about point i at a grid corner by the Drezner-Wesolowsky form (Gauss-Legendre over the correlation: 6, 12
+ *              or 20 nodes for |r| < 0.3, < 0.75, beyond); the four corners are combined per point before the sum over the points.
+ * d_out float64[B, res_b * res_p], row-major [birth_bin, pers_bin] in every case (the reference returns the transpose for a
+ * non-isotropic sigma: DESIGN.md 6.8).  Empty diagrams give zero rows; a NaN coordinate makes its own diagram's image NaN.
+ * SUMMATION ORDER of a pixel: a diagram's points in slices of 1 024; inside a slice the points ascending (cov == 0: on the f64 MFMA,
+ * four at a time); the slices ascending.  No floating-point atomics: the bits of an image depend on its diagram and the
+ * specification alone, not on the batch around it, the launch geometry, the workspace or the run.
+ *
+ * d_offs int64[B + 1] and h_offs, the same offsets in host memory (the entry reads nothing back); d_pts float64[n_pts, 2].
+ * d_work: only diagrams above 1 024 points need it (their slices' partial images).  tlc_pi_image_work_bytes (host arithmetic)
+ * returns the size that runs 32 diagrams of max_points per launch and stores in *least (may be NULL) the size for one; any d_work
+ * of at least *least gives the same bits.  0: d_work may be NULL.  -1: a negative size or a resolution out of range.
+ *
+ * tlc_pi_image_vjp: grad_pts float64[n_pts, 2] = d (sum grad_img * image) / d pts, every row written, one wavefront per point, a
+ * fixed order, no atomics.  The ramp's slope is (high - low) / (end - start) for start <= x <= end and 0 outside.
+ *   TLC_PI_GRAD_WEIGHT  the reference's gradient (pimg.py:392,395 detach the CDF factors): through the weight only,
+ *                       g = slope * sum_pixels grad_img * (the point's unweighted contribution); skew: d/d death = g,
+ *                       d/d birth = -g; no skew: only the persistence column receives g.
+ *   TLC_PI_GRAD_FULL    the true derivative, cov == 0 only: it adds the two terms through Phi (the normal densities at the grid
+ *                       lines in place of one of the CDF differences), chained through x = death - birth under the skew.
+ * Explicit weights have no gradient entry (they are constants of the caller).
+ * TLC_ERR_INVALID_ARG, nothing launched: a resolution outside 1 .. TLC_PI_MAX_RES, grid lines not finite or not strictly increasing,
+ * end <= start, a non-finite ramp or sigma, a singular or non-positive-definite sigma, |r| >= 0.925 (the reference's branch for it is
+ * wrong: DESIGN.md 6.8), TLC_PI_GRAD_FULL with cov != 0, an unknown mode, null required pointers, negative sizes, offsets that
+ * decrease or leave 0 .. n_pts, a d_work below *least.  The message of tlc_last_error says which. */
+#define TLC_PI_MAX_RES      128
+#define TLC_PI_GRAD_WEIGHT  0
+#define TLC_PI_GRAD_FULL    1
+int64_t tlc_pi_image_work_bytes(int32_t n_dgms, int64_t max_points, int32_t res_b, int32_t res_p, int64_t* least);
+int tlc_pi_image(int32_t n_dgms, int64_t n_pts, const int64_t* d_offs, const int64_t* h_offs, const double* d_pts,
+                 const double* d_weights, int32_t res_b, int32_t res_p, const double* h_bpnts, const double* h_ppnts,
+                 const double* h_ramp, const double* h_sigma, int32_t skew, double* d_out, void* d_work, int64_t work_bytes,
+                 void* stream);
+int tlc_pi_image_vjp(int32_t n_dgms, int64_t n_pts, const int64_t* d_offs, const double* d_pts, int32_t res_b, int32_t res_p,
+                     const double* h_bpnts, const double* h_ppnts, const double* h_ramp, const double* h_sigma, int32_t skew,
+                     int32_t mode, const double* d_grad_img, double* d_grad_pts, void* stream);
+
 /* ---- what `loss.backward()` runs through the PDGNN layer and the edge head ---------------------------
  * (Knowledge_Distillation/train_Teacher_Model.py:55-62 through gat_conv.py:113-216 and Teacher_model.py:53-59.)
  * tlc_gat_layer_bwd: gradients of one layer, same operands as tlc_gat_layer_fwd.  Nothing of the forward is kept: the node rows,

@@ -34,6 +34,8 @@ PD_WIDE_LDS_NODES = 40000                                           # TLC_PD_WID
 PD_WIDE_BLOCK, PD_WIDE_SORT_TILE, PD_WIDE_SCAN_CHUNK = 256, 4096, 2048   # workgroup width, edges per radix tile, flags per scan chunk (csrc/pd_wide.hip)
 PD_VERT_WAVE_NMAX, PD_VERT_LDS_NMAX = 64, 2048                       # TLC_PD_VERT_*: the size classes of csrc/pd_grad.hip (wavefront / workgroup per graph)
 SW_WAVE_NMAX, SW_LDS_NMAX, SW_MAX_DIRS = 64, 2048, 128              # TLC_SW_*: the size classes of csrc/sliced_w.hip by n + m, and the most directions
+PI_MAX_RES, PI_GRAD_WEIGHT, PI_GRAD_FULL = 128, 0, 1                # TLC_PI_*: the general imager of csrc/pi_general.hip
+PI_SLICE, PI_CHUNK, PI_GROUP = 1024, 32, 32                         # points per K-slice / per LDS chunk, K-split diagrams per launch
 DESCRIPTOR_FLAG ={"sum": 0, "min": DESC_MIN, "max": DESC_MAX}      # the three node values of filtration.build_fv
 
 # every symbol include/tlcgnn.h declares (tests check that the library exports all of them)
@@ -51,6 +53,7 @@ SYMBOLS = [
     "tlc_ollivier_ricci_otd", "tlc_ollivier_ricci_otd_work_bytes", "tlc_pd_wide", "tlc_pd_wide_work_bytes",
     "tlc_pd_grad_work_bytes", "tlc_pd_point_vertices", "tlc_pd_filtration_grad",
     "tlc_sliced_w_work_bytes", "tlc_sliced_wasserstein",
+    "tlc_pi_image_work_bytes", "tlc_pi_image", "tlc_pi_image_vjp",
     "tlc_gcn2_encode_work_floats", "tlc_gemm_tn_work_floats", "tlc_lp_decode_bwd_work_floats", "tlc_nc_linear_bwd_work_floats",
     "tlc_gat_layer_fwd_work_floats", "tlc_gat_layer_tiled_fwd_work_floats", "tlc_gat_tile_cut_work_ints", "tlc_gat_tile_cut_max_tiles",
     "tlc_csr_by_target_work_ints", "tlc_gat_layer_bwd_work_floats", "tlc_edge_head_fwd_work_floats", "tlc_edge_head_bwd_work_floats",
@@ -203,6 +206,12 @@ def lib():
         L.tlc_sliced_w_work_bytes.restype = C.c_int64
         L.tlc_sliced_wasserstein.argtypes = ([C.c_int32] + [C.c_void_p] * 4 + [C.c_int32, C.c_void_p, C.c_double, C.c_int64] + [C.c_void_p] * 5
                                              + [C.c_int64, C.c_void_p])
+        L.tlc_pi_image_work_bytes.argtypes = [C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_int64)]
+        L.tlc_pi_image_work_bytes.restype = C.c_int64
+        L.tlc_pi_image.argtypes = ([C.c_int32, C.c_int64] + [C.c_void_p] * 4 + [C.c_int32, C.c_int32] + [C.c_void_p] * 4 + [C.c_int32, C.c_void_p,
+                                   C.c_void_p, C.c_int64, C.c_void_p])
+        L.tlc_pi_image_vjp.argtypes = ([C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 4
+                                       + [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p])
         # the scratch sizes of the entries that take a bare d_work (csrc/scratch_layouts.h)
         for name, args in (("tlc_gcn2_encode_work_floats", [C.c_int32] * 3), ("tlc_gemm_tn_work_floats", [C.c_int32] * 2),
                            ("tlc_lp_decode_bwd_work_floats", [C.c_int64]), ("tlc_nc_linear_bwd_work_floats", [C.c_int32] * 2),

@@ -4,7 +4,7 @@
 classifier of Knowledge_Distillation/ConvCurv_GIN.py: CurvConv and NcLinear (nc_curv.hip).
 
 torch.autograd only carries the graph: every forward and every backward below is one C-ABI call (`tlc_gat_layer_fwd/_bwd`,
-`tlc_edge_head_fwd/_bwd`, `tlc_w2_partial_matching`, `tlc_sliced_wasserstein`, `tlc_pi_raster` / `tlc_pi_raster_wgrad`) or a few (`tlc_gemm_f32` /
+`tlc_edge_head_fwd/_bwd`, `tlc_w2_partial_matching`, `tlc_sliced_wasserstein`, `tlc_pi_raster` / `tlc_pi_raster_wgrad`, `tlc_pi_image` / `tlc_pi_image_vjp`) or a few (`tlc_gemm_f32` /
 `tlc_spmm_csr_f32` / `tlc_gemm_tn_f32`, `tlc_lp_decode_fused_f32` / `tlc_lp_decode_bwd_f32`); nothing is recomputed with torch ops
 and there is no CPU path.
 """
@@ -132,6 +132,25 @@ class DiagramImage(torch.autograd.Function):
         return g.to(ctx.dtype), None, None
 
 
+class GeneralDiagramImage(torch.autograd.Function):
+    """Images of one or more diagrams under any imager specification (`engine.PiSpec`), [B, Rb * Rp] row-major [birth_bin, pers_bin]
+    in the diagrams' dtype: `tlc_pi_image` forward, `tlc_pi_image_vjp` backward.  mode 'weight' is the reference's gradient
+    (DiagramImage's, generalised to the ramp's slope), 'full' the true derivative, which also moves a point's position."""
+
+    @staticmethod
+    def forward(ctx, pd_hat, offs, spec, mode):
+        pts = pd_hat.detach().to(torch.float64).contiguous()
+        ctx.save_for_backward(pts, offs)
+        ctx.spec, ctx.mode, ctx.dtype = spec, mode, pd_hat.dtype
+        return engine.pi_image(offs, pts, spec).to(pd_hat.dtype)
+
+    @staticmethod
+    def backward(ctx, gimg):
+        pts, offs = ctx.saved_tensors
+        g = engine.pi_image_vjp(offs, pts, gimg.to(torch.float64), ctx.spec, ctx.mode)
+        return g.to(ctx.dtype), None, None, None
+
+
 class ExtendedPersistence(torch.autograd.Function):
     """The exact extended persistence as a differentiable function of the filtration values: (up, down, one, ext0, counts) in the slot
     layout of `engine.pd_from_filtration`, the same values bit for bit.  Every coordinate is a copy of one f[v], so the backward is a
@@ -187,10 +206,27 @@ def pack_rows(points, starts, n_points):
     return points[rows], offs
 
 
-def diagram_image(pd_hat, offs=None, res=5):
+def diagram_image(pd_hat, offs=None, res=5, imager=None, grad='weight'):
+    """Images [B, Rb * Rp] of one or more diagrams, differentiable in the points.  imager=None, grad='weight': the reference's
+    configuration at resolution `res` on `tlc_pi_raster` / `tlc_pi_raster_wgrad` (DiagramImage).  An imager -- a
+    `Knowledge_Distillation.pimg.PersistenceImager` or an `engine.PiSpec` -- or grad='full' routes through the general entries
+    (GeneralDiagramImage); with imager=None the specification is the default one at `res`, itself a valid imager."""
+    if grad not in ("weight", "full"):
+        raise ValueError("diagram_image: grad is %r, not 'weight' or 'full'" % (grad,))
     if offs is None:
         offs = torch.tensor([0, pd_hat.shape[0]], dtype=torch.int64, device=pd_hat.device)
-    return DiagramImage.apply(pd_hat, offs, int(res))
+    if imager is None and grad == "weight":
+        return DiagramImage.apply(pd_hat, offs, int(res))
+    if imager is None:
+        spec = engine.PiSpec.default(int(res))
+    elif isinstance(imager, engine.PiSpec):
+        spec = imager
+    else:
+        if not imager.weight_is_ramp():
+            raise ValueError("diagram_image: the imager's weight is a host callable; its images are forward only "
+                             "(use imager.transform_batch on detached points)")
+        spec = imager.spec(skew=True)
+    return GeneralDiagramImage.apply(pd_hat, offs, spec, grad)
 
 
 def gat_layer(x, wl, att, wij, bias, rowptr, src, prelu_slope=-1.0):

@@ -96,3 +96,14 @@ struct TlcEdgeHeadBwdScratch {
     TlcEdgeHeadBwdScratch(int64_t n_edges, int64_t c, int64_t hidden)
         : hbuf(n_edges * 2 * c), gpre(hbuf + n_edges * hidden), total(gpre + n_edges * hidden) {}
 };
+
+// tlc_pi_image: the partial images [slices][res_b * res_p] of the diagrams above SLICE points, one per slice of SLICE points (the second
+// pass adds a pixel's slices ascending).  In float64 elements.  `least` holds the slices of the largest diagram, `total` those of
+// MAX_GROUP such diagrams (the most one launch takes); diagrams of up to SLICE points need none.
+struct TlcPiImageScratch {
+    static constexpr int64_t SLICE = 1024, MAX_GROUP = 32;
+    static int64_t slices_of(int64_t n_points) { return n_points > SLICE ? (n_points + SLICE - 1) / SLICE : 0; }
+    int64_t partial = 0, least, total;
+    TlcPiImageScratch(int64_t n_dgms, int64_t max_points, int64_t res_b, int64_t res_p)
+        : least(slices_of(max_points) * res_b * res_p), total(std::min<int64_t>(n_dgms, MAX_GROUP) * least) {}
+};

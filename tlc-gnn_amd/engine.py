@@ -680,6 +680,99 @@ def pi_raster_wgrad(offs, pts, grad_img, res=5):
     return out[:pts.shape[0]]
 
 
+class PiSpec:
+    """One specification of the general imager (tlc_pi_image, include/tlcgnn.h): the grid lines as the imager object holds them
+    (bpnts [Rb + 1], ppnts [Rp + 1]), the ramp (low, high, start, end), the covariance (var_b, var_p, cov) and the skew flag.
+    Host data only; the library checks it (a refusal is a TlcError that says why)."""
+
+    def __init__(self, bpnts, ppnts, ramp=(0.0, 1.0, 0.0, 1.0), sigma=(1.0, 1.0, 0.0), skew=True):
+        self.bpnts = np.ascontiguousarray(np.asarray(bpnts, dtype=np.float64).reshape(-1))
+        self.ppnts = np.ascontiguousarray(np.asarray(ppnts, dtype=np.float64).reshape(-1))
+        self.ramp = np.ascontiguousarray(np.asarray(ramp, dtype=np.float64).reshape(4))
+        self.sigma = np.ascontiguousarray(np.asarray(sigma, dtype=np.float64).reshape(3))
+        self.skew = bool(skew)
+
+    @property
+    def resolution(self):
+        return (self.bpnts.size - 1, self.ppnts.size - 1)
+
+    @classmethod
+    def default(cls, res=5):
+        """PersistenceImager(resolution=res) of the reference: unit ranges, sigma = I, the default ramp -- what `pi_raster` computes."""
+        lines = np.linspace(0.0, 1.0 + 1.0 / res, res + 1, endpoint=False, dtype=np.float64)
+        return cls(lines, lines.copy())
+
+    def _c_args(self):
+        p = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
+        rb, rp = self.resolution
+        return (C.c_int32(rb), C.c_int32(rp), p(self.bpnts), p(self.ppnts), p(self.ramp), p(self.sigma), C.c_int32(int(self.skew)))
+
+
+def pi_image_work_bytes(n_dgms, max_points, spec):
+    """(full, least) bytes of `pi_image`'s workspace (tlc_pi_image_work_bytes): 0 unless a diagram has more than _lib.PI_SLICE points;
+    any size from `least` up gives the same bits."""
+    rb, rp = spec.resolution
+    least = C.c_int64(0)
+    full = _lib.lib().tlc_pi_image_work_bytes(C.c_int32(n_dgms), C.c_int64(max_points), C.c_int32(rb), C.c_int32(rp), C.byref(least))
+    if full < 0:
+        _lib.check(1, "tlc_pi_image_work_bytes")
+    return int(full), int(least.value)
+
+
+_PI_WORK_CAP = 1 << 28          # a workspace pi_image allocates itself stays below this unless one diagram needs more
+
+
+@_lib.on_device_of
+def pi_image(offs, pts, spec, weights=None, work=None):
+    """Batched persistence images of any imager specification (tlc_pi_image; csrc/pi_general.hip).
+
+    offs int64[B+1], pts float64[K, 2] CUDA tensors, spec a PiSpec, weights float64[K] (optional: overrides the ramp), work an optional
+    uint8 CUDA workspace -> float64[B, Rb * Rp], row-major [birth_bin, pers_bin].  The offsets are copied to the host once."""
+    torch = _lib.require_gpu()
+    B = offs.numel() - 1
+    rb, rp = spec.resolution
+    out = torch.empty((max(B, 1), rb * rp), dtype=torch.float64, device=offs.device)
+    offs = offs.contiguous()
+    pts = pts.contiguous()
+    assert pts.dtype == torch.float64 and offs.dtype == torch.int64
+    if weights is not None:
+        weights = weights.contiguous()
+        assert weights.dtype == torch.float64 and weights.numel() == pts.shape[0]
+    h_offs = np.ascontiguousarray(offs.cpu().numpy())
+    max_points = int(np.diff(h_offs).max()) if B > 0 else 0
+    nbytes = 0
+    if max_points > _lib.PI_SLICE:
+        if work is None:
+            full, least = pi_image_work_bytes(B, max_points, spec)
+            work = torch.empty(max(least, min(full, _PI_WORK_CAP)), dtype=torch.uint8, device=offs.device)
+        nbytes = work.numel()
+    rc = _lib.lib().tlc_pi_image(C.c_int32(B), C.c_int64(pts.shape[0]), _lib.ptr(offs), h_offs.ctypes.data_as(C.c_void_p),
+                                 _lib.ptr(pts) if pts.numel() else None, _lib.ptr(weights) if weights is not None and weights.numel() else None,
+                                 *spec._c_args(), _lib.ptr(out), _lib.ptr(work) if nbytes else None, C.c_int64(nbytes), _lib.stream_ptr())
+    _lib.check(rc, "tlc_pi_image")
+    return out[:B]
+
+
+@_lib.on_device_of
+def pi_image_vjp(offs, pts, grad_img, spec, mode="weight"):
+    """d (sum grad_img * pi_image) / d pts -> float64[K, 2] (tlc_pi_image_vjp).  mode 'weight': the reference's gradient, through a
+    point's weight only; 'full': the true derivative (separable sigma only)."""
+    if mode not in ("weight", "full"):
+        raise ValueError("pi_image_vjp: mode is %r, not 'weight' or 'full'" % (mode,))
+    torch = _lib.require_gpu()
+    B = offs.numel() - 1
+    pts = pts.contiguous()
+    grad_img = grad_img.contiguous()
+    rb, rp = spec.resolution
+    assert pts.dtype == torch.float64 and grad_img.dtype == torch.float64 and grad_img.numel() == B * rb * rp
+    out = torch.zeros((max(pts.shape[0], 1), 2), dtype=torch.float64, device=offs.device)
+    rc = _lib.lib().tlc_pi_image_vjp(C.c_int32(B), C.c_int64(pts.shape[0]), _lib.ptr(offs.contiguous()), _lib.ptr(pts) if pts.numel() else None,
+                                     *spec._c_args(), C.c_int32(_lib.PI_GRAD_FULL if mode == "full" else _lib.PI_GRAD_WEIGHT),
+                                     _lib.ptr(grad_img) if grad_img.numel() else None, _lib.ptr(out), _lib.stream_ptr())
+    _lib.check(rc, "tlc_pi_image_vjp")
+    return out[:pts.shape[0]]
+
+
 # size tiers of the PD kernel (csrc/tlc_kernels.h) and what the library's timing slots bracket
 TIER_LIMITS = [("pd_tier_small", 64, 128), ("pd_tier_mid", 128, 256), ("pd_tier_medium", 512, 1024), ("pd_tier_large", 2048, 4096)]
 TINY_LIMITS = (16, 24)          # TLC_T_NMAX / TLC_T_MMAX: lane-per-subgraph kernel (plain image batches at resolution 5)

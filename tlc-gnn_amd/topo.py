@@ -45,14 +45,16 @@ def _select(f, node_offs, edge_offs, edges, which, pd_large):
     return pts, offs[::2].contiguous()
 
 
-def images(f, node_offs, edge_offs, edges, which="ord0+ext1", res=5, pd_large="host"):
+def images(f, node_offs, edge_offs, edges, which="ord0+ext1", res=5, pd_large="host", imager=None, grad="weight"):
     """[B, res * res] persistence images of every graph's diagram `which` -- the three images of
     `data_utils_GC.compute_persistence_image` (Ord0 ++ Ext1, Ord0, Ext1) -- as a differentiable function of f, through
     `autograd.diagram_image`.  The imager's gradient is the reference's (pimg.py:354-400): a point's two normal-CDF factors are
-    computed from detached coordinates, so the gradient flows through the point's weight only."""
+    computed from detached coordinates, so the gradient flows through the point's weight only.
+    imager: a `Knowledge_Distillation.pimg.PersistenceImager` (any grid, sigma and ramp; [B, Rb * Rp], `res` is then unused);
+    grad='full': the true derivative, which also follows a point's position -- what matters most under a small sigma."""
     check_which(which)
     pts, offs = _select(f, node_offs, edge_offs, edges, which, pd_large)
-    return autograd.diagram_image(pts, offs, res)
+    return autograd.diagram_image(pts, offs, res, imager=imager, grad=grad)
 
 
 def wasserstein_to(f, node_offs, edge_offs, edges, target_pts, target_offs, which="ord0+ext1", order=2, pd_large="host"):
