@@ -263,6 +263,31 @@ def test_speculative_launches_beyond_their_reserved_slots():
     g.close()
 
 
+@pytest.mark.parametrize("extract", [1, 0])
+def test_arena_overflow_beside_a_heavy_list(extract):
+    """64 pairs on a fresh handle whose arena guess is too small (x_arena = 64; breadth-first kernels: the least arena, 65 536 entries,
+    against 56 x 1 280), one LARGE vicinity (513 nodes, the first size of that tier) and one MEDIUM one: the chunk overflows, the
+    LARGE list is written by its own list-driven FILL and everything below it by the FILL that leaves the heavy tiers' pairs out
+    (fill_mode 2) -- of the extraction and, with extract = 0, of the breadth-first kernels.  Second call: the arena has grown, COUNT's own writes stand.  Same rows
+    both times (to 1e-12, as wherever two paths write a vicinity's entries in different orders: float64 sums of <= 25 terms differ
+    in their last bits only), the oracle's."""
+    import torch
+    from tlc_gnn_amd import engine, synth
+    rs = np.random.RandomState(64 + extract)
+    e = np.concatenate([hub_component(513, 560, rs, 0), hub_component(450, 640, rs, 513)])
+    rowptr, col, w = synth.edges_to_csr(513 + 450, e, rs.uniform(-0.5, 0.9, size=len(e)))
+    pairs = np.array([[0, k] for k in range(1, 9)] + [[513, 513 + k] for k in range(1, 57)])
+    g = engine.DeviceGraph(rowptr, col, w)
+    g.set_option("extract", extract)
+    g.set_option("x_arena", 64)
+    out1, st1 = _check(g, torch, rowptr, col, w, pairs)
+    stats = g.stats()
+    assert stats["tier_large"] == 8 and stats["tier_medium"] == 56, stats
+    out2, st2 = _check(g, torch, rowptr, col, w, pairs)
+    assert np.array_equal(st1, st2) and np.abs(out1 - out2).max() <= 1e-12 * np.abs(out1).max()
+    g.close()
+
+
 @pytest.mark.parametrize("decimals", [None, 1])
 def test_tiny_tier_boundaries_on_and_off(decimals):
     """Components at the limits of the lane-per-subgraph kernel (16 nodes / 24 edges) and just beyond, and the smallest ones:

@@ -190,7 +190,7 @@ struct Workspace {
     int in_call;                   // ... by the call in progress (its statistics are still to be collected)
     int n_pairs;                   // pairs of that chunk
     ChunkCtx ctx;                  // the chunk in flight
-    int own_early;                 // side[4] is this workspace's own stream
+    int own_early;                 // side[TLC_SIDE_EARLY] is this workspace's own stream
     int back_pending;              // its second half has not been submitted yet
 };
 
@@ -617,10 +617,11 @@ extern "C" int tlc_graph_create(int32_t n_nodes, const int32_t* h_rowptr, const 
     // is blocked on an event stalls whatever shares its queue; so the handle keeps within 4 streams per priority, the caller's
     // own stream included (normal priority):
     //   per workspace: main (normal; carries what the caller's stream carries for a single stream-ordered chunk) and
-    //                  side[4], the early chain (high) -- the lead-in of the next chunk must not queue behind this chunk's tiers;
+    //                  side[TLC_SIDE_EARLY], the early chain (high) -- the lead-in of the next chunk must not queue behind this chunk's tiers;
     //   shared by the workspaces (a chunk's tier kernels queue behind the previous chunk's, which is the order they finish in
-    //                  anyway): side[0] SMALL, side[5] TINY, side[3] MID (low), side[6] MEDIUM and its rarely used twin
-    //                  side[2], side[7] MEDWIDE (normal), side[1] the heavy tiers the early pass did not take (high).
+    //                  anyway): the tiers' side streams, each with the stream and the priority class of its row of tlc_tiers
+    //                  (tlc_kernels.h: SMALL, TINY and MID low, the MEDIUM-sized lists normal, the heavy tiers the early pass did
+    //                  not take high).
     // (MEDWIDE, pipelined chunks only: on MEDIUM's stream the few hundred largest MEDIUM-sized vicinities of a batch, 0.38 ms of
     // tier + swap kernel, ran in front of the MEDIUM chain instead of beside it.  A fifth stream of normal priority shares a
     // queue with another one; measured with MEDWIDE in the low / normal / high pool: 0.683 / 0.651 / 0.703 ms per pipelined
@@ -636,6 +637,10 @@ extern "C" int tlc_graph_create(int32_t n_nodes, const int32_t* h_rowptr, const 
     int prio_lo = 0, prio_hi = 0;
     hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
     const int prio_mid = (prio_lo + prio_hi) / 2;
+    const int prio_of[] = {prio_lo, prio_mid, prio_hi};                      // (by TLC_PRIO_*)
+    // (exceptions to "one stream per side index", see the notes under tlc_tiers)
+    const int k_medhi = tlc_tiers[TLC_TIER_MEDHI].side, k_medium = tlc_tiers[TLC_TIER_MEDIUM].side;
+    const int k_medwide = tlc_tiers[TLC_TIER_MEDWIDE].side, k_heavy = tlc_tiers[TLC_TIER_LARGE].side;
     // The streams of the three workspaces in use exist from the start: the runtime deals hardware queues to streams as they are
     // created, and streams that come into being later -- a framework's capture streams, a communicator's -- would otherwise take
     // the queues the second and third workspace get with their first chunk (measured: a HIP graph captured between the handle's
@@ -658,7 +663,7 @@ extern "C" int tlc_graph_create(int32_t n_nodes, const int32_t* h_rowptr, const 
         // (the fourth workspace's own two streams are created when the first chunk lands on it: option n_ws = 4 only)
         if (i == 0 || (eager_streams && i < n_eager)) CK(hipStreamCreateWithPriority(&ws->main, hipStreamNonBlocking, prio_mid));
         for (int k = 0; k < TLC_N_SIDE; ++k) {
-            if (k == 4) {
+            if (k == TLC_SIDE_EARLY) {
                 if (i == 0 || (eager_streams && i < n_eager)) { CK(hipStreamCreateWithPriority(&ws->side[k], hipStreamNonBlocking, prio_hi)); ws->own_early = 1; }
             }
             else if (i > 0) {
@@ -669,16 +674,17 @@ extern "C" int tlc_graph_create(int32_t n_nodes, const int32_t* h_rowptr, const 
                 // chunk's LAST kernel was its MEDWIDE swap, started behind the previous chunk's.  0.576 -> 0.551 ms per pipelined batch;
                 // the other assignments (second workspace's, the MEDIUM list's, the swaps on a stream of their own) were worse
                 // (profiles/r05_stream_assignment.txt)
-                if (i == 2 && k == 7) ws->side[k] = g->ws[0].side[1];
+                if (i == 2 && k == k_medwide) ws->side[k] = g->ws[0].side[k_heavy];
             }
-            else if (k == 2) ws->side[k] = nullptr;                      // (= side[6], set below)
+            else if (k == k_medhi) ws->side[k] = nullptr;                // (= MEDIUM's, set below)
             else {
-                const int pr = k == 1 ? prio_hi : ((k == 6 || k == 7) ? prio_mid : prio_lo);
+                int pr = prio_lo;
+                for (const TlcTier& r : tlc_tiers) if (r.side == k) pr = prio_of[r.prio];
                 CK(hipStreamCreateWithPriority(&ws->side[k], hipStreamNonBlocking, pr));
             }
             CK(hipEventCreateWithFlags(&ws->ev_join[k], hipEventDisableTiming));
         }
-        if (i == 0) ws->side[2] = ws->side[6];
+        if (i == 0) ws->side[k_medhi] = ws->side[k_medium];
         CK(hipEventCreateWithFlags(&ws->ev_fork, hipEventDisableTiming));
         CK(hipEventCreateWithFlags(&ws->ev_early, hipEventDisableTiming));
         CK(hipEventCreateWithFlags(&ws->ev_scan, hipEventDisableTiming));
@@ -725,7 +731,7 @@ extern "C" int tlc_graph_destroy(tlc_graph* g) {
         hipFree(ws->d_cand_list); hipFree(ws->d_early_list); hipFree(ws->E_dir); hipFree(ws->E_lw);
         if (ws->main) hipStreamDestroy(ws->main);
         for (int k = 0; k < TLC_N_SIDE; ++k) {
-            const bool own = (k == 4 && ws->own_early) || (i == 0 && k != 2);   // (the rest are workspace 0's, see tlc_graph_create)
+            const bool own = (k == TLC_SIDE_EARLY && ws->own_early) || (i == 0 && k != tlc_tiers[TLC_TIER_MEDHI].side);   // (the rest are workspace 0's, see tlc_graph_create)
             if (own && ws->side[k]) hipStreamDestroy(ws->side[k]);
             if (ws->ev_join[k]) hipEventDestroy(ws->ev_join[k]);
         }
@@ -769,8 +775,15 @@ __global__ void tlc_wait_started_dev(const int* counter, const int* target, int 
 //   front_join_early   what the chunk's own stream waits for before the general launch (classification / early pass + residency gate)
 //   front_main_scan    the general extraction launch and the scan that publishes the chunk's sizes
 //   front_speculative  (a chunk on its own) the many-Pos MEDIUM list behind the scan, sized from the previous chunk
-#define T0(k, st) do { if ((c.tmask >> (k)) & 1) { TLC_HIP_CHECK(hipEventRecord(c.ev_t[2 * (k)], st)); } } while (0)
-#define T1(k, st) do { if ((c.tmask >> (k)) & 1) { TLC_HIP_CHECK(hipEventRecord(c.ev_t[2 * (k) + 1], st)); c.ev_used[k] = 1; } } while (0)
+// (the second half has a list of its own, above back_read_sizes)
+// the timing events around the launch(es) of slot k, on the stream they run on (tmask: the slots this chunk times, if any)
+static inline hipError_t time_begin(const ChunkCtx& c, int k, hipStream_t st) { return ((c.tmask >> k) & 1) ? hipEventRecord(c.ev_t[2 * k], st) : hipSuccess; }
+static inline hipError_t time_end(const ChunkCtx& c, int k, hipStream_t st) {
+    if ((c.tmask >> k) & 1) c.ev_used[k] = 1;
+    return ((c.tmask >> k) & 1) ? hipEventRecord(c.ev_t[2 * k + 1], st) : hipSuccess;
+}
+// microseconds of host time since the chunk's submission began (TLC_HOST_TRACE)
+static inline double chunk_us(const ChunkCtx& c) { return (double)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - c.ht0).count() * 1e-3; }
 // The arguments of ONE tier launch, by value: the chunk's base plus tier t's list of `count` positions and its diagnostics row,
 // `handoff_cap` hand-off slots at `handoff` (null: the tier kernel runs the cycle swap itself) and the list for tlc_pd_dc_kernel
 // (`dc`: 0 MEDIUM-sized, 1 LARGE (regular launch), 2 LARGE (early launch), counters zeroed with the control block; -1: none).
@@ -784,8 +797,6 @@ static TlcPdParams tier_params(const tlc_graph* g, const Workspace* ws, int t, i
     q.phase_cycles = g->d_phase ? g->d_phase + 32 * t : nullptr;
     return q;
 }
-// timing slot of each tier kernel (TINY is reported with SMALL, MEDHI / MEDWIDE as MEDIUM)
-static const int tslot[TLC_N_TIERS] = {3, 4, 5, 6, 7, 3, 4, 4};
 
 static int front_prepare(tlc_graph* g, Workspace* ws, const int32_t* d_pairs, int n_pairs, int hop, uint32_t flags, int res,
                          const BatchIO& io, hipStream_t s, bool pipelined) {
@@ -968,7 +979,7 @@ static int front_fast(tlc_graph* g, Workspace* ws) {
     if (early) {
         // (the fork of the early chain: ahead of the FAST launch, which runs beside it)
         TLC_HIP_CHECK(hipEventRecord(ws->ev_fork, s));                  // after the memsets (and the one-off bounds)
-        TLC_HIP_CHECK(hipStreamWaitEvent(ws->side[4], ws->ev_fork, 0));
+        TLC_HIP_CHECK(hipStreamWaitEvent(ws->side[TLC_SIDE_EARLY], ws->ev_fork, 0));
     }
     // (the early pass's candidates -- smaller ball >= 511 nodes -- are not the subgraph-list launch's, in either extraction launch)
     vp.early_min_ball = (early && use_x) ? TLC_M_NMAX - 1 : 0;
@@ -1004,7 +1015,7 @@ static int front_early_chain(tlc_graph* g, Workspace* ws) {
     const int32_t* d_pairs = vp.pairs;
     if (early) {
         if ((rc = ensure_early(g, ws, hop, s)) != TLC_OK) return rc;
-        hipStream_t es = ws->side[4];
+        hipStream_t es = ws->side[TLC_SIDE_EARLY];
         // (TLC_INCLUDE_ROOTS adds at most the two roots to a vicinity)
         if (use_x) {
             // exact ball sizes: the candidates of the early pass and the bins the main pass takes first
@@ -1042,10 +1053,10 @@ static int front_early_chain(tlc_graph* g, Workspace* ws) {
         lp.tier_list = ws->d_early_list; lp.tier_count_dev = &ctl->early_count; lp.started = &ctl->early_started;
         lp.slot_entries = 2 * TLC_L_MMAX; lp.A_dir = ws->E_dir; lp.A_lw = ws->E_lw;
         if (hand) lp.dc_inplace = g->opt_dc_inplace;
-        T0(5, es);
+        TLC_HIP_CHECK(time_begin(c, tlc_tiers[TLC_TIER_LARGE].time_slot, es));
         if (((g->opt_tier_mask >> TLC_TIER_LARGE) & 1) && (rc = tlc_launch_pd_tier(TLC_TIER_LARGE, lp, es)) != TLC_OK) return rc;
-        T1(5, es);
-        TLC_HIP_CHECK(hipEventRecord(ws->ev_join[4], es));
+        TLC_HIP_CHECK(time_end(c, tlc_tiers[TLC_TIER_LARGE].time_slot, es));
+        TLC_HIP_CHECK(hipEventRecord(ws->ev_join[TLC_SIDE_EARLY], es));
     }
     return TLC_OK;
 }
@@ -1098,7 +1109,7 @@ static int front_main_scan(tlc_graph* g, Workspace* ws) {
     vp.work_chunk = std::max(2, n_pairs / (pipelined ? 4096 : 8192));
     // (behind a FAST launch the work list is the two top bins only -- a few thousand pairs of 20 - 80 us: one pair per chunk)
     if (fsplit && early) vp.work_chunk = 1;
-    T0(0, s);
+    TLC_HIP_CHECK(time_begin(c, 0, s));
     if (use_x) {
         // (behind a FAST launch this one is left with the pairs whose smaller ball has more than 128 nodes -- a few thousand, 20 - 80 us
         // each on one wavefront.  512-thread workgroups for them instead -- 256 / 512 / 1024 of them -- measured: pipelined batch
@@ -1109,7 +1120,7 @@ static int front_main_scan(tlc_graph* g, Workspace* ws) {
     } else {
         hipLaunchKernelGGL((tlc_vicinity_kernel<false, 64>), dim3(vgrid), dim3(TLC_WAVE), g->vic_lds, s, vp);
     }
-    T1(0, s);
+    TLC_HIP_CHECK(time_end(c, 0, s));
     vp.work_counter = nullptr;
     vp.skip_count = nullptr; vp.big_count = nullptr;      // (the FILL launches below are list-driven)
     TLC_HIP_CHECK(hipGetLastError());
@@ -1117,7 +1128,7 @@ static int front_main_scan(tlc_graph* g, Workspace* ws) {
 
     // exclusive scan of the induced entry counts + tier binning
     const int nb = (n_pairs + TLC_SCAN_BLOCK - 1) / TLC_SCAN_BLOCK;
-    T0(1, s);
+    TLC_HIP_CHECK(time_begin(c, 1, s));
     const unsigned seq = ++ws->pub_seq;
     TlcScanParams sp;
     memset(&sp, 0, sizeof(sp));                              // (every optional pointer null unless set below)
@@ -1155,7 +1166,7 @@ static int front_main_scan(tlc_graph* g, Workspace* ws) {
     sp.h_seq = const_cast<unsigned*>(&ws->h_sync_dev->pub_seq);
     sp.seq = seq;
     hipLaunchKernelGGL(tlc_scan_bin, dim3(nb), dim3(TLC_SCAN_BLOCK), 0, s, sp);
-    T1(1, s);
+    TLC_HIP_CHECK(time_end(c, 1, s));
     TLC_HIP_CHECK(hipGetLastError());
     c.seq = seq;
     c.tiny_bins = sp.tiny_bin_count != nullptr;
@@ -1176,7 +1187,7 @@ static int front_speculative(tlc_graph* g, Workspace* ws) {
     // between the scan and the batch's second-longest chain.  If COUNT overflowed the arena the kernels return at once
     // (abort flag) and the chunk is redone below.
     bool (&used)[TLC_N_SIDE] = c.used;
-    for (int k = 0; k < TLC_N_SIDE; ++k) used[k] = (k == 4) && early;
+    for (int k = 0; k < TLC_N_SIDE; ++k) used[k] = (k == TLC_SIDE_EARLY) && early;
     // The fork point of the side-stream launches that need nothing but the scan.  Recorded here, it is long complete when the
     // host has seen the sizes and submits them, and a wait on a complete event is no command at all -- an event recorded at
     // submission time costs every side stream a barrier packet on a signal that is still in flight: 60 us per chunk (measured:
@@ -1188,18 +1199,16 @@ static int front_speculative(tlc_graph* g, Workspace* ws) {
     int (&spec_cap)[TLC_N_TIERS] = c.spec_cap;
     for (int t = 0; t < TLC_N_TIERS; ++t) { spec_base[t] = 0; spec_cap[t] = 0; }
     if (spec) {
-        spec_cap[TLC_TIER_MID] = std::min(n_pairs, std::max(4096, ws->prev_tc[TLC_TIER_MID] + ws->prev_tc[TLC_TIER_MID] / 4));
-        spec_cap[TLC_TIER_MEDIUM] = std::min(n_pairs, std::max(2048, ws->prev_tc[TLC_TIER_MEDIUM] + ws->prev_tc[TLC_TIER_MEDIUM] / 4));
-        spec_cap[TLC_TIER_MEDHI] = std::min(n_pairs, std::max(1024, ws->prev_tc[TLC_TIER_MEDHI] + ws->prev_tc[TLC_TIER_MEDHI] / 4));
-        spec_cap[TLC_TIER_MEDWIDE] = 0;       // (the scan fills that list only when the split by Pos edges is off, i.e. never beside a speculative launch)
-        if (g->opt_spec_cap > 0)                                        // (tests: reach the paths beyond the reserved slots)
-            for (int t : {TLC_TIER_MID, TLC_TIER_MEDIUM, TLC_TIER_MEDHI}) spec_cap[t] = std::min(spec_cap[t], g->opt_spec_cap);
-        // hand-off buffer: [MID | MEDHI (speculative launch) | MEDIUM | MEDWIDE]
-        spec_base[TLC_TIER_MEDHI] = (size_t)spec_cap[TLC_TIER_MID] * tlc_handoff_slot_bytes(TLC_TIER_MID);
-        spec_base[TLC_TIER_MEDIUM] = spec_base[TLC_TIER_MEDHI] + (size_t)spec_cap[TLC_TIER_MEDHI] * tlc_handoff_slot_bytes(TLC_TIER_MEDHI);
-        spec_base[TLC_TIER_MEDWIDE] = spec_base[TLC_TIER_MEDIUM] + (size_t)spec_cap[TLC_TIER_MEDIUM] * tlc_handoff_slot_bytes(TLC_TIER_MEDIUM);
-        if ((rc = ensure_handoff(g, ws, spec_base[TLC_TIER_MEDWIDE] +
-                                        (size_t)spec_cap[TLC_TIER_MEDWIDE] * tlc_handoff_slot_bytes(TLC_TIER_MEDWIDE))) != TLC_OK) return rc;
+        // slots reserved per tier (tlc_tiers[t].spec_min and a quarter more than the previous chunk had), laid out in tlc_spec_order
+        // (MEDWIDE reserves none: the scan fills that list only when the split by Pos edges is off, i.e. never beside a speculative launch)
+        size_t spec_bytes = 0;
+        for (int t : tlc_spec_order) {
+            if (tlc_tiers[t].spec_min > 0) spec_cap[t] = std::min(n_pairs, std::max(tlc_tiers[t].spec_min, ws->prev_tc[t] + ws->prev_tc[t] / 4));
+            if (g->opt_spec_cap > 0) spec_cap[t] = std::min(spec_cap[t], g->opt_spec_cap);   // (tests: reach the paths beyond the reserved slots)
+            spec_base[t] = spec_bytes;
+            spec_bytes += (size_t)spec_cap[t] * tlc_handoff_slot_bytes(t);
+        }
+        if ((rc = ensure_handoff(g, ws, spec_bytes)) != TLC_OK) return rc;
         // On the caller's stream itself, tier kernels first, then their swap kernels.  (On side streams they would sit behind
         // event waits until the scan is done, and a blocked stream stalls whatever shares its hardware queue -- ROCm maps all
         // streams onto 4 by default: measured, the scan then started 0.1 ms late and took 55 instead of 11 us.)  The fork
@@ -1209,12 +1218,12 @@ static int front_speculative(tlc_graph* g, Workspace* ws) {
         // its swap kernel costs more than the host round trip saves -- measured)
         const int t = TLC_TIER_MEDHI;
         // (the divide and conquer in this chain only if the previous chunk had vicinities for it: the count is not known yet)
-        TlcPdParams q = tier_params(g, ws, t, n_pairs, ws->handoff + spec_base[t], spec_cap[t], ws->prev_dcm > 0 ? 0 : -1);
+        TlcPdParams q = tier_params(g, ws, t, n_pairs, ws->handoff + spec_base[t], spec_cap[t], ws->prev_dcm > 0 ? tlc_tiers[t].dc : TLC_DC_NONE);
         q.A_dir = ws->A_dir; q.A_lw = ws->A_lw;                  // (the base has no arena yet: complete_base)
         q.tier_count_dev = &ws->d_ctl->tier_count[t]; q.grid = spec_cap[t]; q.abort_flag = &ws->d_ctl->bump_overflow;
-        T0(tslot[t], s);
+        TLC_HIP_CHECK(time_begin(c, tlc_tiers[t].time_slot, s));
         if (((g->opt_tier_mask >> t) & 1) && (rc = tlc_launch_pd_tier(t, q, s)) != TLC_OK) return rc;
-        T1(tslot[t], s);
+        TLC_HIP_CHECK(time_end(c, tlc_tiers[t].time_slot, s));
     }
     c.spec = spec;
     return TLC_OK;
@@ -1232,7 +1241,7 @@ static int run_chunk_front(tlc_graph* g, Workspace* ws, const int32_t* d_pairs, 
     if ((rc = front_join_early(g, ws)) != TLC_OK) return rc;
     if ((rc = front_main_scan(g, ws)) != TLC_OK) return rc;
     if ((rc = front_speculative(g, ws)) != TLC_OK) return rc;
-    c.ht_front = (double)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - c.ht0).count() * 1e-3;
+    c.ht_front = chunk_us(c);
     ws->back_pending = 1;
     return TLC_OK;
 }
@@ -1242,16 +1251,13 @@ static inline bool sizes_published(const Workspace* ws) { return ws->h_sync->pub
 
 // a chunk's tier counts into the statistics of the call it belongs to (tlc_pd_pi_batch_stats, tlc_debug_tier_counts)
 static void account_chunk(tlc_graph* g, const int (&tc)[TLC_N_TIERS], int n_early) {
-    for (int t = 0; t <= TLC_TIER_HUGE; ++t) g->last_stats[t] += tc[t];
-    for (int t = 0; t < TLC_N_TIERS; ++t) g->last_tc[t] += tc[t];
-    g->last_stats[TLC_TIER_MEDIUM] += tc[TLC_TIER_MEDWIDE];            // (reported with MEDIUM)
-    g->last_stats[TLC_TIER_MEDIUM] += tc[TLC_TIER_MEDHI];              // (reported with MEDIUM; on its own in [9])
-    g->last_stats[9] += tc[TLC_TIER_MEDHI];
-    g->last_stats[TLC_TIER_SMALL] += tc[TLC_TIER_TINY];                 // (reported with SMALL; on its own in [8])
-    g->last_stats[8] += tc[TLC_TIER_TINY];
-    g->last_stats[TLC_TIER_LARGE] += n_early;
-    g->last_stats[7] += tc[TLC_TIER_MID];
-    g->last_stats[6] += 1;
+    for (int t = 0; t < TLC_N_TIERS; ++t) {
+        g->last_tc[t] += tc[t];
+        g->last_stats[tlc_tiers[t].stat] += tc[t];
+        if (tlc_tiers[t].stat_own >= 0) g->last_stats[tlc_tiers[t].stat_own] += tc[t];
+    }
+    g->last_stats[tlc_tiers[TLC_TIER_LARGE].stat] += n_early;
+    g->last_stats[6] += 1;                                              // (chunks)
 }
 
 // The host's wait for the sizes a chunk's scan publishes (mapped memory, sequence number).  hipStreamSynchronize would also wait for
@@ -1282,258 +1288,286 @@ static void complete_base(const tlc_graph* g, Workspace* ws) {
     pp.started = &ws->d_ctl->stats.large_started;
 }
 
-// The second half of a chunk: waits (on the host) for the sizes the scan publishes, then submits every launch whose grid or
-// buffers depend on them, and joins the side streams into the chunk's stream.
+// The second half of a chunk, by stage like the first: it waits (on the host) for the sizes the scan publishes, then submits every launch
+// whose grid or buffers depend on them, and joins the side streams into the chunk's stream.  The stages read the chunk's context
+// (ChunkCtx; `used`, the side streams with a launch of this chunk, is the one thing they add to) and share what the sizes decide
+// (ChunkBack); a tier's stream, timing slot, hand-off, swap kernel and dc list are its row of tlc_tiers (tlc_kernels.h).  In order:
+//   back_read_sizes      the published sizes; the arena and the HUGE scratch grow to them (tlc_vicinity_sizes: the count-only copy ends it here)
+//   back_fill_overflow   the whole-chunk FILL after the extraction ran out of arena
+//   back_handoff_layout  where each tier's hand-off slots lie
+//   back_complete_spec   the MEDHI list's positions beyond the slots of the speculative launch
+//   back_heavy           LARGE / HUGE: list-driven FILLs and tier kernels, then the residency gate
+//   back_tiny_small      TINY, SMALL                     } (a chunk on its own with the TINY list in size classes: the other way round)
+//   back_medium_sized    MEDWIDE, MEDHI, MEDIUM, MID     }
+//   back_pending_swaps   the swap kernels, behind every list's tier kernel; then run_chunk_back joins and accounts
+// From back_heavy on every list goes through back_launch_tier: the fork of the tier's side stream, its arguments, its kernel, its join event.
+struct ChunkBack {
+    long long total;               // arena entries
+    int tc[TLC_N_TIERS];           // list lengths; a front list (n_hi vicinities of the scan's MEDHI list) counts as MEDIUM's
+    int n_hi, n_early, n_dcm;
+    int todo, heavy;               // vicinities in all lists / in LARGE + HUGE
+    int rest_fill;                 // fill_mode of a FILL of everything below the heavy tiers: 2 beside heavy or early-pass vicinities, else 0
+    bool bumped, filled_all;       // COUNT's writes stand (no arena overflow) / the whole-chunk FILL has run
+    bool spec_done;                // the speculative launch is running (front_speculative), its slots must not move
+    size_t hand_base[TLC_N_TIERS]; // byte offset of a tier's slots in the shared hand-off buffer
+    struct { bool on, timed; TlcPdParams pp; } pend[TLC_N_TIERS];   // a tier's swap kernel, still to be submitted (back_pending_swaps)
+};
+
+static int back_read_sizes(tlc_graph* g, Workspace* ws, ChunkBack& b) {
+    int rc;
+    const ChunkCtx& c = ws->ctx;
+    std::atomic_thread_fence(std::memory_order_acquire);
+    b.total = ws->h_sync->pub_total;
+    for (int t = 0; t < TLC_N_TIERS; ++t) b.tc[t] = ws->h_sync->pub_tier[t];
+    // (the many-Pos part of a pipelined chunk's compact MEDIUM list: one launch with the rest, in front of it)
+    if (c.mh_front) { b.n_hi = b.tc[TLC_TIER_MEDHI]; b.tc[TLC_TIER_MEDIUM] += b.n_hi; b.tc[TLC_TIER_MEDHI] = 0; }
+    g->cnt_n_hi += b.n_hi;
+    // (COUNT's writes stand unless the chunk overflowed the arena: then everything is laid out by the scan and written by FILL)
+    b.bumped = c.bump && ws->h_sync->pub_overflow == 0;
+    if (c.use_x) ws->x_entries_hint = std::max(ws->x_entries_hint, (size_t)std::max<long long>(b.total - (b.bumped ? c.bump_base : 0), 0));
+    if ((rc = ensure_arena(g, ws, (size_t)b.total, b.bumped ? (size_t)std::min<long long>(b.total, (long long)ws->cap_entries) : 0, c.s)) != TLC_OK) return rc;
+    if (b.tc[TLC_TIER_HUGE] > 0 && (rc = ensure_huge(g, ws)) != TLC_OK) return rc;
+    b.n_early = c.early ? ws->h_sync->pub_early : 0;
+    ws->prev_dcm = b.n_dcm = ws->h_sync->pub_dcm;
+    for (int t = 0; t < TLC_N_TIERS; ++t) b.todo += b.tc[t];
+    b.heavy = b.tc[TLC_TIER_LARGE] + b.tc[TLC_TIER_HUGE];
+    b.rest_fill = (b.heavy > 0 || b.n_early > 0) ? 2 : 0;
+    b.spec_done = c.spec && b.bumped;
+    for (int t : tlc_spec_order) {                 // (what the next chunk's speculative launch is sized from)
+        if (b.spec_done && tlc_tiers[t].spec_min > 0) g->cnt_beyond_spec += std::max(b.tc[t] - c.spec_cap[t], 0);
+        ws->prev_tc[t] = b.tc[t];
+    }
+    return TLC_OK;
+}
+
+// the arguments of one FILL launch: fill_mode 1 = the pairs of `list`, 2 = every pair outside the heavy tiers, 0 = every pair
+static TlcVicParams fill_params(const Workspace* ws, int mode, const int* list, int count) {
+    TlcVicParams f = ws->ctx.vp;
+    f.A_dir = ws->A_dir; f.A_lw = ws->A_lw;                  // (the arena in its final place)
+    f.fill_mode = mode; f.fill_list = list; f.fill_count = count; f.work_count_dev = nullptr;
+    if (ws->ctx.use_x) { f.x_fill = 1; f.bump_top = nullptr; }
+    return f;
+}
+
+// The extraction ran out of arena: every vicinity below the heavy tiers is laid out by the scan and written by the
+// breadth-first FILL -- before any tier kernel may read it (that includes the SMALL tier, which has no slots of its own here)
+static int back_fill_overflow(tlc_graph* g, Workspace* ws, ChunkBack& b) {
+    const ChunkCtx& c = ws->ctx;
+    if (!c.use_x || b.bumped || b.todo - b.heavy <= 0) return TLC_OK;
+    if (int rc = tlc_launch_extract(64, c.xgrid, g->x_lds64, fill_params(ws, b.rest_fill, nullptr, 0), c.s); rc != TLC_OK) return rc;
+    b.filled_all = true;
+    return TLC_OK;
+}
+
+// hand-off slots (images only): the tiers with long serial tails run their cycle swap in a second, one-wavefront kernel
+static int back_handoff_layout(tlc_graph* g, Workspace* ws, ChunkBack& b) {
+    const ChunkCtx& c = ws->ctx;
+    if (!c.pi_enabled) return TLC_OK;
+    if (b.spec_done) {
+        // the speculative launch in flight owns its part of the buffer, which must not move: the other tiers' slots were reserved
+        // around it (front_speculative), for spec_cap[] subgraphs each; beyond that a tier runs its cycle swap itself
+        for (int t = 0; t < TLC_N_TIERS; ++t) b.hand_base[t] = c.spec_base[t];
+        return TLC_OK;
+    }
+    size_t hand_total = 0;
+    for (int t = 0; t < TLC_N_TIERS; ++t) {
+        if (tlc_tiers[t].handoff != TLC_HAND_SHARED) continue;           // (none, or a buffer of its own)
+        b.hand_base[t] = hand_total;
+        hand_total += (size_t)b.tc[t] * tlc_handoff_slot_bytes(t);
+    }
+    return ensure_handoff(g, ws, hand_total);
+}
+
+// the speculative launch had one workgroup per reserved slot: list positions beyond them get a launch of their own,
+// behind it on s (tier kernel only: without a slot a subgraph's cycle swap runs in the tier kernel itself)
+static int back_complete_spec(tlc_graph* g, Workspace* ws, const ChunkBack& b) {
+    const ChunkCtx& c = ws->ctx;
+    const int t = TLC_TIER_MEDHI;
+    if (!b.spec_done || b.tc[t] <= c.spec_cap[t]) return TLC_OK;
+    TlcPdParams q = tier_params(g, ws, t, b.tc[t], ws->handoff + c.spec_base[t], c.spec_cap[t], TLC_DC_NONE);
+    q.wi_base = c.spec_cap[t]; q.grid = b.tc[t] - c.spec_cap[t]; q.phase = 1;
+    return ((g->opt_tier_mask >> t) & 1) ? tlc_launch_pd_tier(t, q, c.s) : TLC_OK;
+}
+
+// One list on its tier's side stream: the fork, the arguments, the tier kernel and -- unless a swap kernel is still to follow -- the
+// stream's join event.  (`behind_s`: the launch depends on what was just submitted to s, e.g. a FILL; else only on the scan)
+static int back_launch_tier(tlc_graph* g, Workspace* ws, ChunkBack& b, int t, bool behind_s = true) {
+    int rc;
+    ChunkCtx& c = ws->ctx;
+    const TlcTier& R = tlc_tiers[t];
+    hipStream_t st = ws->side[R.side];
+    if (b.bumped && !behind_s) {
+        TLC_HIP_CHECK(hipStreamWaitEvent(st, ws->ev_scan, 0));    // (not behind the speculative kernels on s)
+    } else {
+        TLC_HIP_CHECK(hipEventRecord(ws->ev_fork, c.s));
+        TLC_HIP_CHECK(hipStreamWaitEvent(st, ws->ev_fork, 0));
+    }
+    const size_t hs = c.pi_enabled ? tlc_handoff_slot_bytes(t) : 0;     // (0: the tier kernel runs the cycle swap itself)
+    unsigned char* handoff = hs ? ws->handoff + b.hand_base[t] : nullptr;
+    if (hs && R.handoff == TLC_HAND_OWN) {
+        // (the early launch may still be using the first TLC_EARLY_SLOTS slots: this launch takes the ones behind them)
+        if ((rc = ensure_handoff_large(g, ws, (size_t)TLC_EARLY_SLOTS + (size_t)b.tc[t])) != TLC_OK) return rc;
+        handoff = ws->handoff_large + (size_t)TLC_EARLY_SLOTS * hs;
+    }
+    // (beside the speculative launch only its reserved slots exist)
+    const int handoff_cap = !handoff ? 0 : (b.spec_done && R.handoff == TLC_HAND_SHARED) ? std::min(b.tc[t], c.spec_cap[t]) : b.tc[t];
+    TlcPdParams q = tier_params(g, ws, t, b.tc[t], handoff, handoff_cap, (R.dc == TLC_DC_MEDIUM && b.n_dcm <= 0) ? TLC_DC_NONE : R.dc);
+    if (t == TLC_TIER_MEDIUM && b.n_hi > 0) { q.tier_list_hi = ws->tier_list + (size_t)TLC_TIER_MEDHI * c.n_pairs; q.n_hi = b.n_hi; }
+    if (t == TLC_TIER_LARGE) q.dc_inplace = g->opt_dc_inplace;
+    // (by size class, largest first, as the scan binned it: a wavefront of that kernel waits for its slowest lane)
+    if (t == TLC_TIER_TINY && c.tiny_bins) {
+        q.tiny_bin_list = ws->tiny_bins; q.tiny_bin_stride = c.n_pairs;
+        for (int k = 0; k < TLC_TINY_BINS; ++k) q.tiny_bin_cnt[k] = ws->h_sync->pub_tiny[k];
+    }
+    const bool timed = R.timed && !(c.early && t == TLC_TIER_LARGE) && !(c.spec && t == TLC_TIER_MEDIUM);   // (those slots time the early launch / MEDHI)
+    if (timed) TLC_HIP_CHECK(time_begin(c, R.time_slot, st));
+    const bool two = hs && R.swap && !(q.flags & TLC_NO_EXT1);
+    if (two) q.phase = 1;                                                                       // (the tier kernel only)
+    if (((g->opt_tier_mask >> t) & 1) && (rc = tlc_launch_pd_tier(t, q, st)) != TLC_OK) return rc;    // (development: tiers timed alone)
+    c.used[R.side] = true;
+    if (two) {
+        b.pend[t].on = true; b.pend[t].timed = timed; b.pend[t].pp = q; b.pend[t].pp.phase = 2;   // (its swap kernel: back_pending_swaps)
+        return TLC_OK;
+    }
+    if (timed) TLC_HIP_CHECK(time_end(c, R.time_slot, st));
+    TLC_HIP_CHECK(hipEventRecord(ws->ev_join[R.side], st));
+    return TLC_OK;
+}
+
+// 1. the heavy tiers first: their subgraphs are filled by a small early pass (8 wavefronts per pair) so that the
+//    long serial tails of the largest vicinities start as soon as possible and overlap everything else
+static int back_heavy(tlc_graph* g, Workspace* ws, ChunkBack& b) {
+    int rc;
+    const ChunkCtx& c = ws->ctx;
+    hipStream_t s = c.s;
+    // (the LARGE tier's hand-off slots BEFORE anything heavy is submitted: growing them frees the old buffer, and hipFree waits
+    // for the device -- behind the HUGE tier kernel that was 6.3 ms in which the host submitted nothing: the long list of the
+    // strong-scaling leg took 33 instead of 26 ms in every call that needed a few slots more than the one before)
+    if (c.pi_enabled && b.tc[TLC_TIER_LARGE] > 0 && (rc = ensure_handoff_large(g, ws, (size_t)TLC_EARLY_SLOTS + (size_t)b.tc[TLC_TIER_LARGE])) != TLC_OK) return rc;
+    TLC_HIP_CHECK(time_begin(c, 2, s));                                  // (slot 2, the FILLs: ended by back_medium_sized)
+    for (int t = TLC_TIER_HUGE; t >= TLC_TIER_LARGE; --t) {
+        if (b.tc[t] <= 0) continue;
+        const TlcVicParams f = fill_params(ws, 1, ws->tier_list + (size_t)t * c.n_pairs, b.tc[t]);
+        // the heavy vicinities get 8 wavefronts each (hop <= 2), so that their many long CSR rows are in flight together
+        if (c.use_x) {
+            // (same entry order as the early pass's slots: rows do not depend on which way a vicinity took)
+            if ((rc = tlc_launch_extract(512, std::min(b.tc[t], TLC_EARLY_WG), g->x_lds512, f, s)) != TLC_OK) return rc;
+        } else if (c.hop <= 2)
+            hipLaunchKernelGGL((tlc_vicinity_kernel<true, 512>), dim3(std::min(b.tc[t], g->vic_slots)), dim3(512), g->vic_lds, s, f);
+        else
+            hipLaunchKernelGGL((tlc_vicinity_kernel<true, 64>), dim3(std::min(b.tc[t], g->vic_slots)), dim3(TLC_WAVE), g->vic_lds, s, f);
+        TLC_HIP_CHECK(hipGetLastError());
+        if ((rc = back_launch_tier(g, ws, b, t)) != TLC_OK) return rc;
+    }
+    // A LARGE workgroup needs nearly all of a CU's LDS.  If the many small workgroups of the other tiers reach the CUs
+    // first, the dispatcher cannot place it until those kernels drain (measured: the whole LARGE tier, the critical
+    // path of the batch, starts ~0.35 ms late).  So the main stream -- and with it the SMALL fork and the MEDIUM fill --
+    // is held until the LARGE workgroups report themselves resident; the wait is bounded (50 us).
+    if (b.tc[TLC_TIER_LARGE] > 0) {
+        hipLaunchKernelGGL(tlc_wait_started, dim3(1), dim3(TLC_WAVE), 0, s, (const int*)c.base.started,
+                           std::min(b.tc[TLC_TIER_LARGE], 192), 5000ll);
+        TLC_HIP_CHECK(hipGetLastError());
+    }
+    return TLC_OK;
+}
+
+// 0. the SMALL tier needs nothing more (its subgraphs were written by the COUNT pass); it is submitted after the
+//    heavy chain so that its many workgroups do not delay that chain's start
+// the lower end of the SMALL tier first: one lane per subgraph, a few hundred latency-bound wavefronts that need 36 KB of
+// LDS each -- they must find room before the other tiers' workgroups take it
+static int back_tiny_small(tlc_graph* g, Workspace* ws, ChunkBack& b) {
+    if (int rc = b.tc[TLC_TIER_TINY] > 0 ? back_launch_tier(g, ws, b, TLC_TIER_TINY, false) : TLC_OK; rc != TLC_OK) return rc;
+    return b.tc[TLC_TIER_SMALL] > 0 ? back_launch_tier(g, ws, b, TLC_TIER_SMALL, false) : TLC_OK;
+}
+
+// 2. the MEDIUM-sized tiers
+static int back_medium_sized(tlc_graph* g, Workspace* ws, ChunkBack& b) {
+    int rc;
+    const ChunkCtx& c = ws->ctx;
+    const int (&tc)[TLC_N_TIERS] = b.tc;
+    if (tc[TLC_TIER_MEDIUM] + tc[TLC_TIER_MEDHI] + tc[TLC_TIER_MEDWIDE] + tc[TLC_TIER_MID] <= 0) {
+        TLC_HIP_CHECK(time_end(c, 2, c.s));
+        return TLC_OK;
+    }
+    if (!b.bumped && !b.filled_all) {
+        const TlcVicParams f = fill_params(ws, b.rest_fill, nullptr, 0);
+        hipLaunchKernelGGL((tlc_vicinity_kernel<true, 64>), dim3(c.vgrid), dim3(TLC_WAVE), g->vic_lds, c.s, f);
+        TLC_HIP_CHECK(hipGetLastError());
+    }
+    TLC_HIP_CHECK(time_end(c, 2, c.s));
+    // (the few vicinities beyond the compact configuration first: the largest of the MEDIUM-sized ones, the longest swaps)
+    if (tc[TLC_TIER_MEDWIDE] > 0 && (rc = back_launch_tier(g, ws, b, TLC_TIER_MEDWIDE, !b.bumped)) != TLC_OK) return rc;
+    if (!b.spec_done && tc[TLC_TIER_MEDHI] > 0 && (rc = back_launch_tier(g, ws, b, TLC_TIER_MEDHI)) != TLC_OK) return rc;
+    // (round 6, again after the first half got shorter and the MEDIUM stream's queue reached 0.82 busy: a workspace's MEDIUM list on
+    // the heavy tiers' stream or on the MEDWIDE stream: +0.7 ... +5 % per pipelined batch in every assignment tried)
+    // (round 6: every other pipelined chunk with the MEDIUM list on the MID stream and the MID list on the MEDIUM stream -- the two
+    // queues would then be 0.57 busy each instead of 0.82 / 0.42 -- measured: +3 % per pipelined batch)
+    if (tc[TLC_TIER_MEDIUM] > 0 && (rc = back_launch_tier(g, ws, b, TLC_TIER_MEDIUM, !b.bumped)) != TLC_OK) return rc;
+    if (tc[TLC_TIER_MID] > 0 && (rc = back_launch_tier(g, ws, b, TLC_TIER_MID, !b.bumped)) != TLC_OK) return rc;
+    return TLC_OK;
+}
+
+// The tier kernels of all lists first, their second kernels (cycle swap / divide and conquer, same stream, behind a tier kernel
+// that runs > 100 us) afterwards: a launch costs the host 3 - 4 us, and with both kernels of a tier submitted together the last
+// list's tier kernel started 84 us after the scan had ended (profiles/r04_bench_timeline.txt).  Option split_launch, default on.
+// (per tier, not per stream: two lists may share a stream)
+static int back_pending_swaps(tlc_graph* g, Workspace* ws, ChunkBack& b) {
+    int rc;
+    const ChunkCtx& c = ws->ctx;
+    for (int t = 0; t < TLC_N_TIERS; ++t) {
+        if (!b.pend[t].on) continue;
+        b.pend[t].on = false;
+        hipStream_t st = ws->side[tlc_tiers[t].side];
+        if (((g->opt_tier_mask >> t) & 1) && (rc = tlc_launch_pd_tier(t, b.pend[t].pp, st)) != TLC_OK) return rc;
+        if (b.pend[t].timed) TLC_HIP_CHECK(time_end(c, tlc_tiers[t].time_slot, st));
+        TLC_HIP_CHECK(hipEventRecord(ws->ev_join[tlc_tiers[t].side], st));
+    }
+    return TLC_OK;
+}
+
+// (development: TLC_HOST_TRACE=1 prints where the submitting thread spends a chunk -- front submitted, sizes seen, tiers submitted)
+static void host_trace_chunk(const tlc_graph* g, const Workspace* ws, double ht_seen) {
+    static const bool host_trace = getenv("TLC_HOST_TRACE") != nullptr;
+    if (!host_trace) return;
+    static std::chrono::steady_clock::time_point last_end;
+    const double gap = (double)std::chrono::duration_cast<std::chrono::nanoseconds>(ws->ctx.ht0 - last_end).count() * 1e-3;
+    fprintf(stderr, "[tlc host] ws%d since-last-chunk %.0f us | front submitted %.0f | sizes seen %.0f | tiers submitted %.0f\n",
+            (int)(ws - g->ws), gap, ws->ctx.ht_front, ht_seen, chunk_us(ws->ctx));
+    last_end = std::chrono::steady_clock::now();
+}
+
 static int run_chunk_back(tlc_graph* g, Workspace* ws) {
     int rc;
-    const ChunkCtx& c = ws->ctx;                    // (read-only: the launches below take their arguments from it by value)
-    // (development: TLC_HOST_TRACE=1 prints where the submitting thread spends a chunk -- front submitted, sizes seen, tiers submitted)
-    static const bool host_trace = getenv("TLC_HOST_TRACE") != nullptr;
-    const auto ht0 = c.ht0;
-    auto ht_us = [&]() { return (double)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - ht0).count() * 1e-3; };
-    const double ht_front = c.ht_front;
-    double ht_seen = 0;
-    hipStream_t s = c.s;
-    const int n_pairs = c.n_pairs, hop = c.hop, pi_enabled = c.pi_enabled, xgrid = c.xgrid, vgrid = c.vgrid;
-    const bool bump = c.bump, use_x = c.use_x, early = c.early, spec = c.spec;
-    const long long bump_base = c.bump_base;
-    const size_t (&spec_base)[TLC_N_TIERS] = c.spec_base;
-    const int (&spec_cap)[TLC_N_TIERS] = c.spec_cap;
-    bool (&used)[TLC_N_SIDE] = ws->ctx.used;        // side streams with a launch of this chunk: the one thing the second half adds to
+    const ChunkCtx& c = ws->ctx;
+    ChunkBack b = {};
     ws->back_pending = 0;
-    if ((rc = wait_for_sizes(ws, s, c.seq)) != TLC_OK) return rc;
-    ht_seen = ht_us();
-    std::atomic_thread_fence(std::memory_order_acquire);
-    const long long total = ws->h_sync->pub_total;
-    int tc[TLC_N_TIERS];
-    for (int t = 0; t < TLC_N_TIERS; ++t) tc[t] = ws->h_sync->pub_tier[t];
-    // (the many-Pos part of a pipelined chunk's compact MEDIUM list: one launch with the rest, in front of it)
-    int n_hi = 0;
-    if (c.mh_front) { n_hi = tc[TLC_TIER_MEDHI]; tc[TLC_TIER_MEDIUM] += n_hi; tc[TLC_TIER_MEDHI] = 0; }
-    g->cnt_n_hi += n_hi;
-    // (COUNT's writes stand unless the chunk overflowed the arena: then everything is laid out by the scan and written by FILL)
-    const bool bumped = bump && ws->h_sync->pub_overflow == 0;
-    if (use_x) ws->x_entries_hint = std::max(ws->x_entries_hint, (size_t)std::max<long long>(total - (bumped ? bump_base : 0), 0));
-    if ((rc = ensure_arena(g, ws, (size_t)total, bumped ? (size_t)std::min<long long>(total, (long long)ws->cap_entries) : 0, s)) != TLC_OK) return rc;
-    if (tc[TLC_TIER_HUGE] > 0 && (rc = ensure_huge(g, ws)) != TLC_OK) return rc;
-
-    const int n_early = early ? ws->h_sync->pub_early : 0;
-    const int n_dcm = ws->h_sync->pub_dcm;
-    ws->prev_dcm = n_dcm;
-    int todo = tc[0] + tc[1] + tc[2] + tc[3] + tc[4] + tc[5] + tc[6] + tc[7];
+    if ((rc = wait_for_sizes(ws, c.s, c.seq)) != TLC_OK) return rc;
+    const double ht_seen = chunk_us(c);
+    if ((rc = back_read_sizes(g, ws, b)) != TLC_OK) return rc;
     if (c.count_only) {
         // tlc_vicinity_sizes: the headers are all it asks for (out_n / out_m: the caller's arrays at this chunk's offset)
-        if ((rc = tlc_launch_copy_sizes(n_pairs, ws->hdr_n, ws->hdr_m2, c.base.out_n, c.base.out_m, s)) != TLC_OK) return rc;
-        todo = 0;
-    }
-    const bool spec_done = spec && bumped;          // the MID / MEDIUM tiers are already running
-    if (spec_done)
-        for (int t : {TLC_TIER_MID, TLC_TIER_MEDIUM, TLC_TIER_MEDHI}) g->cnt_beyond_spec += std::max(tc[t] - spec_cap[t], 0);
-    ws->prev_tc[TLC_TIER_MID] = tc[TLC_TIER_MID]; ws->prev_tc[TLC_TIER_MEDIUM] = tc[TLC_TIER_MEDIUM]; ws->prev_tc[TLC_TIER_MEDHI] = tc[TLC_TIER_MEDHI];
-    ws->prev_tc[TLC_TIER_MEDWIDE] = tc[TLC_TIER_MEDWIDE];
-    if (todo > 0) {
+        if ((rc = tlc_launch_copy_sizes(c.n_pairs, ws->hdr_n, ws->hdr_m2, c.base.out_n, c.base.out_m, c.s)) != TLC_OK) return rc;
+    } else if (b.todo > 0) {
         complete_base(g, ws);
-        // the arguments of one FILL launch: fill_mode 1 = the pairs of `list`, 2 = every pair outside the heavy tiers, 0 = every pair
-        auto fill_params = [&](int mode, const int* list, int count) {
-            TlcVicParams f = c.vp;
-            f.A_dir = ws->A_dir; f.A_lw = ws->A_lw;                  // (the arena in its final place)
-            f.fill_mode = mode; f.fill_list = list; f.fill_count = count; f.work_count_dev = nullptr;
-            if (use_x) { f.x_fill = 1; f.bump_top = nullptr; }
-            return f;
-        };
-        // The extraction ran out of arena: every vicinity below the heavy tiers is laid out by the scan and written by the
-        // breadth-first FILL -- before any tier kernel may read it (that includes the SMALL tier, which has no slots of its own here)
-        bool filled_all = false;
-        if (use_x && !bumped && tc[0] + tc[1] + tc[4] + tc[5] + tc[6] + tc[7] > 0) {
-            const TlcVicParams f = fill_params((tc[TLC_TIER_LARGE] + tc[TLC_TIER_HUGE] > 0 || n_early > 0) ? 2 : 0, nullptr, 0);
-            if ((rc = tlc_launch_extract(64, xgrid, g->x_lds64, f, s)) != TLC_OK) return rc;
-            filled_all = true;
-        }
-        // hand-off slots (images only): the tiers with long serial tails run their cycle swap in a second, one-wavefront kernel
-        size_t hand_base[TLC_N_TIERS] = {0, 0, 0, 0, 0, 0, 0, 0};
-        if (pi_enabled && !spec_done) {
-            size_t hand_total = 0;
-            for (int t = 0; t < TLC_N_TIERS; ++t) {
-                if (t == TLC_TIER_LARGE) continue;                   // (its own buffer)
-                hand_base[t] = hand_total;
-                hand_total += (size_t)tc[t] * tlc_handoff_slot_bytes(t);
-            }
-            if ((rc = ensure_handoff(g, ws, hand_total)) != TLC_OK) return rc;
-        } else if (pi_enabled) {
-            // the speculative launch in flight owns its part of the buffer, which must not move: the MID tier's slots were
-            // reserved in front of it and the MEDIUM tier's behind it, for spec_cap[] subgraphs each; beyond that a tier runs
-            // its cycle swap itself
-            hand_base[TLC_TIER_MID] = 0;
-            hand_base[TLC_TIER_MEDIUM] = spec_base[TLC_TIER_MEDIUM];
-            hand_base[TLC_TIER_MEDWIDE] = spec_base[TLC_TIER_MEDWIDE];
-        }
-        // the speculative launch had one workgroup per reserved slot: list positions beyond them get a launch of their own,
-        // behind it on s (tier kernel only: without a slot a subgraph's cycle swap runs in the tier kernel itself)
-        if (spec_done && tc[TLC_TIER_MEDHI] > spec_cap[TLC_TIER_MEDHI]) {
-            const int t = TLC_TIER_MEDHI;
-            TlcPdParams q = tier_params(g, ws, t, tc[t], ws->handoff + spec_base[t], spec_cap[t], -1);
-            q.wi_base = spec_cap[t]; q.grid = tc[t] - spec_cap[t]; q.phase = 1;
-            if (((g->opt_tier_mask >> t) & 1) && (rc = tlc_launch_pd_tier(t, q, s)) != TLC_OK) return rc;
-        }
-        // The tier kernels of all lists first, their second kernels (cycle swap / divide and conquer, same stream, behind a tier kernel
-        // that runs > 100 us) afterwards: a launch costs the host 3 - 4 us, and with both kernels of a tier submitted together the last
-        // list's tier kernel started 84 us after the scan had ended (profiles/r04_bench_timeline.txt).  Option split_launch, default on.
-        // (per tier, not per stream: two lists may share a stream)
-        struct PendingSwap { bool on; int k; bool timed; TlcPdParams pp; };
-        PendingSwap pend[TLC_N_TIERS];
-        for (int t = 0; t < TLC_N_TIERS; ++t) pend[t].on = false;
-        auto finish_pending_swaps = [&]() -> int {
-            for (int t = 0; t < TLC_N_TIERS; ++t) {
-                if (!pend[t].on) continue;
-                pend[t].on = false;
-                const int k = pend[t].k;
-                hipStream_t ss = ws->side[k];
-                int r = ((g->opt_tier_mask >> t) & 1) ? tlc_launch_pd_tier(t, pend[t].pp, ss) : TLC_OK;
-                if (r != TLC_OK) return r;
-                if (pend[t].timed) T1(tslot[t], ss);
-                TLC_HIP_CHECK(hipEventRecord(ws->ev_join[k], ss));
-            }
-            return TLC_OK;
-        };
-        // (`behind_s`: the launch depends on what was just submitted to s, e.g. a FILL; else only on the scan)
-        auto launch_side = [&](int k, int t, bool behind_s = true) -> int {
-            if (bumped && !behind_s) {
-                TLC_HIP_CHECK(hipStreamWaitEvent(ws->side[k], ws->ev_scan, 0));    // (not behind the speculative kernels on s)
-            } else {
-                TLC_HIP_CHECK(hipEventRecord(ws->ev_fork, s));
-                TLC_HIP_CHECK(hipStreamWaitEvent(ws->side[k], ws->ev_fork, 0));
-            }
-            const size_t hs = pi_enabled ? tlc_handoff_slot_bytes(t) : 0;       // (0: the tier kernel runs the cycle swap itself -- SMALL, MID)
-            unsigned char* handoff = hs ? ws->handoff + hand_base[t] : nullptr;
-            if (hs && t == TLC_TIER_LARGE) {
-                // (the early launch may still be using the first TLC_EARLY_SLOTS slots: this launch takes the ones behind them)
-                if (int r2 = ensure_handoff_large(g, ws, (size_t)TLC_EARLY_SLOTS + (size_t)tc[t]); r2 != TLC_OK) return r2;
-                handoff = ws->handoff_large + (size_t)TLC_EARLY_SLOTS * hs;
-            }
-            const int handoff_cap = (spec_done && (t == TLC_TIER_MID || t == TLC_TIER_MEDIUM || t == TLC_TIER_MEDWIDE)) ? std::min(tc[t], spec_cap[t]) : tc[t];
-            const int dc = t == TLC_TIER_LARGE ? 1 : (((t == TLC_TIER_MEDHI || t == TLC_TIER_MEDWIDE) && n_dcm > 0) ? 0 : -1);
-            TlcPdParams q = tier_params(g, ws, t, tc[t], handoff, handoff_cap, dc);
-            if (t == TLC_TIER_MEDIUM && n_hi > 0) { q.tier_list_hi = ws->tier_list + (size_t)TLC_TIER_MEDHI * n_pairs; q.n_hi = n_hi; }
-            if (t == TLC_TIER_LARGE) q.dc_inplace = g->opt_dc_inplace;
-            const bool timed = !(early && t == TLC_TIER_LARGE) && !(t == TLC_TIER_MEDIUM && spec) && t != TLC_TIER_MEDWIDE;   // (those slots time the early launch / MEDHI / MEDIUM)
-            if (timed) T0(tslot[t], ws->side[k]);
-            const bool two = hs && !(q.flags & TLC_NO_EXT1) &&
-                             (t == TLC_TIER_MEDIUM || t == TLC_TIER_MID || t == TLC_TIER_MEDHI || t == TLC_TIER_MEDWIDE);
-            if (two) q.phase = 1;                                                                       // (the tier kernel only)
-            int r = ((g->opt_tier_mask >> t) & 1) ? tlc_launch_pd_tier(t, q, ws->side[k]) : TLC_OK;    // (development: tiers timed alone)
-            if (r != TLC_OK) return r;
-            used[k] = true;
-            if (two) {
-                pend[t].on = true; pend[t].k = k; pend[t].timed = timed; pend[t].pp = q; pend[t].pp.phase = 2;   // (its swap kernel: finish_pending_swaps)
-                return TLC_OK;
-            }
-            if (timed) T1(tslot[t], ws->side[k]);
-            TLC_HIP_CHECK(hipEventRecord(ws->ev_join[k], ws->side[k]));
-            return TLC_OK;
-        };
-        // 1. the heavy tiers first: their subgraphs are filled by a small early pass (8 wavefronts per pair) so that the
-        //    long serial tails of the largest vicinities start as soon as possible and overlap everything else
-        const int heavy = tc[TLC_TIER_LARGE] + tc[TLC_TIER_HUGE];
-        // (the LARGE tier's hand-off slots BEFORE anything heavy is submitted: growing them frees the old buffer, and hipFree waits
-        // for the device -- behind the HUGE tier kernel that was 6.3 ms in which the host submitted nothing: the long list of the
-        // strong-scaling leg took 33 instead of 26 ms in every call that needed a few slots more than the one before)
-        if (pi_enabled && tc[TLC_TIER_LARGE] > 0 && (rc = ensure_handoff_large(g, ws, (size_t)TLC_EARLY_SLOTS + (size_t)tc[TLC_TIER_LARGE])) != TLC_OK) return rc;
-        T0(2, s);
-        for (int t = TLC_TIER_HUGE; t >= TLC_TIER_LARGE; --t) {
-            if (tc[t] <= 0) continue;
-            const TlcVicParams f = fill_params(1, ws->tier_list + (size_t)t * n_pairs, tc[t]);
-            // the heavy vicinities get 8 wavefronts each (hop <= 2), so that their many long CSR rows are in flight together
-            if (use_x) {
-                // (same entry order as the early pass's slots: rows do not depend on which way a vicinity took)
-                if ((rc = tlc_launch_extract(512, std::min(tc[t], TLC_EARLY_WG), g->x_lds512, f, s)) != TLC_OK) return rc;
-            } else if (hop <= 2)
-                hipLaunchKernelGGL((tlc_vicinity_kernel<true, 512>), dim3(std::min(tc[t], g->vic_slots)), dim3(512), g->vic_lds, s, f);
-            else
-                hipLaunchKernelGGL((tlc_vicinity_kernel<true, 64>), dim3(std::min(tc[t], g->vic_slots)), dim3(TLC_WAVE), g->vic_lds, s, f);
-            TLC_HIP_CHECK(hipGetLastError());
-            if ((rc = launch_side(1, t)) != TLC_OK) return rc;
-        }
-        // A LARGE workgroup needs nearly all of a CU's LDS.  If the many small workgroups of the other tiers reach the CUs
-        // first, the dispatcher cannot place it until those kernels drain (measured: the whole LARGE tier, the critical
-        // path of the batch, starts ~0.35 ms late).  So the main stream -- and with it the SMALL fork and the MEDIUM fill --
-        // is held until the LARGE workgroups report themselves resident; the wait is bounded (50 us).
-        if (tc[TLC_TIER_LARGE] > 0) {
-            hipLaunchKernelGGL(tlc_wait_started, dim3(1), dim3(TLC_WAVE), 0, s, (const int*)c.base.started,
-                               std::min(tc[TLC_TIER_LARGE], 192), 5000ll);
-            TLC_HIP_CHECK(hipGetLastError());
-        }
-        // 0. the SMALL tier needs nothing more (its subgraphs were written by the COUNT pass); it is submitted after the
-        //    heavy chain so that its many workgroups do not delay that chain's start
-        // the lower end of the SMALL tier first: one lane per subgraph, a few hundred latency-bound wavefronts that need 36 KB of
-        // LDS each -- they must find room before the other tiers' workgroups take it
-        auto launch_tiny_small = [&]() -> int {
-            if (tc[TLC_TIER_TINY] > 0) {
-                if (bumped) { TLC_HIP_CHECK(hipStreamWaitEvent(ws->side[5], ws->ev_scan, 0)); }
-                else { TLC_HIP_CHECK(hipEventRecord(ws->ev_fork, s)); TLC_HIP_CHECK(hipStreamWaitEvent(ws->side[5], ws->ev_fork, 0)); }
-                TlcPdParams q = tier_params(g, ws, TLC_TIER_TINY, tc[TLC_TIER_TINY], nullptr, 0, -1);
-                // (by size class, largest first, as the scan binned it: a wavefront of that kernel waits for its slowest lane)
-                if (c.tiny_bins) {
-                    q.tiny_bin_list = ws->tiny_bins; q.tiny_bin_stride = n_pairs;
-                    for (int b = 0; b < TLC_TINY_BINS; ++b) q.tiny_bin_cnt[b] = ws->h_sync->pub_tiny[b];
-                }
-                int r = ((g->opt_tier_mask >> TLC_TIER_TINY) & 1) ? tlc_launch_pd_tiny(q, ws->side[5]) : TLC_OK;
-                if (r != TLC_OK) return r;
-                TLC_HIP_CHECK(hipEventRecord(ws->ev_join[5], ws->side[5]));
-                used[5] = true;
-            }
-            if (tc[TLC_TIER_SMALL] > 0) return launch_side(0, TLC_TIER_SMALL, false);
-            return TLC_OK;
-        };
-        // 2. the MEDIUM-sized tiers
-        auto launch_medium_mid = [&]() -> int {
-            int r;
-            if (tc[TLC_TIER_MEDIUM] + tc[TLC_TIER_MEDHI] + tc[TLC_TIER_MEDWIDE] + tc[TLC_TIER_MID] > 0) {
-                if (!bumped && !filled_all) {
-                    const TlcVicParams f = fill_params((heavy > 0 || n_early > 0) ? 2 : 0, nullptr, 0);
-                    hipLaunchKernelGGL((tlc_vicinity_kernel<true, 64>), dim3(vgrid), dim3(TLC_WAVE), g->vic_lds, s, f);
-                    TLC_HIP_CHECK(hipGetLastError());
-                }
-                T1(2, s);
-                // (the few vicinities beyond the compact configuration first: the largest of the MEDIUM-sized ones, the longest swaps)
-                if (tc[TLC_TIER_MEDWIDE] > 0 && (r = launch_side(7, TLC_TIER_MEDWIDE, !bumped)) != TLC_OK) return r;
-                if (!spec_done && tc[TLC_TIER_MEDHI] > 0 && (r = launch_side(2, TLC_TIER_MEDHI)) != TLC_OK) return r;
-                // (round 6, again after the first half got shorter and the MEDIUM stream's queue reached 0.82 busy: a workspace's MEDIUM list on
-                // the heavy tiers' stream or on the MEDWIDE stream: +0.7 ... +5 % per pipelined batch in every assignment tried)
-                // (round 6: every other pipelined chunk with the MEDIUM list on the MID stream and the MID list on the MEDIUM stream -- the two
-                // queues would then be 0.57 busy each instead of 0.82 / 0.42 -- measured: +3 % per pipelined batch)
-                if (tc[TLC_TIER_MEDIUM] > 0 && (r = launch_side(6, TLC_TIER_MEDIUM, !bumped)) != TLC_OK) return r;
-                if (tc[TLC_TIER_MID] > 0 && (r = launch_side(3, TLC_TIER_MID, !bumped)) != TLC_OK) return r;
-            } else {
-                T1(2, s);
-            }
-            return TLC_OK;
-        };
+        if ((rc = back_fill_overflow(g, ws, b)) != TLC_OK) return rc;
+        if ((rc = back_handoff_layout(g, ws, b)) != TLC_OK) return rc;
+        if ((rc = back_complete_spec(g, ws, b)) != TLC_OK) return rc;
+        if ((rc = back_heavy(g, ws, b)) != TLC_OK) return rc;
         // Submission order.  A chunk on its own with the TINY list in size classes: MEDIUM / MID first -- their tier kernels have a
         // serial second kernel behind them and the lane-per-subgraph kernel, no longer the last to finish, only takes LDS from them
         // when it starts alongside (tools/ab_option.py medium_first 0 1: one batch alone 0.7605 -> 0.7325 ms, pipelined batches equal;
         // with the TINY kernel held back 110 us by an explicit sort it was 0.696).
         // (round 6: MEDIUM / MID first for pipelined chunks too: 0.4884 vs 0.4866 ms, no gain)
-        if (!c.pipelined && c.tiny_bins) {
-            if ((rc = launch_medium_mid()) != TLC_OK) return rc;
-            if ((rc = launch_tiny_small()) != TLC_OK) return rc;
-        } else {
-            if ((rc = launch_tiny_small()) != TLC_OK) return rc;
-            if ((rc = launch_medium_mid()) != TLC_OK) return rc;
-        }
-        if ((rc = finish_pending_swaps()) != TLC_OK) return rc;
+        const bool medium_first = !c.pipelined && c.tiny_bins;
+        if (medium_first && (rc = back_medium_sized(g, ws, b)) != TLC_OK) return rc;
+        if ((rc = back_tiny_small(g, ws, b)) != TLC_OK) return rc;
+        if (!medium_first && (rc = back_medium_sized(g, ws, b)) != TLC_OK) return rc;
+        if ((rc = back_pending_swaps(g, ws, b)) != TLC_OK) return rc;
     }
     for (int k = 0; k < TLC_N_SIDE; ++k)
-        if (used[k]) TLC_HIP_CHECK(hipStreamWaitEvent(s, ws->ev_join[k], 0));
-#undef T0
-#undef T1
-    if (c.call_seq == g->call_seq) { account_chunk(g, tc, n_early); g->last_n_hi += n_hi; }      // (a deferred second half submitted by a LATER call does not count into that call's statistics)
-    if (host_trace) {
-        static std::chrono::steady_clock::time_point last_end;
-        const double gap = (double)std::chrono::duration_cast<std::chrono::nanoseconds>(ht0 - last_end).count() * 1e-3;
-        fprintf(stderr, "[tlc host] ws%d since-last-chunk %.0f us | front submitted %.0f | sizes seen %.0f | tiers submitted %.0f\n",
-                (int)(ws - g->ws), gap, ht_front, ht_seen, ht_us());
-        last_end = std::chrono::steady_clock::now();
-    }
+        if (c.used[k]) TLC_HIP_CHECK(hipStreamWaitEvent(c.s, ws->ev_join[k], 0));
+    if (c.call_seq == g->call_seq) { account_chunk(g, b.tc, b.n_early); g->last_n_hi += b.n_hi; }      // (a deferred second half submitted by a LATER call does not count into that call's statistics)
+    host_trace_chunk(g, ws, ht_seen);
     return TLC_OK;
 }
 
@@ -1572,7 +1606,7 @@ static int acquire_workspace(tlc_graph* g, Workspace** out, bool same) {
         int prio_lo = 0, prio_hi = 0;
         hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
         TLC_HIP_CHECK(hipStreamCreateWithPriority(&ws->main, hipStreamNonBlocking, (prio_lo + prio_hi) / 2));
-        TLC_HIP_CHECK(hipStreamCreateWithPriority(&ws->side[4], hipStreamNonBlocking, prio_hi));
+        TLC_HIP_CHECK(hipStreamCreateWithPriority(&ws->side[TLC_SIDE_EARLY], hipStreamNonBlocking, prio_hi));
         ws->own_early = 1;
     }
     // (round 6, measured and not kept: an asynchronous batch that does NOT wait here -- everything it submits is ordered on the GPU behind the

@@ -2359,22 +2359,8 @@ __global__ __launch_bounds__(256, (RES <= 5 ? 3 : 2)) void tlc_pi_raster_kernel(
 
 // ---- host launchers ------------------------------------------------------------------------------------------------------
 size_t tlc_handoff_slot_bytes(int tier) {
-    switch (tier) {
-        // (MID: none since round 6 -- its tier kernel walks the Pos edges itself.  A 128-thread workgroup with 10.6 KB that keeps a
-        // second wavefront waiting during the walk costs a pipelined batch and the long list nothing against the hand-off record +
-        // tlc_pd_swap_kernel<128, 256> on the same stream, and one batch alone 0.618 -> 0.589 ms: one launch and 4.6 KB out and in
-        // again per vicinity less.  The compact MEDIUM configuration the same way: pipelined batch +5 %, long list +13 %
-        // -- four wavefronts and 26 KB wait for one walker there.  gpurun_out A/Bs: profiles/r06_fused_tiers_ab.txt)
-        case TLC_TIER_MID: return 0;
-        case TLC_TIER_MEDIUM: return handoff_bytes(TLC_C_NMAX, TLC_C_MMAX);
-        case TLC_TIER_MEDHI:
-        case TLC_TIER_MEDWIDE: return handoff_bytes(TLC_M_NMAX, TLC_M_MMAX);
-        // (LARGE keeps the serial cycle swap of its subgraphs with few Pos edges: they are few and the batch waits for the
-        // slowest of them, which runs fastest with a CU to itself -- measured 0.91 vs 1.07 ms with the swap in the shared
-        // one-wavefront kernel; only the subgraphs meant for tlc_pd_dc_kernel are handed off, into a buffer of their own)
-        case TLC_TIER_LARGE: return handoff_bytes(TLC_L_NMAX, TLC_L_MMAX);
-        default: return 0;
-    }
+    const TlcTier& r = tlc_tiers[tier];
+    return r.handoff != TLC_HAND_NONE ? handoff_bytes(r.nm, r.mm) : 0;
 }
 size_t tlc_huge_slot_bytes(int nmax, int mmax) { return al16(make_layout(nmax, mmax, 2, TLC_HUGE_MIN_TABLE).total); }
 
@@ -2382,6 +2368,44 @@ template <class K>
 static int set_lds_limit(K kernel, size_t bytes) {
     if (bytes > 64 * 1024) TLC_HIP_CHECK(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
     return TLC_OK;
+}
+
+// One launch of a kernel that has a PLAIN and a general instance: the LDS limit raised where the launch needs more than the default,
+// then whichever instance `plain` selects.
+using PdKernel = void (*)(TlcPdParams);
+static int launch_pd(bool plain, PdKernel k_plain, PdKernel k_general, int grid, int threads, size_t lds, hipStream_t s, const TlcPdParams& p) {
+    const PdKernel k = plain ? k_plain : k_general;
+    if (int rc = set_lds_limit(k, lds)) return rc;
+    hipLaunchKernelGGL(k, dim3(grid), dim3(threads), lds, s, p);
+    return TLC_OK;
+}
+// ... the tier kernel / the swap kernel of tier T's configuration (tlc_tiers)
+template <int T>
+static int launch_tier_kernel(bool plain, int grid, hipStream_t s, const TlcPdParams& p) {
+    constexpr TlcTier R = tlc_tiers[T];
+    constexpr Layout L = make_layout(R.nm, R.mm, 2);
+    return launch_pd(plain, tlc_pd_tier_kernel<R.nm, R.mm, R.threads, false, true>, tlc_pd_tier_kernel<R.nm, R.mm, R.threads, false>, grid,
+                     R.threads, L.total, s, p);
+}
+template <int T>
+static int launch_swap_kernel(bool plain, int grid, hipStream_t s, const TlcPdParams& p) {
+    constexpr TlcTier R = tlc_tiers[T];
+    constexpr SwapLayout SL = make_swap_layout(R.nm, R.mm);
+    return launch_pd(plain, tlc_pd_swap_kernel<R.nm, R.mm, true>, tlc_pd_swap_kernel<R.nm, R.mm>, grid, 64, SL.total, s, p);
+}
+static_assert(tlc_tiers[TLC_TIER_MEDHI].nm == tlc_tiers[TLC_TIER_MEDWIDE].nm && tlc_tiers[TLC_TIER_MEDHI].mm == tlc_tiers[TLC_TIER_MEDWIDE].mm &&
+              tlc_tiers[TLC_TIER_MEDHI].threads == tlc_tiers[TLC_TIER_MEDWIDE].threads, "MEDHI and MEDWIDE share one case of tlc_launch_pd_tier");
+
+// (development, TLC_HOST_TRACE=1: LDS bytes per workgroup of every kernel of the tiers, once)
+static void trace_tier_lds() {
+    static const bool host_trace = getenv("TLC_HOST_TRACE") != nullptr;
+    static int once = 0;
+    if (!host_trace || once++) return;
+    auto tier = [](int t) { return (size_t)make_layout(tlc_tiers[t].nm, tlc_tiers[t].mm, 2).total; };
+    auto swap = [](int t) { return (size_t)make_swap_layout(tlc_tiers[t].nm, tlc_tiers[t].mm).total; };
+    fprintf(stderr, "[tlc] LDS per workgroup: SMALL %zu | MEDIUM tier %zu swap %zu | MEDWIDE tier %zu swap %zu | MID tier %zu swap %zu | LARGE tier %zu dc %zu\n",
+            tier(TLC_TIER_SMALL), tier(TLC_TIER_MEDIUM), swap(TLC_TIER_MEDIUM), tier(TLC_TIER_MEDWIDE), swap(TLC_TIER_MEDWIDE),
+            tier(TLC_TIER_MID), swap(TLC_TIER_MID), tier(TLC_TIER_LARGE), (size_t)dc_kernel_lds(TLC_L_NMAX, TLC_L_MMAX));
 }
 
 int tlc_launch_pd_tier(int tier, const TlcPdParams& p, void* stream) {
@@ -2392,112 +2416,50 @@ int tlc_launch_pd_tier(int tier, const TlcPdParams& p, void* stream) {
     const int grid = p.grid > 0 ? p.grid : p.tier_count;
     // (the instances with the plain image batch's parameters as constants: tlc_pd_tier_kernel's PLAIN; handle option plain_kernels = 0: the general ones)
     const bool plain = !p.no_plain && p.flags == 0u && p.res == 5 && p.pi_enabled && !p.out_f && !p.out_n && !p.out_edges && !p.out_m;
-    static const bool host_trace = getenv("TLC_HOST_TRACE") != nullptr;
-    if (host_trace) {                                 // (development: LDS bytes per workgroup of every kernel of the tiers)
-        static int once = 0;
-        if (!once++)
-            fprintf(stderr, "[tlc] LDS per workgroup: SMALL %zu | MEDIUM tier %zu swap %zu | MEDWIDE tier %zu swap %zu | MID tier %zu swap %zu | LARGE tier %zu dc %zu\n",
-                    (size_t)make_layout(TLC_S_NMAX, TLC_S_MMAX, 2).total, (size_t)make_layout(TLC_C_NMAX, TLC_C_MMAX, 2).total,
-                    (size_t)make_swap_layout(TLC_C_NMAX, TLC_C_MMAX).total, (size_t)make_layout(TLC_M_NMAX, TLC_M_MMAX, 2).total,
-                    (size_t)make_swap_layout(TLC_M_NMAX, TLC_M_MMAX).total, (size_t)make_layout(TLC_D_NMAX, TLC_D_MMAX, 2).total,
-                    (size_t)make_swap_layout(TLC_D_NMAX, TLC_D_MMAX).total, (size_t)make_layout(TLC_L_NMAX, TLC_L_MMAX, 2).total,
-                    (size_t)dc_kernel_lds(TLC_L_NMAX, TLC_L_MMAX));
-    }
+    trace_tier_lds();
+    int rc = TLC_OK;
     switch (tier) {
-        case TLC_TIER_SMALL: {
-            constexpr Layout L = make_layout(TLC_S_NMAX, TLC_S_MMAX, 2);
+        case TLC_TIER_SMALL:
             // (this tier's footprint is what DESIGN.md's "the tier phase is bound by LDS capacity x time" measured: 4 KB more of it
             // cost the batch 2.5 %, 16 KB more 20 %)
-            if (plain)
-                hipLaunchKernelGGL((tlc_pd_tier_kernel<TLC_S_NMAX, TLC_S_MMAX, 64, false, true>), dim3(p.tier_count), dim3(64),
-                                   L.total, s, p);
-            else
-                hipLaunchKernelGGL((tlc_pd_tier_kernel<TLC_S_NMAX, TLC_S_MMAX, 64, false>), dim3(p.tier_count), dim3(64),
-                                   L.total, s, p);
+            rc = launch_tier_kernel<TLC_TIER_SMALL>(plain, p.tier_count, s, p);
             break;
-        }
-        case TLC_TIER_MEDIUM: {
-            constexpr Layout L = make_layout(TLC_C_NMAX, TLC_C_MMAX, 2);   // (256 threads; 128 measured: DESIGN_HISTORY.md, round 6)
-            if (p.phase != 2) {
-                if (plain)
-                    hipLaunchKernelGGL((tlc_pd_tier_kernel<TLC_C_NMAX, TLC_C_MMAX, 256, false, true>), dim3(grid),
-                                       dim3(256), L.total, s, p);
-                else
-                    hipLaunchKernelGGL((tlc_pd_tier_kernel<TLC_C_NMAX, TLC_C_MMAX, 256, false>), dim3(grid),
-                                       dim3(256), L.total, s, p);
-            }
-            if (deferring && p.phase != 1) {
-                constexpr SwapLayout SL = make_swap_layout(TLC_C_NMAX, TLC_C_MMAX);
-                if (plain) hipLaunchKernelGGL((tlc_pd_swap_kernel<TLC_C_NMAX, TLC_C_MMAX, true>), dim3(grid), dim3(64), SL.total, s, p);
-                else hipLaunchKernelGGL((tlc_pd_swap_kernel<TLC_C_NMAX, TLC_C_MMAX>), dim3(grid), dim3(64), SL.total, s, p);
-            }
+        case TLC_TIER_MEDIUM:                                           // (256 threads; 128 measured: DESIGN_HISTORY.md, round 6)
+            if (p.phase != 2) rc = launch_tier_kernel<TLC_TIER_MEDIUM>(plain, grid, s, p);
+            if (!rc && deferring && p.phase != 1) rc = launch_swap_kernel<TLC_TIER_MEDIUM>(plain, grid, s, p);
             break;
-        }
         case TLC_TIER_MEDHI:
-        case TLC_TIER_MEDWIDE: {
-            constexpr Layout L = make_layout(TLC_M_NMAX, TLC_M_MMAX, 2);
-            // (37.5 KB = four workgroups per CU)
-            if (p.phase != 2) {
-                if (plain)
-                    hipLaunchKernelGGL((tlc_pd_tier_kernel<TLC_M_NMAX, TLC_M_MMAX, 256, false, true>), dim3(grid),
-                                       dim3(256), L.total, s, p);
-                else
-                    hipLaunchKernelGGL((tlc_pd_tier_kernel<TLC_M_NMAX, TLC_M_MMAX, 256, false>), dim3(grid),
-                                       dim3(256), L.total, s, p);
-            }
+        case TLC_TIER_MEDWIDE:                                          // (one configuration: 37.5 KB = four workgroups per CU)
+            if (p.phase != 2) rc = launch_tier_kernel<TLC_TIER_MEDWIDE>(plain, grid, s, p);
             // (a dc list on the launch: the scan counted vicinities with Pos edges enough -- dense hop-1 vicinities of the Amazon
             // shapes, 600 Pos edges on 80 nodes -- and the tier kernel marked them; the rest stay for the swap kernel behind)
-            if (deferring && p.phase != 1 && p.dc_count) {
+            if (!rc && deferring && p.phase != 1 && p.dc_count) {
                 constexpr size_t dcm = dc_kernel_lds(TLC_M_NMAX, TLC_M_MMAX);
                 hipLaunchKernelGGL((tlc_pd_dc_kernel<TLC_M_NMAX, TLC_M_MMAX, 256>), dim3(grid), dim3(256), dcm, s, p);
             }
-            if (deferring && p.phase != 1) {
-                constexpr SwapLayout SL = make_swap_layout(TLC_M_NMAX, TLC_M_MMAX);
-                if (plain) hipLaunchKernelGGL((tlc_pd_swap_kernel<TLC_M_NMAX, TLC_M_MMAX, true>), dim3(grid), dim3(64), SL.total, s, p);
-                else hipLaunchKernelGGL((tlc_pd_swap_kernel<TLC_M_NMAX, TLC_M_MMAX>), dim3(grid), dim3(64), SL.total, s, p);
-            }
+            if (!rc && deferring && p.phase != 1) rc = launch_swap_kernel<TLC_TIER_MEDWIDE>(plain, grid, s, p);
             break;
-        }
-        case TLC_TIER_MID: {
-            constexpr Layout L = make_layout(TLC_D_NMAX, TLC_D_MMAX, 2);
-            if (p.phase != 2) {
-                if (plain)
-                    hipLaunchKernelGGL((tlc_pd_tier_kernel<TLC_D_NMAX, TLC_D_MMAX, TLC_D_THREADS, false, true>), dim3(grid),
-                                       dim3(TLC_D_THREADS), L.total, s, p);
-                else
-                    hipLaunchKernelGGL((tlc_pd_tier_kernel<TLC_D_NMAX, TLC_D_MMAX, TLC_D_THREADS, false>), dim3(grid),
-                                       dim3(TLC_D_THREADS), L.total, s, p);
-            }
-            break;                                                    // (no hand-off: tlc_handoff_slot_bytes)
-        }
-        case TLC_TIER_LARGE: {
-            constexpr Layout L = make_layout(TLC_L_NMAX, TLC_L_MMAX, 2);
+        case TLC_TIER_MID:
+            if (p.phase != 2) rc = launch_tier_kernel<TLC_TIER_MID>(plain, grid, s, p);
+            break;                                                    // (no hand-off: tlc_tiers)
+        case TLC_TIER_TINY:
+            return tlc_launch_pd_tiny(p, stream);                     // (pd_tiny.hip: a kernel of another shape)
+        case TLC_TIER_LARGE:
             // (each kernel asks for its own LDS only, not the whole CU.  Measured: with the divide-and-conquer kernel's 107 of 160 KB a
             // TINY workgroup fits beside it, 0.838 -> 0.818 ms for the PubMed batch; a LARGE workgroup holds its CU for ~0.49 ms of a
             // 0.53 ms pipelined batch (71 of them: 0.065 ms of the batch, profiles/r05_tier_cost_pipelined.txt), and the 15 KB its
             // 145 KB leave are room for two SMALL or one MID / swap workgroup: pipelined batch 0.526 -> 0.517 ms, one batch alone equal)
-            const size_t lds_bytes = L.total;
-            int rc = plain ? set_lds_limit(tlc_pd_tier_kernel<TLC_L_NMAX, TLC_L_MMAX, TLC_L_THREADS, false, true>, lds_bytes)
-                           : set_lds_limit(tlc_pd_tier_kernel<TLC_L_NMAX, TLC_L_MMAX, TLC_L_THREADS, false>, lds_bytes);
-            if (rc) return rc;
-            if (plain)
-                hipLaunchKernelGGL((tlc_pd_tier_kernel<TLC_L_NMAX, TLC_L_MMAX, TLC_L_THREADS, false, true>), dim3(p.tier_count),
-                                   dim3(TLC_L_THREADS), lds_bytes, s, p);
-            else
-                hipLaunchKernelGGL((tlc_pd_tier_kernel<TLC_L_NMAX, TLC_L_MMAX, TLC_L_THREADS, false>), dim3(p.tier_count),
-                                   dim3(TLC_L_THREADS), lds_bytes, s, p);
-            if (deferring) {
+            rc = launch_tier_kernel<TLC_TIER_LARGE>(plain, p.tier_count, s, p);
+            if (!rc && deferring) {
                 // (only the subgraphs marked for the divide and conquer were handed off; tlc_pd_dc_kernel runs the serial walk itself
                 // for those it gives back)
                 constexpr size_t dcl = dc_kernel_lds(TLC_L_NMAX, TLC_L_MMAX);
                 rc = set_lds_limit(tlc_pd_dc_kernel<TLC_L_NMAX, TLC_L_MMAX, TLC_L_THREADS>, dcl);
-                if (rc) return rc;
-                if (p.dc_count && !p.dc_inplace)
+                if (!rc && p.dc_count && !p.dc_inplace)
                     hipLaunchKernelGGL((tlc_pd_dc_kernel<TLC_L_NMAX, TLC_L_MMAX, TLC_L_THREADS>), dim3(p.tier_count),
                                        dim3(TLC_L_THREADS), dcl, s, p);
             }
             break;
-        }
         case TLC_TIER_HUGE: {
             if (p.huge_slots <= 0 || !p.huge_scratch) { tlc_set_error("HUGE tier without scratch"); return TLC_ERR_INVALID_ARG; }
             const int grid = p.tier_count < p.huge_slots ? p.tier_count : p.huge_slots;
@@ -2506,8 +2468,7 @@ int tlc_launch_pd_tier(int tier, const TlcPdParams& p, void* stream) {
             constexpr int huge_lds = 144 * 1024;
             TlcPdParams q = p;
             q.huge_lds = huge_lds;
-            int rc = set_lds_limit(tlc_pd_tier_kernel<0, 0, 256, true>, (size_t)huge_lds);
-            if (rc) return rc;
+            if ((rc = set_lds_limit(tlc_pd_tier_kernel<0, 0, 256, true>, (size_t)huge_lds)) != TLC_OK) return rc;
             hipLaunchKernelGGL((tlc_pd_tier_kernel<0, 0, 256, true>), dim3(grid), dim3(256), (size_t)huge_lds, s, q);
             break;
         }
@@ -2515,31 +2476,29 @@ int tlc_launch_pd_tier(int tier, const TlcPdParams& p, void* stream) {
             tlc_set_error("bad tier");
             return TLC_ERR_INVALID_ARG;
     }
+    if (rc) return rc;
     TLC_HIP_CHECK(hipGetLastError());
+    return TLC_OK;
+}
+
+// the kernel of tier T's configuration for a caller-supplied filtration
+template <int T>
+static int launch_pdf_kernel(const TlcPdfParams& p, hipStream_t s) {
+    constexpr TlcTier R = tlc_tiers[T];
+    constexpr Layout L = make_layout(R.nm, R.mm, 2);
+    if (int rc = set_lds_limit(tlc_pdf_tier_kernel<R.nm, R.mm, R.threads, false>, L.total)) return rc;
+    hipLaunchKernelGGL((tlc_pdf_tier_kernel<R.nm, R.mm, R.threads, false>), dim3(p.count), dim3(R.threads), L.total, s, p);
     return TLC_OK;
 }
 
 int tlc_launch_pdf_tier(int tier, const TlcPdfParams& p, void* stream) {
     hipStream_t s = (hipStream_t)stream;
     if (p.count <= 0) return TLC_OK;
+    int rc = TLC_OK;
     switch (tier) {
-        case TLC_TIER_SMALL: {
-            constexpr Layout L = make_layout(TLC_S_NMAX, TLC_S_MMAX, 2);
-            hipLaunchKernelGGL((tlc_pdf_tier_kernel<TLC_S_NMAX, TLC_S_MMAX, 64, false>), dim3(p.count), dim3(64), L.total, s, p);
-            break;
-        }
-        case TLC_TIER_MEDIUM: {
-            constexpr Layout L = make_layout(TLC_M_NMAX, TLC_M_MMAX, 2);
-            hipLaunchKernelGGL((tlc_pdf_tier_kernel<TLC_M_NMAX, TLC_M_MMAX, 256, false>), dim3(p.count), dim3(256), L.total, s, p);
-            break;
-        }
-        case TLC_TIER_LARGE: {
-            constexpr Layout L = make_layout(TLC_L_NMAX, TLC_L_MMAX, 2);
-            int rc = set_lds_limit(tlc_pdf_tier_kernel<TLC_L_NMAX, TLC_L_MMAX, 512, false>, L.total);
-            if (rc) return rc;
-            hipLaunchKernelGGL((tlc_pdf_tier_kernel<TLC_L_NMAX, TLC_L_MMAX, 512, false>), dim3(p.count), dim3(512), L.total, s, p);
-            break;
-        }
+        case TLC_TIER_SMALL: rc = launch_pdf_kernel<TLC_TIER_SMALL>(p, s); break;
+        case TLC_TIER_MEDIUM: rc = launch_pdf_kernel<TLC_TIER_MEDWIDE>(p, s); break;      // (no compact configuration here: the wide one)
+        case TLC_TIER_LARGE: rc = launch_pdf_kernel<TLC_TIER_LARGE>(p, s); break;
         case TLC_TIER_HUGE: {
             if (p.huge_slots <= 0 || !p.huge_scratch) { tlc_set_error("HUGE tier without scratch"); return TLC_ERR_INVALID_ARG; }
             const int grid = p.count < p.huge_slots ? p.count : p.huge_slots;
@@ -2550,6 +2509,7 @@ int tlc_launch_pdf_tier(int tier, const TlcPdfParams& p, void* stream) {
             tlc_set_error("bad tier");
             return TLC_ERR_INVALID_ARG;
     }
+    if (rc) return rc;
     TLC_HIP_CHECK(hipGetLastError());
     return TLC_OK;
 }

@@ -16,15 +16,15 @@
 #define TLC_TIER_MEDIUM 1
 #define TLC_TIER_LARGE 2
 #define TLC_TIER_HUGE 3
-#define TLC_TIER_MID 4      /* the lower end of MEDIUM (reported with it): 128 threads, ~10 KB of LDS, 8 workgroups per CU */
-#define TLC_TIER_MEDHI 6    /* a chunk on its own only: the MEDIUM-sized vicinities with many Pos edges or beyond the compact configuration
-                               (reported with MEDIUM): the wide kernels, launched FIRST and on the critical stream, so that their long
+#define TLC_TIER_MID 4      /* the lower end of MEDIUM: 128 threads, ~10 KB of LDS, 8 workgroups per CU */
+#define TLC_TIER_MEDHI 6    /* a chunk on its own only: the MEDIUM-sized vicinities with many Pos edges or beyond the compact configuration:
+                               the wide kernels, launched FIRST and on the critical stream, so that their long
                                serial cycle swaps overlap the rest of the MEDIUM tier */
 #ifndef TLC_MH_MIN_POS             /* (overridable for a threshold sweep: make EXTRA=-DTLC_MH_MIN_POS=n) */
 #define TLC_MH_MIN_POS 120
 #endif
-#define TLC_TIER_TINY 5     /* the lower end of SMALL (reported with it): ONE LANE per subgraph, 64 subgraphs per wavefront (pd_tiny.hip) */
-#define TLC_TIER_MEDWIDE 7  /* pipelined chunks only (no MEDHI list there): the upper end of MEDIUM (reported with it), more than TLC_C_NMAX
+#define TLC_TIER_TINY 5     /* the lower end of SMALL: ONE LANE per subgraph, 64 subgraphs per wavefront (pd_tiny.hip) */
+#define TLC_TIER_MEDWIDE 7  /* pipelined chunks only (no MEDHI list there): the upper end of MEDIUM, more than TLC_C_NMAX
                                nodes or TLC_C_MMAX edges.  MEDIUM runs the kernels sized for TLC_C_NMAX / TLC_C_MMAX (26 KB of LDS, six
                                workgroups per CU; cycle swap 14 KB, eleven wavefronts per CU), MEDHI and this tier the ones sized for
                                TLC_M_NMAX / TLC_M_MMAX (37 KB, four; 20 KB, eight) */
@@ -77,6 +77,50 @@
 #define TLC_L_MMAX 4096
 #define TLC_L_THREADS 512   /* 1024 measured slower (0.99 vs 0.94 ms): barriers over 16 wavefronts, 128-VGPR cap */
 #define TLC_HUGE_MIN_TABLE 16384  /* bytes reserved for the image table in a HUGE scratch slot */
+
+// ---- What the host knows about a tier: ONE row per TLC_TIER_*, read directly (tlc_tiers[t].side ...).  What depends on the chunk
+// (early, spec, bumped, n_dcm > 0, pi_enabled, TLC_NO_EXT1) stays code at its single use in api.hip and reads the row for the tier part.
+enum { TLC_PRIO_LOW, TLC_PRIO_NORMAL, TLC_PRIO_HIGH };          // priority class of a side stream (tlc_graph_create has the measurements)
+enum { TLC_HAND_NONE, TLC_HAND_SHARED, TLC_HAND_OWN };          // hand-off slots: none / in the workspace's shared buffer / in a buffer of the tier's own
+enum { TLC_DC_NONE = -1, TLC_DC_MEDIUM = 0, TLC_DC_LARGE = 1 }; // list for tlc_pd_dc_kernel the tier feeds (index of ChunkCtl::dc; [2]: the early LARGE launch)
+struct TlcTier {
+    const char* name;
+    int nm, mm, threads;   // the kernel configuration it runs: S, D, C, M, L; HUGE has no fixed size; TINY: a lane per subgraph (pd_tiny.hip)
+    int side, prio;        // its side stream (Workspace::side[]) and that stream's priority class
+    int time_slot;         // its timing slot (tlc_pd_pi_batch_timings; 0 - 2 are the extraction, the scan and the FILLs) ...
+    bool timed;            // ... which its launch brackets, or leaves to the tier it shares the slot with (TINY to SMALL, MEDWIDE to MEDIUM)
+    int stat, stat_own;    // the slot of last_stats it is reported in, and the slot that counts it on its own (-1: none)
+    int handoff;           // TLC_HAND_*: the cycle swap + image of a subgraph left to a second kernel through a hand-off slot
+    bool swap;             // ... to tlc_pd_swap_kernel, behind its tier kernel
+    int dc;                // TLC_DC_* (MEDIUM-sized: only in a chunk whose scan counted vicinities for it)
+    int spec_min;          // hand-off slots the speculative launch reserves for it at least (0: none)
+};
+#define TLC_SIDE_EARLY 4   /* side[4] carries no tier list: the early chain (classification, early pass, early LARGE launch), high priority, one per workspace */
+constexpr TlcTier tlc_tiers[] = {
+    //  name       nm          mm          threads        side prio             slot  timed stat own  hand-off         swap   dc             spec_min
+    {"SMALL",   TLC_S_NMAX, TLC_S_MMAX, 64,            0, TLC_PRIO_LOW,    3, true,  0, -1, TLC_HAND_NONE,   false, TLC_DC_NONE,   0},
+    {"MEDIUM",  TLC_C_NMAX, TLC_C_MMAX, 256,           6, TLC_PRIO_NORMAL, 4, true,  1, -1, TLC_HAND_SHARED, true,  TLC_DC_NONE,   2048},
+    {"LARGE",   TLC_L_NMAX, TLC_L_MMAX, TLC_L_THREADS, 1, TLC_PRIO_HIGH,   5, true,  2, -1, TLC_HAND_OWN,    false, TLC_DC_LARGE,  0},
+    {"HUGE",    0,          0,          256,           1, TLC_PRIO_HIGH,   6, true,  3, -1, TLC_HAND_NONE,   false, TLC_DC_NONE,   0},
+    {"MID",     TLC_D_NMAX, TLC_D_MMAX, TLC_D_THREADS, 3, TLC_PRIO_LOW,    7, true,  7, -1, TLC_HAND_NONE,   false, TLC_DC_NONE,   4096},
+    {"TINY",    TLC_T_NMAX, TLC_T_MMAX, 64,            5, TLC_PRIO_LOW,    3, false, 0, 8,  TLC_HAND_NONE,   false, TLC_DC_NONE,   0},
+    {"MEDHI",   TLC_M_NMAX, TLC_M_MMAX, 256,           2, TLC_PRIO_NORMAL, 4, true,  1, 9,  TLC_HAND_SHARED, true,  TLC_DC_MEDIUM, 1024},
+    {"MEDWIDE", TLC_M_NMAX, TLC_M_MMAX, 256,           7, TLC_PRIO_NORMAL, 4, false, 1, -1, TLC_HAND_SHARED, true,  TLC_DC_MEDIUM, 0},
+};
+static_assert(sizeof(tlc_tiers) / sizeof(tlc_tiers[0]) == TLC_N_TIERS, "one row per tier");
+// Two exceptions (tlc_graph_create): side[2] is no stream of its own -- MEDHI's rarely used list shares MEDIUM's stream, side[2] = side[6],
+// and keeps a join event of its own -- and the third workspace's MEDWIDE list goes to the heavy tiers' stream (measured there).
+// The order of the tiers in the speculative launch's hand-off buffer (api.hip, front_speculative):
+constexpr int tlc_spec_order[] = {TLC_TIER_MID, TLC_TIER_MEDHI, TLC_TIER_MEDIUM, TLC_TIER_MEDWIDE};
+// Why MID has no hand-off and LARGE a buffer of its own:
+// (MID: none since round 6 -- its tier kernel walks the Pos edges itself.  A 128-thread workgroup with 10.6 KB that keeps a
+// second wavefront waiting during the walk costs a pipelined batch and the long list nothing against the hand-off record +
+// tlc_pd_swap_kernel<128, 256> on the same stream, and one batch alone 0.618 -> 0.589 ms: one launch and 4.6 KB out and in
+// again per vicinity less.  The compact MEDIUM configuration the same way: pipelined batch +5 %, long list +13 %
+// -- four wavefronts and 26 KB wait for one walker there.  gpurun_out A/Bs: profiles/r06_fused_tiers_ab.txt)
+// (LARGE keeps the serial cycle swap of its subgraphs with few Pos edges: they are few and the batch waits for the
+// slowest of them, which runs fastest with a CU to itself -- measured 0.91 vs 1.07 ms with the swap in the shared
+// one-wavefront kernel; only the subgraphs meant for tlc_pd_dc_kernel are handed off, into a buffer of their own)
 
 // Node record of tlc_extract_kernel (extract.hip): what a sweep needs of a member node in ONE 64-byte line -- where its CSR row
 // starts, its degree, its index in the heavy set (or -1) and its first four entries (n_in = min(degree, 4) of them)
