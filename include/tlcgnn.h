@@ -59,7 +59,8 @@ extern "C" {
 #define TLC_ST_NOT_CONVERGED   6   /* tlc_hks_batch: the Jacobi sweeps did not converge within their bound; slice untouched */
 #define TLC_ST_BAD_INPUT       7   /* tlc_hks_batch, tlc_struct_batch: offsets out of order / beyond the totals, an edge with an id outside
                                       0 .. n-1, a self loop (nothing of it is dereferenced) or an unordered pair listed
-                                      more than once, in either orientation; slice untouched */
+                                      more than once, in either orientation; slice untouched.  tlc_graph_components: the
+                                      offsets and the ids only (loops and repeats are its input) */
 
 /* ---- variant flags (one kernel family serves the TLC-GNN and the PDGNN forks) ---- */
 #define TLC_KEEP_ZERO_PERS   0x01u /* Knowledge_Distillation/accelerated_PD.py:68-69,108-109,169-170 */
@@ -583,6 +584,52 @@ int tlc_struct_batch_work_bytes(int64_t n_graphs, int64_t total_nodes, int64_t t
 int tlc_struct_batch(const int64_t* d_node_ptr, const int64_t* d_edge_ptr, const int32_t* d_edges, int64_t n_graphs,
                      int64_t total_nodes, int64_t total_edges, uint32_t kinds, uint32_t flags, double* d_out,
                      uint8_t* d_status, void* d_work, int64_t work_bytes, void* stream);
+
+/* ---- Connected components of a packed batch of RAW edge lists, the largest one extracted (Knowledge_Distillation/data_utils_GC.py:
+ * 240-248: self loops removed, nx.Graph, the largest connected component, convert_node_labels_to_integers) ------------------------------
+ * Input: the packed batch of tlc_hks_batch (d_node_ptr / d_edge_ptr int64[n_graphs + 1], d_edges int32[total_edges, 2] local ids), but
+ * the edges as a dataset gives them: both orientations, repeated pairs and self loops are allowed and dropped.  For graph g of n nodes
+ * (the specification is `data_utils_GC.largest_component`, integer for integer):
+ *   the simple graph = the distinct unordered pairs {a, b}, a != b;
+ *   the chosen component = the one with the most nodes, among equals the one that holds the lowest node id (n >= 1 without an edge:
+ *   node 0 alone);
+ *   its nodes are renumbered 0 .. k-1 in ascending order of the old ids, its edges written as rows (lo, hi), lo < hi, in ascending
+ *   lexicographic order.
+ * Outputs in SLOT layout (graph g's slices start at its input offsets, like the diagrams of tlc_pd_from_filtration):
+ *   d_info int32[n_graphs, 4]: k = nodes of the chosen component, m = its distinct edges, c = components of the simple graph (an
+ *   isolated node is one), s = distinct non-loop pairs of the whole graph; a graph without nodes: 0 0 0 0;
+ *   d_new_id int32[total_nodes]: the new id of a kept node, -1 for a dropped one (every entry of a computed graph is written);
+ *   d_out_edges int32[total_edges, 2]: the first m rows of slot g; the rest of the slot is left untouched;
+ *   d_status uint8[n_graphs]: TLC_ST_OK, or TLC_ST_BAD_INPUT -- offsets that are negative, decrease or pass the totals, more nodes than
+ *   max_nodes, or an id outside 0 .. n-1, which is found before anything is indexed by it.  A refused graph has nothing written (its
+ *   d_info row included) and no other graph is affected.
+ * Everything is an integer and the only atomics are integer: a component's label is its lowest node id, the unique fixed point of
+ * min-label hooking, counts are integer sums, and the edge order is the order of the sorted keys -- the outputs are the same bits run to
+ * run, alone or anywhere in any batch, with any workspace of at least the reported size, whatever number of labelling rounds ran.
+ * Size classes, binned on the device from d_node_ptr:
+ *   WAVE  n <= TLC_CC_WAVE_NMAX: a wavefront per graph (four per workgroup, persistent, graphs drawn by a ticket).  Lane v owns row v of
+ *         the adjacency matrix as one u64 in LDS (atomicOr: repeats and orientation fold into the bit, loops are masked); the rows are
+ *         closed in registers by one Warshall sweep over the n pivot rows (readlane), label = lowest bit, size = popcount, the winner a
+ *         wavefront maximum of (size, -label), new ids = popcount of the winner's mask below the lane, edges read off the rows.
+ *         No host read-back.
+ *   WIDE  every larger graph, all of them together in device-wide passes (a batch of thousands costs the launches of one; no node cap
+ *         below the totals): keys (global lo id, global hi id), global id = node_ptr[g] + local id, sorted by the shared radix passes
+ *         (16 or 32 bits per half, by total_nodes), repeats dropped against the predecessor; labels by hooking with a 32-bit atomicMin
+ *         onto the grandparents plus pointer jumping (FastSV: the rounds grow with log n, not with the diameter); sizes by atomicAdd per
+ *         label, the winner by a u64 atomicMax of (size << 32 | ~label); new ids and edge rows from two exclusive scans.
+ *         Host reads of this class: 8 bytes once (its graphs and keys) and one "changed" word per four rounds; surplus rounds of a
+ *         group return at once.
+ * max_nodes: an upper bound on the nodes of one graph where the caller has it (a graph above it is TLC_ST_BAD_INPUT), negative where
+ * not.  With max_nodes <= TLC_CC_WAVE_NMAX, or total_nodes <= TLC_CC_WAVE_NMAX, no graph can be WIDE and the call reads nothing back.
+ * d_work: tlc_graph_components_work_bytes() bytes (host arithmetic: 4 B per graph; with total_nodes > TLC_CC_WAVE_NMAX another 17 B per
+ * graph, 16 B per node, 24 B per edge and the sort's histograms), 16-byte aligned.  TLC_ERR_INVALID_ARG with nothing launched: a null
+ * pointer, a negative size, total_nodes or total_edges of 2^31 or more, a workspace below the reported size or not 16-byte aligned.
+ * n_graphs == 0: TLC_OK, nothing read.  Runs on the caller's current device, asynchronous on `stream` apart from the WIDE class's reads. */
+#define TLC_CC_WAVE_NMAX            64      /* most nodes of a graph that one wavefront computes (a u64 adjacency row per lane) */
+int tlc_graph_components_work_bytes(int64_t n_graphs, int64_t total_nodes, int64_t total_edges, int64_t* bytes);
+int tlc_graph_components(const int64_t* d_node_ptr, const int64_t* d_edge_ptr, const int32_t* d_edges, int64_t n_graphs,
+                         int64_t total_nodes, int64_t total_edges, int64_t max_nodes, int32_t* d_info, int32_t* d_new_id,
+                         int32_t* d_out_edges, uint8_t* d_status, void* d_work, int64_t work_bytes, void* stream);
 
 /* ---- M4-M6: PDGNN layer forward (Knowledge_Distillation/gat_conv.py:113-216) ----------------------
  * One GATConv(heads=1, new_node_feat, use_edge_attn) layer on a block-diagonal batch of graphs whose

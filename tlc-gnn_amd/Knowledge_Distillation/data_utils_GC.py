@@ -9,6 +9,9 @@ classification: whole graph = one diagram) and for the forward-only loop of trai
 The extended persistence of every graph runs in `tlc_pd_from_filtration` (Knowledge_Distillation fork: zero-persistence pairs
 kept), the three images (Ord0 ++ Ext1, Ord0, Ext1; :155-163) in `tlc_pi_raster`; `*_batch` processes a whole dataset in one
 launch of each instead of the reference's per-graph Python loop.
+
+The packed route at the end of the file -- `pack_dataset`, `ground_truth_packed`, `call_packed`, `evaluate_packed` -- is the same ground
+truth with nothing per graph on the host: components, relabelling and deduplication in `tlc_graph_components`, everything else tensor ops.
 """
 import numpy as np
 
@@ -247,4 +250,175 @@ def evaluate_batch(model, samples):
     with torch.no_grad():
         _, img, *_ = model(x, edge_index, None, compute_loss=False, grad_PI=False, graph_ptr=torch.tensor(gptr).cuda(),
                            edge_ptr=torch.tensor(eptr).cuda())
+    return img, kept
+
+
+# ---- the packed route: tensors in, tensors out, nothing per graph ---------------------------------------------------------------------
+COMPONENTS = ("largest", "whole")
+PACKED_FILTS = ("degree", "centrality", "clustering", "hks")
+
+
+def _item(data):
+    if hasattr(data, "edge_index"):
+        return int(data.num_nodes), np.asarray(data.edge_index.cpu()).T.reshape(-1, 2)
+    return _edges_nodes(data)
+
+
+def pack_dataset(dataset, gn=None):
+    """The first `gn` items of `dataset` (None: all) -- PyG-like items with num_nodes and edge_index [2, m], or (n, edges[m, 2]) tuples,
+    mixed as they come -- as one packed batch on the device: (node_ptr int64[B + 1], edge_ptr int64[B + 1], edges int32[sum m, 2]), the
+    edges RAW, exactly as the items hold them.  One concatenation on the host and three copies; no device op per graph."""
+    import torch
+    items = [_item(dataset[t]) for t in range(len(dataset) if gn is None else gn)]
+    node_ptr = np.zeros(len(items) + 1, dtype=np.int64)
+    edge_ptr = np.zeros(len(items) + 1, dtype=np.int64)
+    np.cumsum(np.asarray([n for n, _ in items], dtype=np.int64), out=node_ptr[1:])
+    np.cumsum(np.asarray([len(e) for _, e in items], dtype=np.int64), out=edge_ptr[1:])
+    edges = np.concatenate([e for _, e in items] + [np.zeros((0, 2), dtype=np.int64)]).astype(np.int32)
+    return torch.from_numpy(node_ptr).cuda(), torch.from_numpy(edge_ptr).cuda(), torch.from_numpy(edges).cuda()
+
+
+class PackedGroundTruth:
+    """What `ground_truth_packed` returns; every field a tensor on the device.  For a batch of B graphs of which S are ok:
+      ok [B] bool                                  the graphs that have a ground truth (the others are the reference's (None, None))
+      node_ptr, edge_ptr int64[S + 1]              the extracted batch of the ok graphs, in their order: the chosen component of each,
+      edges int32[sum m, 2], old_id int64[sum k]   renumbered, rows (lo, hi) ascending; old_id = the input's local id of every node
+      f float64[sum k]                             the filtration on the extracted batch
+      d0, d1 float64[., 2], o0, o1 int64[S + 1]    Ord0 and Ext1 of the ok graphs, packed: d0[o0[i] : o0[i + 1]] is graph i's
+      img, PI0, PI1 float64[B, 25]                 the images (Ord0 ++ Ext1, Ord0, Ext1), rows of zeros where not ok"""
+    FIELDS = ("ok", "node_ptr", "edge_ptr", "edges", "old_id", "f", "d0", "o0", "d1", "o1", "img", "PI0", "PI1")
+
+    def __init__(self, **fields):
+        assert set(fields) == set(self.FIELDS)
+        self.__dict__.update(fields)
+
+    def tuples(self):
+        """The reference's 9-tuple per ok graph (:166) and (None, None) per other one, on the host: the list
+        `compute_persistence_image_batch` returns.  The only place of the packed route that loops over graphs."""
+        import torch
+        h = {k: getattr(self, k).cpu().numpy() for k in self.FIELDS}
+        out = [(None, None)] * len(h["ok"])
+        for i, gi in enumerate(np.flatnonzero(h["ok"])):
+            n0, n1, e0, e1 = h["node_ptr"][i], h["node_ptr"][i + 1], h["edge_ptr"][i], h["edge_ptr"][i + 1]
+            edge_index = torch.from_numpy(h["edges"][e0:e1].T.astype(np.int64))
+            out[gi] = (h["d0"][h["o0"][i]:h["o0"][i + 1]], h["d1"][h["o1"][i]:h["o1"][i + 1]], h["img"][gi], h["f"][n0:n1].tolist(), edge_index,
+                       h["PI0"][gi], h["PI1"][gi], 0.0, 0.0)
+        return out
+
+
+def ground_truth_packed(node_ptr, edge_ptr, edges, filt='degree', hks_time=10, component='largest', filtrations=None, hks_large='host',
+                        pd_large='host'):
+    """The ground truth of a packed batch of RAW graphs (`pack_dataset`) without a loop over graphs -> `PackedGroundTruth`.
+    component='largest': `call`'s semantics -- the largest connected component of every graph, renumbered (`largest_component`, here
+    `engine.graph_components`), a ground truth where it has an edge.  component='whole': `compute_persistence_image_batch`'s semantics on
+    the deduplicated graph -- a ground truth where the graph is connected and has an edge (the component then IS the graph).
+    filt 'degree' / 'centrality' / 'clustering': `engine.struct_batch` on the extracted batch; 'hks': `data_utils_LP.hks_filtration_device`
+    at hks_time (hks_large as there); `filtrations`: a packed float64 tensor over the ORIGINAL nodes instead, gathered through old_id.
+    Diagrams from `engine.pd_from_filtration` (zero-persistence pairs kept; pd_large as there), the three images from `engine.pi_raster`
+    with the batch function's rule for an empty Ord0 or Ext1 (:128-137).  The values are those of `compute_persistence_image_batch` with
+    the device backends on the same graphs, bit for bit: the same kernels on the same packed input.
+    Host reads, per call and never per graph: the input's totals (one read), the status together with the extracted batch's totals (one
+    read), and what `hks_filtration_device`, `pd_from_filtration` and the two `autograd.pack_rows` read themselves.  A graph the kernel
+    refuses (offsets out of order, an id outside 0 .. n-1) raises RuntimeError naming the first one."""
+    import torch
+    from ..autograd import pack_rows
+    from .data_utils_LP import STRUCT_DEVICE_FILTS, check_hks_large, hks_filtration_device
+    if component not in COMPONENTS:
+        raise ValueError("component should be one of %s, not %r" % (COMPONENTS, component))
+    check_hks_large(hks_large)
+    engine.check_pd_large(pd_large)
+    if filtrations is None and filt not in PACKED_FILTS:
+        raise NotImplementedError("data_utils_GC (HIP): filt is one of %s here; pass `filtrations` for anything else" % (PACKED_FILTS,))
+    dev, B = node_ptr.device, node_ptr.numel() - 1
+    i64 = dict(dtype=torch.int64, device=dev)
+    zero, ar = torch.zeros(1, **i64), torch.arange(B, **i64)
+    n_g = node_ptr[1:] - node_ptr[:-1]
+    tot_n, max_n = torch.stack([node_ptr[-1], n_g.max()]).tolist() if B else (0, 0)
+    cc = engine.graph_components(node_ptr, edge_ptr, edges, total_nodes=tot_n, max_nodes=max_n)
+    k, m, c, s = cc["info"].to(torch.int64).unbind(1)
+    bad = cc["status"] != _lib.ST_OK
+    ok = ((m > 0) if component == 'largest' else ((c == 1) & (s > 0))) & ~bad
+    first_bad, S, K, M = torch.stack([torch.where(bad, ar, B).min() if B else zero[0], ok.sum(), (k * ok).sum(), (m * ok).sum()]).tolist()
+    if first_bad < B:
+        raise RuntimeError("ground_truth_packed: graph %d: TLC_ST_BAD_INPUT (offsets out of order or beyond the totals, or an edge id "
+                           "outside 0 .. n-1); no graph of the batch is returned" % first_bad)
+    # the ok graphs in ascending order, and the offsets of the batch their components form
+    sel = torch.argsort(~ok, stable=True)[:S]
+    ks, ms = k[sel], m[sel]
+    node_ptr2, edge_ptr2 = torch.cat([zero, ks.cumsum(0)]), torch.cat([zero, ms.cumsum(0)])
+    # every kept node of an ok graph writes its old local id to where its new id puts it (the others into a spare last entry)
+    owner = torch.repeat_interleave(ar, n_g, output_size=tot_n)
+    new_id = cc["new_id"].to(torch.int64)
+    slot = node_ptr2[(torch.cumsum(ok, 0) - 1).clamp(min=0)]
+    dest = torch.where(ok[owner] & (new_id >= 0), slot[owner] + new_id, K)
+    old_id = torch.empty(K + 1, **i64)
+    old_id[dest] = torch.arange(tot_n, **i64) - node_ptr[owner]
+    old_id = old_id[:K]
+    gn = torch.repeat_interleave(torch.arange(S, **i64), ks, output_size=K)
+    ge = torch.repeat_interleave(torch.arange(S, **i64), ms, output_size=M)
+    edges2 = cc["out_edges"][torch.arange(M, **i64) - edge_ptr2[ge] + edge_ptr[sel][ge]].reshape(-1, 2).contiguous()
+    img, PI0, PI1 = (torch.zeros((B, 25), dtype=torch.float64, device=dev) for _ in range(3))
+    if S == 0:
+        e2, e1 = torch.zeros((0, 2), dtype=torch.float64, device=dev), torch.zeros(0, dtype=torch.float64, device=dev)
+        return PackedGroundTruth(ok=ok, node_ptr=node_ptr2, edge_ptr=edge_ptr2, edges=edges2, old_id=old_id, f=e1, d0=e2, o0=zero, d1=e2, o1=zero,
+                                 img=img, PI0=PI0, PI1=PI1)
+    if filtrations is not None:
+        f = filtrations.to(torch.float64)[node_ptr[sel][gn] + old_id].contiguous()
+    elif filt == 'hks':
+        f = hks_filtration_device(node_ptr2, edge_ptr2, edges2, hks_time, K, hks_large=hks_large)
+    else:
+        # the extracted batch is simple and in range by construction: the status byte is not read back (a refused graph would be NaN)
+        f = engine.struct_batch(node_ptr2, edge_ptr2, edges2, filt, normalise=True, total_nodes=K)[0][0]
+    r = engine.pd_from_filtration(node_ptr2, edge_ptr2, edges2, f, _lib.KEEP_ZERO_PERS, want_rank=False, pd_large=pd_large)
+    c0, c1 = r["counts"][:, 0].to(torch.int64).clamp(min=0), r["counts"][:, 2].to(torch.int64).clamp(min=0)
+    d0, o0 = pack_rows(r["up"], node_ptr2[:-1], c0)
+    d1, o1 = pack_rows(r["one"], edge_ptr2[:-1], c1)
+    # Ord0 ++ Ext1 per graph (:163): row j of graph i comes from d0 while j < c0[i], from d1 behind it
+    T = d0.shape[0] + d1.shape[0]
+    ob = o0 + o1
+    own = torch.repeat_interleave(torch.arange(S, **i64), c0 + c1, output_size=T)
+    pos = torch.arange(T, **i64) - ob[own]
+    both = torch.cat((d0, d1))[torch.where(pos < c0[own], o0[own] + pos, d0.shape[0] + o1[own] + pos - c0[own])]
+    has0, has1 = (c0 > 0)[:, None], (c1 > 0)[:, None]
+    pi0 = torch.where(has0, engine.pi_raster(o0, d0, 5), 0.0)
+    pi1 = torch.where(has1, engine.pi_raster(o1, d1, 5), 0.0)
+    img[sel] = torch.where(has0, torch.where(has1, engine.pi_raster(ob, both, 5), pi0), pi1)
+    PI0[sel], PI1[sel] = pi0, pi1
+    return PackedGroundTruth(ok=ok, node_ptr=node_ptr2, edge_ptr=edge_ptr2, edges=edges2, old_id=old_id, f=f, d0=d0, o0=o0, d1=d1, o1=o1,
+                             img=img, PI0=PI0, PI1=PI1)
+
+
+def call_packed(dataset, name, filt='degree', hks_time=10, gn=0, save_dir=None, store=None, hks_large='host', pd_large='host'):
+    """`call` through the packed route: the first `gn` graphs of `dataset` in one `pack_dataset` and one `ground_truth_packed`
+    (component='largest').  Leaves in `store`, and in <save_dir>/<name>_<filt>_total_test.pkl, what `call` leaves with the device
+    backends; returns (0, 0) like it, and prints nothing per graph."""
+    import os
+    import pickle
+    from .data_utils_LP import check_hks_large
+    check_hks_large(hks_large)
+    engine.check_pd_large(pd_large)
+    gt = ground_truth_packed(*pack_dataset(dataset, gn), filt=filt, hks_time=hks_time, component='largest', hks_large=hks_large, pd_large=pd_large)
+    dict_store = {} if store is None else store
+    dict_store.update(enumerate(gt.tuples()))
+    if save_dir is not None:
+        with open(os.path.join(save_dir, name + '_' + filt + '_total_test.pkl'), 'wb') as f:
+            pickle.dump(dict_store, f, pickle.HIGHEST_PROTOCOL)
+    return 0, 0
+
+
+def evaluate_packed(model, gt):
+    """`evaluate_batch` on a `PackedGroundTruth` without the per-sample loop: the block-diagonal edge_index (the real edges, then one self
+    loop per node), x = f.float(), graph_ptr and edge_ptr straight from gt's tensors.  Returns float32 CUDA [n_kept, 25] images + kept
+    indices (one read: the ok flags)."""
+    import torch
+    kept = torch.nonzero(gt.ok).flatten().tolist()
+    if not kept:
+        return torch.zeros(0, 25, device="cuda"), kept
+    K = gt.f.numel()
+    base = torch.repeat_interleave(gt.node_ptr[:-1], gt.edge_ptr[1:] - gt.edge_ptr[:-1], output_size=gt.edges.shape[0])
+    loops = torch.arange(K, dtype=torch.int64, device=gt.f.device)
+    edge_index = torch.cat([(gt.edges.to(torch.int64) + base[:, None]).t(), torch.stack([loops, loops])], dim=1)
+    with torch.no_grad():
+        _, img, *_ = model(gt.f.float().view(-1, 1), edge_index, None, compute_loss=False, grad_PI=False, graph_ptr=gt.node_ptr,
+                           edge_ptr=gt.edge_ptr)
     return img, kept

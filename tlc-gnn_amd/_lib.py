@@ -24,6 +24,7 @@ HKS_LARGE_TILE, HKS_LARGE_KSTEP = 64, 16                            # HKSL_T, HK
 STRUCT_DEGREE, STRUCT_CENTRALITY, STRUCT_CLUSTERING, STRUCT_NORMALISE = 0x1, 0x2, 0x4, 0x100      # TLC_STRUCT_* of include/tlcgnn.h
 STRUCT_WAVE_NMAX, STRUCT_LDS_SMALL_NMAX, STRUCT_LDS_NMAX, STRUCT_BITMAP_BITS = 64, 256, 1024, 65536
 STRUCT_KINDS = {"degree": STRUCT_DEGREE, "centrality": STRUCT_CENTRALITY, "clustering": STRUCT_CLUSTERING}   # in output-row order
+CC_WAVE_NMAX = 64                                                   # TLC_CC_WAVE_NMAX: tlc_graph_components, a wavefront per graph up to here
 OTD_WAVE_PRODUCT, OTD_WAVE_SUPPORT, OTD_WAVE_DENOM, OTD_MAX_SUPPORT, OTD_LDS_BYTES = 8192, 256, 65535, 12794, 153600   # TLC_OTD_* of include/tlcgnn.h
 KEEP_ZERO_PERS, INCLUDE_ROOTS, NORM_EPS, PI_ORD0_EXT1, NO_EXT1, UNREACHABLE_100 = 0x1, 0x2, 0x4, 0x8, 0x10, 0x20
 DESC_MIN, DESC_MAX, DESC_ROOT1, NO_NORM = 0x40, 0x80, 0xC0, 0x100
@@ -54,6 +55,7 @@ SYMBOLS = [
     "tlc_pd_grad_work_bytes", "tlc_pd_point_vertices", "tlc_pd_filtration_grad",
     "tlc_sliced_w_work_bytes", "tlc_sliced_wasserstein",
     "tlc_pi_image_work_bytes", "tlc_pi_image", "tlc_pi_image_vjp",
+    "tlc_graph_components_work_bytes", "tlc_graph_components",
     "tlc_gcn2_encode_work_floats", "tlc_gemm_tn_work_floats", "tlc_lp_decode_bwd_work_floats", "tlc_nc_linear_bwd_work_floats",
     "tlc_gat_layer_fwd_work_floats", "tlc_gat_layer_tiled_fwd_work_floats", "tlc_gat_tile_cut_work_ints", "tlc_gat_tile_cut_max_tiles",
     "tlc_csr_by_target_work_ints", "tlc_gat_layer_bwd_work_floats", "tlc_edge_head_fwd_work_floats", "tlc_edge_head_bwd_work_floats",
@@ -212,6 +214,8 @@ def lib():
                                    C.c_void_p, C.c_int64, C.c_void_p])
         L.tlc_pi_image_vjp.argtypes = ([C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 4
                                        + [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p])
+        L.tlc_graph_components_work_bytes.argtypes = [C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_int64)]
+        L.tlc_graph_components.argtypes = [C.c_void_p] * 3 + [C.c_int64] * 4 + [C.c_void_p] * 5 + [C.c_int64, C.c_void_p]
         # the scratch sizes of the entries that take a bare d_work (csrc/scratch_layouts.h)
         for name, args in (("tlc_gcn2_encode_work_floats", [C.c_int32] * 3), ("tlc_gemm_tn_work_floats", [C.c_int32] * 2),
                            ("tlc_lp_decode_bwd_work_floats", [C.c_int64]), ("tlc_nc_linear_bwd_work_floats", [C.c_int32] * 2),

@@ -97,6 +97,30 @@ struct TlcEdgeHeadBwdScratch {
         : hbuf(n_edges * 2 * c), gpre(hbuf + n_edges * hidden), total(gpre + n_edges * hidden) {}
 };
 
+// tlc_graph_components (gc_prep.hip).  In BYTES, every array on a multiple of 256: the control words [HEAD bytes] | the WAVE class's
+// graph list int[B] | and, only when the batch can hold a WIDE graph (total_nodes > wave_nmax): per graph the class byte u8[B], the
+// winner u64[B], the component count int[B], the first sorted key int[B]; per node the label u32[N], the component size int[N], the
+// keep-flag scan u64[N + 1]; per raw edge the keys' two halves, each twice for the radix sort's ping-pong, u32[M] x 4, and the
+// "distinct | kept" scan u64[M + 1]; the scans' chunk sums u64[chunks + 1]; the radix sort's hist and tot (ints: the caller passes
+// rk_hist_ints(M) and RK_TOT_INTS of radix_passes.h, which is device code and stays out of this header).
+struct TlcGraphComponentsScratch {
+    static constexpr int64_t HEAD = 256, SCAN_CHUNK = 2048;
+    static int64_t up256(int64_t v) { return (v + 255) & ~(int64_t)255; }
+    bool wide;
+    int64_t head = 0, list, cls, best, comps, first, parent, size, nscan, klo_a, klo_b, khi_a, khi_b, escan, sums, hist, tot, total;
+    TlcGraphComponentsScratch(int64_t B, int64_t N, int64_t M, int64_t wave_nmax, int64_t hist_ints, int64_t tot_ints) : wide(N > wave_nmax) {
+        int64_t o = HEAD;
+        auto take = [&](int64_t count, int64_t size_of) { const int64_t at = o; o += up256((wide ? count : 0) * size_of); return at; };
+        list = o; o += up256(B * 4);
+        cls = take(B, 1); best = take(B, 8); comps = take(B, 4); first = take(B, 4);
+        parent = take(N, 4); size = take(N, 4); nscan = take(N + 1, 8);
+        klo_a = take(M, 4); klo_b = take(M, 4); khi_a = take(M, 4); khi_b = take(M, 4); escan = take(M + 1, 8);
+        sums = take(std::max(N, M) / SCAN_CHUNK + 2, 8);
+        hist = take(hist_ints, 4); tot = take(tot_ints, 4);
+        total = o;
+    }
+};
+
 // tlc_pi_image: the partial images [slices][res_b * res_p] of the diagrams above SLICE points, one per slice of SLICE points (the second
 // pass adds a pixel's slices ascending).  In float64 elements.  `least` holds the slices of the largest diagram, `total` those of
 // MAX_GROUP such diagrams (the most one launch takes); diagrams of up to SLICE points need none.

@@ -407,6 +407,47 @@ def struct_batch(node_ptr, edge_ptr, edges, kinds, normalise=True, total_nodes=N
     return out, status[:B]
 
 
+def graph_components_work_bytes(n_graphs, total_nodes, total_edges):
+    """Bytes of workspace tlc_graph_components needs for a batch of these totals: host arithmetic, no device."""
+    need = C.c_int64(0)
+    _lib.check(_lib.lib().tlc_graph_components_work_bytes(C.c_int64(int(n_graphs)), C.c_int64(int(total_nodes)), C.c_int64(int(total_edges)),
+                                                          C.byref(need)), "tlc_graph_components_work_bytes")
+    return need.value
+
+
+@_lib.on_device_of
+def graph_components(node_ptr, edge_ptr, edges, work=None, total_nodes=None, max_nodes=None):
+    """Connected components of a packed batch of RAW edge lists on the device, the largest component of every graph extracted,
+    renumbered and deduplicated (tlc_graph_components; `data_utils_GC.largest_component`, integer for integer).
+
+    node_ptr / edge_ptr int64[B+1], edges int32[sum m, 2] local ids: CUDA tensors; both orientations, repeated pairs and self loops are
+    allowed and dropped.  Returns dict(info int32[B, 4] = (k, m, c, s) per graph -- nodes and distinct edges of the chosen component,
+    components and distinct pairs of the whole graph --, new_id int32[sum n] (-1: dropped), out_edges int32[sum m, 2] (slot layout: the
+    first m rows of graph g's input slot, (lo, hi) ascending), status uint8[B] (ST_OK / ST_BAD_INPUT; a refused graph's slots and info row
+    keep what they held: -1 where the tensors are allocated here)).
+    work: a 16-byte aligned uint8 CUDA tensor of at least `graph_components_work_bytes` (None: allocated).  total_nodes: sum n if the
+    caller has it; else node_ptr[-1] is read.  max_nodes: an upper bound on one graph's nodes if the caller has it (a graph above it is
+    refused): up to _lib.CC_WAVE_NMAX, or with total_nodes up to there, the call reads nothing back."""
+    torch = _lib.require_gpu()
+    dev = node_ptr.device
+    B = node_ptr.numel() - 1
+    tot_m = int(edges.shape[0])
+    tot_n = int(total_nodes) if total_nodes is not None else (int(node_ptr[-1]) if B > 0 else 0)
+    out = dict(info=torch.full((max(B, 1), 4), -1, dtype=torch.int32, device=dev),
+               new_id=torch.full((max(tot_n, 1),), -1, dtype=torch.int32, device=dev),
+               out_edges=torch.full((max(tot_m, 1), 2), -1, dtype=torch.int32, device=dev),
+               status=torch.zeros(max(B, 1), dtype=torch.uint8, device=dev))
+    if B > 0:
+        if work is None:
+            work = torch.empty(max(graph_components_work_bytes(B, tot_n, tot_m), 16), dtype=torch.uint8, device=dev)
+        rc = _lib.lib().tlc_graph_components(_lib.ptr(node_ptr.contiguous()), _lib.ptr(edge_ptr.contiguous()), _lib.ptr(edges.contiguous()),
+                                             C.c_int64(B), C.c_int64(tot_n), C.c_int64(tot_m), C.c_int64(-1 if max_nodes is None else int(max_nodes)),
+                                             _lib.ptr(out["info"]), _lib.ptr(out["new_id"]), _lib.ptr(out["out_edges"]), _lib.ptr(out["status"]),
+                                             _lib.ptr(work), C.c_int64(work.numel()), _lib.stream_ptr())
+        _lib.check(rc, "tlc_graph_components")
+    return dict(info=out["info"][:B], new_id=out["new_id"][:tot_n], out_edges=out["out_edges"][:tot_m], status=out["status"][:B])
+
+
 def check_pd_large(pd_large):
     """'host' (tlc_pd_from_filtration alone: the one-workgroup HUGE tier, and no answer above its cap) or 'device' (the HUGE class and
     everything above it through tlc_pd_wide)."""
