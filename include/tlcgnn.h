@@ -520,6 +520,17 @@ int tlc_hks_batch_work_bytes(int64_t n_graphs, int64_t total_nodes, int64_t tota
 int tlc_hks_batch(const int64_t* d_node_ptr, const int64_t* d_edge_ptr, const int32_t* d_edges, int64_t n_graphs, int64_t total_nodes,
                   int64_t total_edges, const double* h_times, int32_t n_times, uint32_t flags, double* d_out, uint8_t* d_status,
                   void* d_work, int64_t work_bytes, void* stream);
+/* tlc_hks_batch with the derivative in the diffusion time.  d_dout f64[n_times, total_nodes] is d/dt of exactly what d_out holds:
+ *   d/dt hks_t(x) = - sum_k lambda_k exp(-t lambda_k) phi_k(x)^2   (k ascending, from the eigenpairs of the value),
+ * and under TLC_HKS_NORMALISE, with f = hks / (mx + 1e-10) and mx = hks(a) taken at the LOWEST index a that attains the maximum,
+ *   d/dt f(x) = (hks'(x) - f(x) hks'(a)) / (mx + 1e-10).
+ * A node of degree 0 has derivative 0; at t = 0 every node of degree > 0 has -1 (raw).  d_out and d_status are bit for bit what
+ * tlc_hks_batch writes for the same arguments; row k of d_dout is bit-equal to a call with h_times[k] alone; a graph whose status is
+ * not TLC_ST_OK keeps both slices untouched.  Same workspace (tlc_hks_batch_work_bytes) and refusals, plus a null d_dout, all decided
+ * before anything is launched. */
+int tlc_hks_batch_dt(const int64_t* d_node_ptr, const int64_t* d_edge_ptr, const int32_t* d_edges, int64_t n_graphs, int64_t total_nodes,
+                     int64_t total_edges, const double* h_times, int32_t n_times, uint32_t flags, double* d_out, double* d_dout,
+                     uint8_t* d_status, void* d_work, int64_t work_bytes, void* stream);
 
 /* ---- Heat-kernel signatures of graphs above TLC_HKS_NMAX nodes ---------------------------------------------------------------------------
  * The same values for SELECTED graphs of the packed batch of tlc_hks_batch, without eigenpairs: hks_t(v) = [exp(-t L)]_vv, and with
@@ -550,6 +561,16 @@ int tlc_hks_large_batch(const int64_t* d_node_ptr, const int64_t* d_edge_ptr, co
                         int64_t total_nodes, int64_t total_edges, const int64_t* h_sel, const int64_t* h_sel_nodes, int64_t n_sel,
                         const double* h_times, int32_t n_times, uint32_t flags, double* d_out, uint8_t* d_status,
                         void* d_work, int64_t work_bytes, void* stream);
+/* tlc_hks_large_batch with the derivative in the diffusion time, d_dout f64[n_times, total_nodes] as in tlc_hks_batch_dt, from
+ *   d/dt hks_t(v) = -[L K_t]_vv = -[K_t]_vv + sum over the neighbours u of v of [K_t]_uv / sqrt(d_u d_v),   K_t = exp(-t L):
+ * no product beyond those of the value.  The last matrix P is K_t (s = 0: [K_t]_uv = P_uv) or K_t/2 ([K_t]_uv = sum_j P_uj P_vj, a row
+ * dot per edge end); the neighbours are walked u ascending in partial sums of 64 columns; t = 0 is answered directly (-1 for degree
+ * > 0).  No floating-point atomics: the bits depend on the graph and the time alone, with any workspace.  d_out and d_status are bit
+ * for bit tlc_hks_large_batch's; same workspace (tlc_hks_large_work_bytes) and refusals, plus a null d_dout. */
+int tlc_hks_large_batch_dt(const int64_t* d_node_ptr, const int64_t* d_edge_ptr, const int32_t* d_edges, int64_t n_graphs,
+                           int64_t total_nodes, int64_t total_edges, const int64_t* h_sel, const int64_t* h_sel_nodes, int64_t n_sel,
+                           const double* h_times, int32_t n_times, uint32_t flags, double* d_out, double* d_dout, uint8_t* d_status,
+                           void* d_work, int64_t work_bytes, void* stream);
 
 /* ---- Degree / centrality / clustering filtrations (Knowledge_Distillation/data_utils_LP.py:131-133; data_utils_NC.py:124-135: networkx's
  * degree(), degree_centrality and clustering of the vicinity, then / (max + 1e-10)) ------------------------------------------------------

@@ -50,7 +50,7 @@ SYMBOLS = [
     "tlc_lp_decode_fused", "tlc_lp_decode_fused_f32", "tlc_gat_layer_fwd", "tlc_gat_layer_tiled_fwd", "tlc_gat_tile_cut", "tlc_csr_by_target", "tlc_pdgnn_forward", "tlc_pdgnn_forward_work_bytes", "tlc_scatter_f32", "tlc_edge_head_fwd",
     "tlc_complement_rows", "tlc_complement_pairs", "tlc_select_rows", "tlc_pack_vicinities", "tlc_stack_batch", "tlc_ollivier_ricci_sinkhorn",
     "tlc_near_pairs", "tlc_w2_partial_matching", "tlc_w2_inference_matching", "tlc_gat_layer_bwd", "tlc_edge_head_bwd", "tlc_pack_offsets", "tlc_vicinity_sizes", "tlc_debug_dc_stats", "tlc_debug_tier_counts", "tlc_debug_chunk_counters", "tlc_debug_phase_profile", "tlc_debug_set_option", "tlc_debug_pair_times",
-    "tlc_hks_batch", "tlc_hks_batch_work_bytes", "tlc_hks_large_batch", "tlc_hks_large_work_bytes", "tlc_struct_batch", "tlc_struct_batch_work_bytes",
+    "tlc_hks_batch", "tlc_hks_batch_work_bytes", "tlc_hks_large_batch", "tlc_hks_large_work_bytes", "tlc_hks_batch_dt", "tlc_hks_large_batch_dt", "tlc_struct_batch", "tlc_struct_batch_work_bytes",
     "tlc_ollivier_ricci_otd", "tlc_ollivier_ricci_otd_work_bytes", "tlc_pd_wide", "tlc_pd_wide_work_bytes",
     "tlc_pd_grad_work_bytes", "tlc_pd_point_vertices", "tlc_pd_filtration_grad",
     "tlc_sliced_w_work_bytes", "tlc_sliced_wasserstein",
@@ -193,6 +193,11 @@ def lib():
         L.tlc_hks_large_work_bytes.argtypes = [C.POINTER(C.c_int64), C.c_int64, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
         L.tlc_hks_large_batch.argtypes = ([C.c_void_p] * 3 + [C.c_int64] * 3 + [C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int64,
                                           C.POINTER(C.c_double), C.c_int32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p])
+        L.tlc_hks_batch_dt.argtypes = ([C.c_void_p] * 3 + [C.c_int64] * 3 + [C.POINTER(C.c_double), C.c_int32, C.c_uint32, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p])
+        L.tlc_hks_large_batch_dt.argtypes = ([C.c_void_p] * 3 + [C.c_int64] * 3 + [C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int64,
+                                             C.POINTER(C.c_double), C.c_int32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                             C.c_int64, C.c_void_p])
         L.tlc_struct_batch_work_bytes.argtypes = [C.c_int64, C.c_int64, C.c_int64, C.c_uint32, C.POINTER(C.c_int64)]
         L.tlc_struct_batch.argtypes = [C.c_void_p] * 3 + [C.c_int64] * 3 + [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
         L.tlc_ollivier_ricci_otd_work_bytes.argtypes = [C.c_int64, C.c_int32, C.c_int64, C.POINTER(C.c_int64)]

@@ -4,7 +4,7 @@
 classifier of Knowledge_Distillation/ConvCurv_GIN.py: CurvConv and NcLinear (nc_curv.hip).
 
 torch.autograd only carries the graph: every forward and every backward below is one C-ABI call (`tlc_gat_layer_fwd/_bwd`,
-`tlc_edge_head_fwd/_bwd`, `tlc_w2_partial_matching`, `tlc_sliced_wasserstein`, `tlc_pi_raster` / `tlc_pi_raster_wgrad`, `tlc_pi_image` / `tlc_pi_image_vjp`) or a few (`tlc_gemm_f32` /
+`tlc_edge_head_fwd/_bwd`, `tlc_w2_partial_matching`, `tlc_sliced_wasserstein`, `tlc_pi_raster` / `tlc_pi_raster_wgrad`, `tlc_pi_image` / `tlc_pi_image_vjp`, `tlc_hks_batch_dt` + `tlc_hks_large_batch_dt`) or a few (`tlc_gemm_f32` /
 `tlc_spmm_csr_f32` / `tlc_gemm_tn_f32`, `tlc_lp_decode_fused_f32` / `tlc_lp_decode_bwd_f32`); nothing is recomputed with torch ops
 and there is no CPU path.
 """
@@ -186,6 +186,62 @@ def extended_persistence(f, node_offs, edge_offs, edges, flags=_lib.KEEP_ZERO_PE
     not).  A graph that is not computed raises RuntimeError naming it."""
     engine.check_pd_large(pd_large)
     return ExtendedPersistence.apply(f, node_offs, edge_offs, edges, int(flags), pd_large)
+
+
+class HksSignature(torch.autograd.Function):
+    """Heat-kernel signatures of a packed batch as a differentiable function of the diffusion times: float64[T, sum n], the values of
+    `engine.hks_batch` / `engine.hks_large_batch` bit for bit, with d / d t from the same kernels (tlc_hks_batch_dt, then
+    tlc_hks_large_batch_dt for the graphs above HKS_NMAX nodes).  The gradient is in `times` only:
+    grad_times[k] = sum(grad[k] * d out[k] / d t)."""
+
+    @staticmethod
+    def forward(ctx, times, node_ptr, edge_ptr, edges, normalise):
+        host = [float(t) for t in times.detach().to(torch.float64).cpu().tolist()]    # the one read of the times
+        B = node_ptr.numel() - 1
+        tot_n = int(node_ptr[-1]) if B > 0 else 0
+        out, dout, st = engine.hks_batch(node_ptr, edge_ptr, edges, host, normalise=normalise, total_nodes=tot_n, dt=True)
+        st_h = st.cpu()
+        rest = torch.nonzero(st_h != _lib.ST_OK).flatten()
+        if rest.numel():
+            sizes = (node_ptr[1:] - node_ptr[:-1]).cpu()[rest]
+            take = (st_h[rest] == _lib.ST_TOO_LARGE) & (sizes <= _lib.HKS_LARGE_NMAX)
+            if bool(take.any()):
+                bad_t = [t for t in host if not 0.0 <= t <= _lib.HKS_LARGE_TIME_MAX]     # (a NaN fails both comparisons)
+                if bad_t:
+                    raise RuntimeError("hks_signature: graph(s) %s have more than %d nodes (status %d = ST_TOO_LARGE) and their tier takes "
+                                       "times inside [0, %g], not %s" % (rest[take].tolist(), _lib.HKS_NMAX, _lib.ST_TOO_LARGE,
+                                                                         _lib.HKS_LARGE_TIME_MAX, bad_t))
+                engine.hks_large_batch(node_ptr, edge_ptr, edges, rest[take].tolist(), sizes[take].tolist(), host, normalise=normalise,
+                                       total_nodes=tot_n, out=out, status=st, dout=dout)
+                st_h = st.cpu()
+            bad = torch.nonzero(st_h != _lib.ST_OK).flatten().tolist()
+            if bad:
+                raise RuntimeError("hks_signature: graph(s) %s are not computed: status %s (%d = ST_TOO_LARGE: more than %d nodes; %d = "
+                                   "ST_NOT_CONVERGED; %d = ST_BAD_INPUT: offsets out of order, an edge id out of range, a self loop or a "
+                                   "repeated edge); there is no host route with a derivative"
+                                   % (bad, st_h[bad].tolist(), _lib.ST_TOO_LARGE, _lib.HKS_LARGE_NMAX, _lib.ST_NOT_CONVERGED, _lib.ST_BAD_INPUT))
+        ctx.save_for_backward(dout)
+        ctx.dtype, ctx.device = times.dtype, times.device
+        return out
+
+    @staticmethod
+    def backward(ctx, grad):
+        dout, = ctx.saved_tensors
+        g = (grad.to(torch.float64) * dout).sum(dim=1)
+        return g.to(device=ctx.device, dtype=ctx.dtype), None, None, None, None
+
+
+def hks_signature(times, node_ptr, edge_ptr, edges, normalise=True):
+    """-> float64[T, sum n]: row k is the heat-kernel signature at times[k] of every graph of the packed batch (node_ptr / edge_ptr
+    int64[B + 1], edges int32[sum m, 2] local ids, CUDA tensors; simple graphs, each undirected edge once), normalised per graph by
+    (max + 1e-10) unless normalise=False; differentiable in `times`, a 1-D tensor of 1 .. HKS_TMAX entries of any float dtype, on any
+    device.  The forward READS THE TIMES TO THE HOST once: both kernels take them as launch arguments, and the number of squarings of
+    the large tier depends on them.  Graphs up to HKS_NMAX nodes take the Jacobi tiers, larger ones up to HKS_LARGE_NMAX the large
+    tier (times inside [0, HKS_LARGE_TIME_MAX] then); anything else raises RuntimeError naming graph and status -- there is no host
+    fallback, because the host route has no derivative."""
+    if not torch.is_tensor(times) or times.dim() != 1 or not times.is_floating_point() or not 1 <= times.numel() <= _lib.HKS_TMAX:
+        raise ValueError("hks_signature: times should be a 1-D float tensor of 1 .. %d entries" % _lib.HKS_TMAX)
+    return HksSignature.apply(times, node_ptr, edge_ptr, edges, bool(normalise))
 
 
 def packed_points(points, slot_offs, n_points):

@@ -26,6 +26,10 @@
 //   GLOBAL n <= TLC_HKS_NMAX = 256   one 1 024-thread workgroup per graph (its rounds wait on L2: more loads in flight), A and V^T in the
 //                                     workgroup's slot of the caller's workspace (1.0 MiB), rotations and the pair table in LDS
 // Leading dimension NMAX + 1 (odd): a column walk of the fp64 array touches every bank pair once.
+//
+// tlc_hks_batch_dt: the same tiers instantiated with DT, which add per time one more pass of the signature's loop with the weights
+// -lambda_k exp(-t lambda_k) -- d/dt of the row just stored, into a second output; cs and vals are reused, no further LDS.  The kernels of
+// tlc_hks_batch are the instantiations without DT and hold none of it.
 #include "tlc_common.h"
 
 #include <algorithm>
@@ -70,10 +74,11 @@ constexpr size_t hks_lds_bytes(int nmax, bool global) {
 }
 
 // One graph on NT threads (tid = 0 .. NT-1).  A, Vt: (NMAX) x (NMAX + 1) fp64 each, LDS or global.  Returns the status byte (uniform).
-template <int NMAX, int NT, bool WAVE>
+// DT: row ti of `dout` is d/dt of what row ti of `out` holds (tlc_hks_batch_dt); without it `dout` is unused and nothing below changes.
+template <int NMAX, int NT, bool WAVE, bool DT>
 __device__ __forceinline__ int hks_graph(double* A, double* Vt, double* cs, double* vals, int* deg, int* flag, unsigned short* tab, int tid,
                                          int n, int m, const int* __restrict__ edges, const HksTimes& times, int T, unsigned flags,
-                                         double* __restrict__ out, long long out_stride) {
+                                         double* __restrict__ out, double* __restrict__ dout, long long out_stride) {
     constexpr int ld = NMAX + 1;
     const int ne = (n + 1) & ~1, h = ne >> 1, M = ne - 1;
     for (int i = tid; i < ne * ld; i += NT) { A[i] = 0.0; Vt[i] = 0.0; }
@@ -199,6 +204,37 @@ __device__ __forceinline__ int hks_graph(double* A, double* Vt, double* cs, doub
         for (int x = tid; x < n; x += NT)
             out[(long long)ti * out_stride + x] = (flags & TLC_HKS_NORMALISE) ? vals[x] / (mx + 1e-10) : vals[x];
         hks_sync<WAVE>();
+        if constexpr (DT) {
+            // d/dt hks(x) = - sum_k lambda_k exp(-t lambda_k) phi_k(x)^2: the same loop, k ascending, over cs and vals again.  Normalised,
+            // f = hks / (mx + 1e-10) with mx = hks(a), a the LOWEST index of the maximum:  f'(x) = (hks'(x) - f(x) hks'(a)) / (mx + 1e-10)
+            int a = 0;
+            if (flags & TLC_HKS_NORMALISE) {
+                double top = vals[0];
+                for (int x = 1; x < n; ++x)
+                    if (vals[x] > top) { top = vals[x]; a = x; }
+            }
+            hks_sync<WAVE>();                                  // every thread has read vals
+            for (int k = tid; k < ne; k += NT) {
+                const double lam = A[k * ld + k];
+                cs[k] = -lam * exp(-time * lam);
+            }
+            hks_sync<WAVE>();
+            for (int x = tid; x < n; x += NT) {
+                double acc = 0.0;
+                for (int k = 0; k < ne; ++k) {
+                    const double v = Vt[k * ld + x];
+                    acc += (v * v) * cs[k];
+                }
+                vals[x] = acc;
+            }
+            hks_sync<WAVE>();
+            const double da = vals[a];
+            for (int x = tid; x < n; x += NT) {
+                const long long o = (long long)ti * out_stride + x;
+                dout[o] = (flags & TLC_HKS_NORMALISE) ? (vals[x] - out[o] * da) / (mx + 1e-10) : vals[x];   // out[o]: this thread's store
+            }
+            hks_sync<WAVE>();
+        }
     }
     return TLC_ST_OK;
 }
@@ -234,11 +270,11 @@ __global__ __launch_bounds__(256) void hks_bin_kernel(long long B, long long tot
 constexpr int hks_threads(bool wave, bool global) { return wave ? 64 : global ? 1024 : 256; }
 constexpr int hks_block(bool global) { return global ? 1024 : 256; }
 
-template <int NMAX, bool WAVE, bool GLOBAL>
-__global__ __launch_bounds__(hks_block(GLOBAL)) void hks_tier_kernel(int tier, long long B, const long long* __restrict__ node_ptr, const long long* __restrict__ edge_ptr,
-                                                       const int* __restrict__ edges, HksTimes times, int T, unsigned flags, double* __restrict__ out,
-                                                       long long out_stride, unsigned char* __restrict__ status, int* __restrict__ head,
-                                                       const int* __restrict__ lists, double* __restrict__ slots) {
+template <int NMAX, bool WAVE, bool GLOBAL, bool DT>
+__device__ __forceinline__ void hks_tier_body(int tier, long long B, const long long* __restrict__ node_ptr, const long long* __restrict__ edge_ptr,
+                                              const int* __restrict__ edges, const HksTimes& times, int T, unsigned flags, double* __restrict__ out,
+                                              double* __restrict__ dout, long long out_stride, unsigned char* __restrict__ status,
+                                              int* __restrict__ head, const int* __restrict__ lists, double* __restrict__ slots) {
     extern __shared__ __attribute__((aligned(16))) unsigned char hks_smem[];
     constexpr int NT = hks_threads(WAVE, GLOBAL);
     constexpr size_t UNIT = hks_lds_bytes(NMAX, GLOBAL);
@@ -269,10 +305,28 @@ __global__ __launch_bounds__(hks_block(GLOBAL)) void hks_tier_kernel(int tier, l
         const int g = list[i];
         const long long n0 = node_ptr[g], e0 = edge_ptr[g];
         const int n = (int)(node_ptr[g + 1] - n0), m = (int)(edge_ptr[g + 1] - e0);
-        const int st = hks_graph<NMAX, NT, WAVE>(A, Vt, cs, vals, deg, flag, tab, tid, n, m, edges + 2 * e0, times, T, flags, out + n0, out_stride);
+        const int st = hks_graph<NMAX, NT, WAVE, DT>(A, Vt, cs, vals, deg, flag, tab, tid, n, m, edges + 2 * e0, times, T, flags, out + n0,
+                                                     DT ? dout + n0 : nullptr, out_stride);
         if (tid == 0 && st != TLC_ST_OK) status[g] = (unsigned char)st;
         hks_sync<WAVE>();
     }
+}
+
+template <int NMAX, bool WAVE, bool GLOBAL>
+__global__ __launch_bounds__(hks_block(GLOBAL)) void hks_tier_kernel(int tier, long long B, const long long* __restrict__ node_ptr, const long long* __restrict__ edge_ptr,
+                                                       const int* __restrict__ edges, HksTimes times, int T, unsigned flags, double* __restrict__ out,
+                                                       long long out_stride, unsigned char* __restrict__ status, int* __restrict__ head,
+                                                       const int* __restrict__ lists, double* __restrict__ slots) {
+    hks_tier_body<NMAX, WAVE, GLOBAL, false>(tier, B, node_ptr, edge_ptr, edges, times, T, flags, out, nullptr, out_stride, status, head, lists, slots);
+}
+
+// the same tiers with the derivative in t (tlc_hks_batch_dt): one more row per time, written to dout
+template <int NMAX, bool WAVE, bool GLOBAL>
+__global__ __launch_bounds__(hks_block(GLOBAL)) void hks_tier_dt_kernel(int tier, long long B, const long long* __restrict__ node_ptr, const long long* __restrict__ edge_ptr,
+                                                       const int* __restrict__ edges, HksTimes times, int T, unsigned flags, double* __restrict__ out,
+                                                       double* __restrict__ dout, long long out_stride, unsigned char* __restrict__ status,
+                                                       int* __restrict__ head, const int* __restrict__ lists, double* __restrict__ slots) {
+    hks_tier_body<NMAX, WAVE, GLOBAL, true>(tier, B, node_ptr, edge_ptr, edges, times, T, flags, out, dout, out_stride, status, head, lists, slots);
 }
 
 struct HksLayout {
@@ -308,19 +362,29 @@ extern "C" int tlc_hks_batch_work_bytes(int64_t n_graphs, int64_t total_nodes, i
     return TLC_OK;
 }
 
-extern "C" int tlc_hks_batch(const int64_t* d_node_ptr, const int64_t* d_edge_ptr, const int32_t* d_edges, int64_t n_graphs, int64_t total_nodes,
-                             int64_t total_edges, const double* h_times, int32_t n_times, uint32_t flags, double* d_out, uint8_t* d_status,
-                             void* d_work, int64_t work_bytes, void* stream) {
-    TLC_REQUIRE(n_graphs >= 0 && n_graphs < (1ll << 31) && total_nodes >= 0 && total_edges >= 0, "bad sizes");
-    TLC_REQUIRE(h_times && n_times >= 1 && n_times <= TLC_HKS_TMAX, "n_times outside 1 .. TLC_HKS_TMAX");
-    TLC_REQUIRE((flags & ~TLC_HKS_NORMALISE) == 0, "unknown flag");
+namespace {
+
+// tlc_hks_batch (d_dout == nullptr, DT false) and tlc_hks_batch_dt: the same checks, workspace, binning and grids
+template <bool DT>
+int hks_run(const char* fn, const int64_t* d_node_ptr, const int64_t* d_edge_ptr, const int32_t* d_edges, int64_t n_graphs, int64_t total_nodes,
+            int64_t total_edges, const double* h_times, int32_t n_times, uint32_t flags, double* d_out, double* d_dout, uint8_t* d_status,
+            void* d_work, int64_t work_bytes, void* stream) {
+#define HKS_REQUIRE(cond, msg)                                                                                                                 \
+    do {                                                                                                                                       \
+        if (!(cond)) { tlc_set_error("%s: %s", fn, msg); return TLC_ERR_INVALID_ARG; }                                                         \
+    } while (0)
+    HKS_REQUIRE(n_graphs >= 0 && n_graphs < (1ll << 31) && total_nodes >= 0 && total_edges >= 0, "bad sizes");
+    HKS_REQUIRE(h_times && n_times >= 1 && n_times <= TLC_HKS_TMAX, "n_times outside 1 .. TLC_HKS_TMAX");
+    HKS_REQUIRE((flags & ~TLC_HKS_NORMALISE) == 0, "unknown flag");
+    if (DT) HKS_REQUIRE(d_dout, "null d_dout");
     if (n_graphs == 0) return TLC_OK;
-    TLC_REQUIRE(d_node_ptr && d_edge_ptr && d_status && d_work && (total_nodes == 0 || d_out) && (total_edges == 0 || d_edges), "null pointer");
+    HKS_REQUIRE(d_node_ptr && d_edge_ptr && d_status && d_work && (total_nodes == 0 || d_out) && (total_edges == 0 || d_edges), "null pointer");
     HksLayout L;
     const int rc = hks_layout(n_graphs, total_nodes, &L);
     if (rc != TLC_OK) return rc;
-    TLC_REQUIRE(work_bytes >= (int64_t)L.bytes, "d_work is smaller than tlc_hks_batch_work_bytes()");
-    TLC_REQUIRE((reinterpret_cast<uintptr_t>(d_work) & 15) == 0, "d_work must be 16-byte aligned");
+    HKS_REQUIRE(work_bytes >= (int64_t)L.bytes, "d_work is smaller than tlc_hks_batch_work_bytes()");
+    HKS_REQUIRE((reinterpret_cast<uintptr_t>(d_work) & 15) == 0, "d_work must be 16-byte aligned");
+#undef HKS_REQUIRE
     HksTimes times;
     for (int i = 0; i < TLC_HKS_TMAX; ++i) times.t[i] = i < n_times ? h_times[i] : 0.0;
     hipStream_t s = (hipStream_t)stream;
@@ -337,9 +401,15 @@ extern "C" int tlc_hks_batch(const int64_t* d_node_ptr, const int64_t* d_edge_pt
     constexpr size_t lds_wave = 4 * hks_lds_bytes(HKS_WAVE_N, false), lds64 = hks_lds_bytes(HKS_WG64_N, false);
     constexpr size_t lds96 = hks_lds_bytes(HKS_WG96_N, false), lds_gl = hks_lds_bytes(TLC_HKS_NMAX, true);
     static_assert(2 * lds_wave <= 160 * 1024 && 2 * lds64 <= 160 * 1024 && lds96 <= 160 * 1024, "LDS budget of a gfx950 CU");
-    TLC_HIP_CHECK(hipFuncSetAttribute((const void*)hks_tier_kernel<HKS_WAVE_N, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_wave));
-    TLC_HIP_CHECK(hipFuncSetAttribute((const void*)hks_tier_kernel<HKS_WG64_N, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds64));
-    TLC_HIP_CHECK(hipFuncSetAttribute((const void*)hks_tier_kernel<HKS_WG96_N, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds96));
+    if (DT) {
+        TLC_HIP_CHECK(hipFuncSetAttribute((const void*)hks_tier_dt_kernel<HKS_WAVE_N, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_wave));
+        TLC_HIP_CHECK(hipFuncSetAttribute((const void*)hks_tier_dt_kernel<HKS_WG64_N, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds64));
+        TLC_HIP_CHECK(hipFuncSetAttribute((const void*)hks_tier_dt_kernel<HKS_WG96_N, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds96));
+    } else {
+        TLC_HIP_CHECK(hipFuncSetAttribute((const void*)hks_tier_kernel<HKS_WAVE_N, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_wave));
+        TLC_HIP_CHECK(hipFuncSetAttribute((const void*)hks_tier_kernel<HKS_WG64_N, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds64));
+        TLC_HIP_CHECK(hipFuncSetAttribute((const void*)hks_tier_kernel<HKS_WG96_N, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds96));
+    }
     const long long cus = L.cus;
     // a graph of the WG tiers has at least 33 / 65 nodes: no more workgroups than the batch can hold such graphs
     const long long g_wave = std::min<long long>((B + 3) / 4, 2 * cus);
@@ -348,8 +418,13 @@ extern "C" int tlc_hks_batch(const int64_t* d_node_ptr, const int64_t* d_edge_pt
     const long long stride = total_nodes;
 #define HKS_LAUNCH(NMAX, WAVE, GLOBAL, tier, grid, lds)                                                                                        \
     if ((grid) > 0) {                                                                                                                          \
-        hipLaunchKernelGGL((hks_tier_kernel<NMAX, WAVE, GLOBAL>), dim3((unsigned)(grid)), dim3(hks_block(GLOBAL)), lds, s, tier, B, (const long long*)d_node_ptr, \
-                           (const long long*)d_edge_ptr, d_edges, times, (int)n_times, flags, d_out, stride, d_status, head, lists, slots);   \
+        if (DT)                                                                                                                                \
+            hipLaunchKernelGGL((hks_tier_dt_kernel<NMAX, WAVE, GLOBAL>), dim3((unsigned)(grid)), dim3(hks_block(GLOBAL)), lds, s, tier, B,     \
+                               (const long long*)d_node_ptr, (const long long*)d_edge_ptr, d_edges, times, (int)n_times, flags, d_out, d_dout, \
+                               stride, d_status, head, lists, slots);                                                                          \
+        else                                                                                                                                   \
+            hipLaunchKernelGGL((hks_tier_kernel<NMAX, WAVE, GLOBAL>), dim3((unsigned)(grid)), dim3(hks_block(GLOBAL)), lds, s, tier, B, (const long long*)d_node_ptr, \
+                               (const long long*)d_edge_ptr, d_edges, times, (int)n_times, flags, d_out, stride, d_status, head, lists, slots); \
         TLC_HIP_CHECK(hipGetLastError());                                                                                                      \
     }
     HKS_LAUNCH(HKS_WAVE_N, true, false, 0, g_wave, lds_wave)
@@ -358,4 +433,20 @@ extern "C" int tlc_hks_batch(const int64_t* d_node_ptr, const int64_t* d_edge_pt
     HKS_LAUNCH(TLC_HKS_NMAX, false, true, 3, (long long)L.slots, lds_gl)
 #undef HKS_LAUNCH
     return TLC_OK;
+}
+
+}  // namespace
+
+extern "C" int tlc_hks_batch(const int64_t* d_node_ptr, const int64_t* d_edge_ptr, const int32_t* d_edges, int64_t n_graphs, int64_t total_nodes,
+                             int64_t total_edges, const double* h_times, int32_t n_times, uint32_t flags, double* d_out, uint8_t* d_status,
+                             void* d_work, int64_t work_bytes, void* stream) {
+    return hks_run<false>(__func__, d_node_ptr, d_edge_ptr, d_edges, n_graphs, total_nodes, total_edges, h_times, n_times, flags, d_out, nullptr,
+                          d_status, d_work, work_bytes, stream);
+}
+
+extern "C" int tlc_hks_batch_dt(const int64_t* d_node_ptr, const int64_t* d_edge_ptr, const int32_t* d_edges, int64_t n_graphs, int64_t total_nodes,
+                                int64_t total_edges, const double* h_times, int32_t n_times, uint32_t flags, double* d_out, double* d_dout,
+                                uint8_t* d_status, void* d_work, int64_t work_bytes, void* stream) {
+    return hks_run<true>(__func__, d_node_ptr, d_edge_ptr, d_edges, n_graphs, total_nodes, total_edges, h_times, n_times, flags, d_out, d_dout,
+                         d_status, d_work, work_bytes, stream);
 }

@@ -15,6 +15,8 @@
 // tiles, K-steps of HKSL_KS through LDS, one fixed grid walking the group's list of (graph, tile row, tile column)), rows (a wavefront per
 // node), norm (a workgroup per graph).  A K-sum runs in one fixed order inside one wavefront (partial sums of 64 k): no split-K, no atomics on values;
 // the bits of a graph depend on the graph and the time alone.
+// tlc_hks_large_batch_dt: the same products, then rows_dt / norm_dt in place of rows / norm -- the value as above and its derivative in t
+// from the last P and the non-zeros of X (see hksl_rows_dt_kernel); the kernels and launches of tlc_hks_large_batch are unchanged.
 #include "tlc_common.h"
 
 #include <math.h>
@@ -274,6 +276,111 @@ __global__ __launch_bounds__(256) void hksl_norm_kernel(HkslGroup G, const long 
     for (int x = tid; x < d.n; x += 256) o[x] = o[x] / (mx + 1e-10);
 }
 
+// ---- rows with the derivative in t (tlc_hks_large_batch_dt): a wavefront per node -------------------------------------------------------
+// d/dt [K_t]_vv = -[L K_t]_vv = -[K_t]_vv + sum over the neighbours u of v of [K_t]_uv / sqrt(d_u d_v), K_t = exp(-t L).  The last
+// matrix P is K_t itself (diag_only: [K]_uv = P_vu) or K_t/2 ([K]_uv = sum_j P_vj P_uj, the lanes' strided sums and the butterfly of the
+// value), so no further product is needed.  The neighbours are the non-zeros of row v of X (= scale * M until the next time's memset),
+// walked u ascending: 64 columns at a time make one partial sum, the partial sums are added block after block -- an order the graph
+// alone fixes.  at_zero (t = 0: X = 0 names no neighbour, K_0 = I'): -1 for a node of degree > 0.  Columns >= n are never a neighbour
+// and are zero in P.  The value is formed exactly as in hksl_rows_kernel.
+__global__ __launch_bounds__(256) void hksl_rows_dt_kernel(HkslGroup G, const long long* __restrict__ node_ptr, int p_sel, int diag_only, int at_zero,
+                                                           double* __restrict__ out, double* __restrict__ dout) {
+    const int lane = threadIdx.x & 63, row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    for (int gi = blockIdx.y; gi < G.ng; gi += gridDim.y) {
+        if (G.state[gi] != 1) continue;
+        const HkslDesc d = G.descs[gi];
+        if (row >= d.n) continue;
+        const int np = d.np;
+        const double* Pm = hksl_mat(G, d, p_sel);
+        const double* P = Pm + row * np;
+        const int* deg = G.deg + d.deg_off;
+        const int dv = deg[row];
+        double v, dvdt = 0.0;
+        if (dv == 0) v = 1.0;
+        else if (diag_only) v = P[row];
+        else {
+            v = 0.0;
+            for (int c = lane; c < np; c += 64) { const double x = P[c]; v += x * x; }
+            v += tlc_lane_xor_f64<1>(v);
+            v += tlc_lane_xor_f64<2>(v);
+            v += tlc_lane_xor_f64<4>(v);
+            v += tlc_lane_xor_f64<8>(v);
+            v += tlc_lane_xor_f64<16>(v);
+            v += tlc_lane_xor_f64<32>(v);
+        }
+        if (dv > 0 && at_zero) dvdt = -1.0;
+        else if (dv > 0) {
+            const double* X = G.mats + d.x_off + row * np;
+            const double sv = sqrt((double)dv);
+            double sum = 0.0;
+            for (int c0 = 0; c0 < d.n; c0 += 64) {             // c0 + lane < np: np is a multiple of 64
+                unsigned long long nb = __ballot(c0 + lane < d.n && X[c0 + lane] != 0.0);
+                double part = 0.0;
+                while (nb) {                                   // uniform over the wavefront
+                    const int u = c0 + __ffsll((long long)nb) - 1;
+                    nb &= nb - 1;
+                    double k;
+                    if (diag_only) k = P[u];
+                    else {
+                        const double* Q = Pm + u * np;
+                        k = 0.0;
+                        for (int c = lane; c < np; c += 64) k += P[c] * Q[c];
+                        k += tlc_lane_xor_f64<1>(k);
+                        k += tlc_lane_xor_f64<2>(k);
+                        k += tlc_lane_xor_f64<4>(k);
+                        k += tlc_lane_xor_f64<8>(k);
+                        k += tlc_lane_xor_f64<16>(k);
+                        k += tlc_lane_xor_f64<32>(k);
+                    }
+                    part += k / (sv * sqrt((double)deg[u]));
+                }
+                sum += part;
+            }
+            dvdt = sum - v;
+        }
+        if (lane == 0) {
+            out[node_ptr[d.g] + row] = v;
+            dout[node_ptr[d.g] + row] = dvdt;
+        }
+    }
+}
+
+// ---- norm with the derivative: a workgroup per graph.  f = hks / (mx + 1e-10), mx = hks(a) at the LOWEST index a of the maximum:
+// f'(x) = (hks'(x) - f(x) hks'(a)) / (mx + 1e-10); `out` becomes what hksl_norm_kernel makes of it ---------------------------------------
+__global__ __launch_bounds__(256) void hksl_norm_dt_kernel(HkslGroup G, const long long* __restrict__ node_ptr, double* __restrict__ out,
+                                                           double* __restrict__ dout) {
+    __shared__ double smax[256];
+    __shared__ int sarg[256];
+    const int gi = blockIdx.x, tid = threadIdx.x;
+    if (G.state[gi] != 1) return;
+    const HkslDesc d = G.descs[gi];
+    double* o = out + node_ptr[d.g];
+    double* dd = dout + node_ptr[d.g];
+    double mx = o[0];
+    int a = 0;
+    for (int x = tid; x < d.n; x += 256)                       // x ascending: the first of equal values stays
+        if (o[x] > mx) { mx = o[x]; a = x; }
+    smax[tid] = mx;
+    sarg[tid] = a;
+    __syncthreads();
+    for (int h = 128; h > 0; h >>= 1) {
+        if (tid < h) {
+            const double m2 = smax[tid + h];
+            const int a2 = sarg[tid + h];
+            if (m2 > smax[tid] || (m2 == smax[tid] && a2 < sarg[tid])) { smax[tid] = m2; sarg[tid] = a2; }
+        }
+        __syncthreads();
+    }
+    mx = smax[0];
+    const double da = dd[sarg[0]];
+    __syncthreads();                                           // every thread holds hks'(a) before its owner overwrites it
+    for (int x = tid; x < d.n; x += 256) {
+        const double f = o[x] / (mx + 1e-10);
+        o[x] = f;
+        dd[x] = (dd[x] - f * da) / (mx + 1e-10);
+    }
+}
+
 // ---- host side -------------------------------------------------------------------------------------------------------------------------
 inline int64_t hksl_up(int64_t v, int64_t a) { return (v + a - 1) / a * a; }
 inline int64_t hksl_np(int64_t n) { return n > TLC_HKS_LARGE_NMAX ? 0 : hksl_up(n, HKSL_T); }
@@ -304,27 +411,37 @@ extern "C" int tlc_hks_large_work_bytes(const int64_t* h_sel_nodes, int64_t n_se
     return TLC_OK;
 }
 
-extern "C" int tlc_hks_large_batch(const int64_t* d_node_ptr, const int64_t* d_edge_ptr, const int32_t* d_edges, int64_t n_graphs, int64_t total_nodes,
-                                   int64_t total_edges, const int64_t* h_sel, const int64_t* h_sel_nodes, int64_t n_sel, const double* h_times,
-                                   int32_t n_times, uint32_t flags, double* d_out, uint8_t* d_status, void* d_work, int64_t work_bytes, void* stream) {
-    TLC_REQUIRE(n_graphs >= 0 && n_graphs < (1ll << 31) && total_nodes >= 0 && total_edges >= 0, "bad sizes");
-    TLC_REQUIRE(n_sel >= 0 && n_sel <= n_graphs, "n_sel outside 0 .. n_graphs");
-    TLC_REQUIRE(h_times && n_times >= 1 && n_times <= TLC_HKS_TMAX, "n_times outside 1 .. TLC_HKS_TMAX");
-    TLC_REQUIRE((flags & ~TLC_HKS_NORMALISE) == 0, "unknown flag");
+namespace {
+
+#define HKSL_REQUIRE(cond, msg)                                                                                                                \
+    do {                                                                                                                                       \
+        if (!(cond)) { tlc_set_error("%s: %s", fn, msg); return TLC_ERR_INVALID_ARG; }                                                         \
+    } while (0)
+
+// tlc_hks_large_batch (d_dout == nullptr, DT false) and tlc_hks_large_batch_dt: the same checks, groups, workspace and products
+template <bool DT>
+int hksl_run(const char* fn, const int64_t* d_node_ptr, const int64_t* d_edge_ptr, const int32_t* d_edges, int64_t n_graphs, int64_t total_nodes,
+             int64_t total_edges, const int64_t* h_sel, const int64_t* h_sel_nodes, int64_t n_sel, const double* h_times, int32_t n_times,
+             uint32_t flags, double* d_out, double* d_dout, uint8_t* d_status, void* d_work, int64_t work_bytes, void* stream) {
+    HKSL_REQUIRE(n_graphs >= 0 && n_graphs < (1ll << 31) && total_nodes >= 0 && total_edges >= 0, "bad sizes");
+    HKSL_REQUIRE(n_sel >= 0 && n_sel <= n_graphs, "n_sel outside 0 .. n_graphs");
+    HKSL_REQUIRE(h_times && n_times >= 1 && n_times <= TLC_HKS_TMAX, "n_times outside 1 .. TLC_HKS_TMAX");
+    HKSL_REQUIRE((flags & ~TLC_HKS_NORMALISE) == 0, "unknown flag");
     for (int i = 0; i < n_times; ++i)
-        TLC_REQUIRE(isfinite(h_times[i]) && h_times[i] >= 0.0 && h_times[i] <= TLC_HKS_LARGE_TIME_MAX, "a time outside [0, TLC_HKS_LARGE_TIME_MAX]");
-    TLC_REQUIRE(n_sel == 0 || (h_sel && h_sel_nodes), "null pointer");
+        HKSL_REQUIRE(isfinite(h_times[i]) && h_times[i] >= 0.0 && h_times[i] <= TLC_HKS_LARGE_TIME_MAX, "a time outside [0, TLC_HKS_LARGE_TIME_MAX]");
+    if (DT) HKSL_REQUIRE(d_dout, "null d_dout");
+    HKSL_REQUIRE(n_sel == 0 || (h_sel && h_sel_nodes), "null pointer");
     for (int64_t i = 0; i < n_sel; ++i) {
-        TLC_REQUIRE(h_sel[i] >= 0 && h_sel[i] < n_graphs && (i == 0 || h_sel[i] > h_sel[i - 1]), "h_sel is not strictly ascending inside 0 .. n_graphs-1");
-        TLC_REQUIRE(h_sel_nodes[i] >= 0, "negative node count");
+        HKSL_REQUIRE(h_sel[i] >= 0 && h_sel[i] < n_graphs && (i == 0 || h_sel[i] > h_sel[i - 1]), "h_sel is not strictly ascending inside 0 .. n_graphs-1");
+        HKSL_REQUIRE(h_sel_nodes[i] >= 0, "negative node count");
     }
     if (n_sel == 0) return TLC_OK;
-    TLC_REQUIRE(d_node_ptr && d_edge_ptr && d_status && d_work && (total_nodes == 0 || d_out) && (total_edges == 0 || d_edges), "null pointer");
+    HKSL_REQUIRE(d_node_ptr && d_edge_ptr && d_status && d_work && (total_nodes == 0 || d_out) && (total_edges == 0 || d_edges), "null pointer");
     int64_t min_bytes = 0, all_bytes = 0;
     const int rc = tlc_hks_large_work_bytes(h_sel_nodes, n_sel, n_times, &min_bytes, &all_bytes);
     if (rc != TLC_OK) return rc;
-    TLC_REQUIRE(work_bytes >= min_bytes, "d_work is smaller than tlc_hks_large_work_bytes()'s min_bytes");
-    TLC_REQUIRE((reinterpret_cast<uintptr_t>(d_work) & 15) == 0, "d_work must be 16-byte aligned");
+    HKSL_REQUIRE(work_bytes >= min_bytes, "d_work is smaller than tlc_hks_large_work_bytes()'s min_bytes");
+    HKSL_REQUIRE((reinterpret_cast<uintptr_t>(d_work) & 15) == 0, "d_work must be 16-byte aligned");
     int dev = 0, cus = 0;
     TLC_HIP_CHECK(hipGetDevice(&dev));
     TLC_HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
@@ -353,7 +470,7 @@ extern "C" int tlc_hks_large_batch(const int64_t* d_node_ptr, const int64_t* d_e
         const size_t item_off = (size_t)hksl_up(deg_off + deg_ints * sizeof(int), HKSL_ALIGN);
         const size_t mat_off = (size_t)hksl_up(item_off + n_items * sizeof(int4), HKSL_ALIGN);
         if ((int64_t)(mat_off + 3 * mat_doubles * sizeof(double)) > work_bytes) {
-            tlc_set_error("%s: internal: a group of %lld graphs does not fit its workspace", __func__, (long long)ng);
+            tlc_set_error("%s: internal: a group of %lld graphs does not fit its workspace", fn, (long long)ng);
             return TLC_ERR_INVALID_ARG;
         }
         {
@@ -409,6 +526,17 @@ extern "C" int tlc_hks_large_batch(const int64_t* d_node_ptr, const int64_t* d_e
             }
             double* out_t = d_out + (size_t)t * (size_t)total_nodes;
             const unsigned gy = (unsigned)(ng < 65535 ? ng : 65535);
+            if (DT) {                                          // the value as below and its derivative in t, from the same last matrix
+                double* dout_t = d_dout + (size_t)t * (size_t)total_nodes;
+                hipLaunchKernelGGL(hksl_rows_dt_kernel, dim3((unsigned)((max_n + 3) / 4), gy), dim3(256), 0, s, G, (const long long*)d_node_ptr,
+                                   cur, sq == 0 ? 1 : 0, time == 0.0 ? 1 : 0, out_t, dout_t);
+                TLC_HIP_CHECK(hipGetLastError());
+                if (flags & TLC_HKS_NORMALISE) {
+                    hipLaunchKernelGGL(hksl_norm_dt_kernel, dim3((unsigned)ng), dim3(256), 0, s, G, (const long long*)d_node_ptr, out_t, dout_t);
+                    TLC_HIP_CHECK(hipGetLastError());
+                }
+                continue;
+            }
             hipLaunchKernelGGL(hksl_rows_kernel, dim3((unsigned)((max_n + 3) / 4), gy), dim3(256), 0, s, G, (const long long*)d_node_ptr, cur,
                                sq == 0 ? 1 : 0, out_t);
             TLC_HIP_CHECK(hipGetLastError());
@@ -420,4 +548,22 @@ extern "C" int tlc_hks_large_batch(const int64_t* d_node_ptr, const int64_t* d_e
         first = last;
     }
     return TLC_OK;
+}
+#undef HKSL_REQUIRE
+
+}  // namespace
+
+extern "C" int tlc_hks_large_batch(const int64_t* d_node_ptr, const int64_t* d_edge_ptr, const int32_t* d_edges, int64_t n_graphs, int64_t total_nodes,
+                                   int64_t total_edges, const int64_t* h_sel, const int64_t* h_sel_nodes, int64_t n_sel, const double* h_times,
+                                   int32_t n_times, uint32_t flags, double* d_out, uint8_t* d_status, void* d_work, int64_t work_bytes, void* stream) {
+    return hksl_run<false>(__func__, d_node_ptr, d_edge_ptr, d_edges, n_graphs, total_nodes, total_edges, h_sel, h_sel_nodes, n_sel, h_times, n_times,
+                           flags, d_out, nullptr, d_status, d_work, work_bytes, stream);
+}
+
+extern "C" int tlc_hks_large_batch_dt(const int64_t* d_node_ptr, const int64_t* d_edge_ptr, const int32_t* d_edges, int64_t n_graphs,
+                                      int64_t total_nodes, int64_t total_edges, const int64_t* h_sel, const int64_t* h_sel_nodes, int64_t n_sel,
+                                      const double* h_times, int32_t n_times, uint32_t flags, double* d_out, double* d_dout, uint8_t* d_status,
+                                      void* d_work, int64_t work_bytes, void* stream) {
+    return hksl_run<true>(__func__, d_node_ptr, d_edge_ptr, d_edges, n_graphs, total_nodes, total_edges, h_sel, h_sel_nodes, n_sel, h_times, n_times,
+                          flags, d_out, d_dout, d_status, d_work, work_bytes, stream);
 }

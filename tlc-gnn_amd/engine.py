@@ -276,7 +276,7 @@ def pack_offsets(n, m):
 
 
 @_lib.on_device_of
-def hks_batch(node_ptr, edge_ptr, edges, times, normalise=True, total_nodes=None):
+def hks_batch(node_ptr, edge_ptr, edges, times, normalise=True, total_nodes=None, dt=False):
     """Heat-kernel signatures of a packed batch of simple graphs on the device (tlc_hks_batch; `hks_signature` of the reference's
     data_utils_LP/NC/GC, one Jacobi eigen-decomposition per graph shared by all `times`).
 
@@ -286,7 +286,9 @@ def hks_batch(node_ptr, edge_ptr, edges, times, normalise=True, total_nodes=None
     beyond the totals, an id outside 0 .. n-1, a self loop, or an unordered pair listed twice, in the same or in both directions --
     each undirected edge once is the contract, a multigraph is refused and never computed differently from the host route) has NaN in
     its slice.
-    total_nodes: sum n if the caller has it already (`Vicinities.batch` does); else node_ptr[-1] is read, the call's only host read."""
+    total_nodes: sum n if the caller has it already (`Vicinities.batch` does); else node_ptr[-1] is read, the call's only host read.
+    dt=True: tlc_hks_batch_dt, returns (f, df, status) with df float64[T, sum n] = d f / d t of exactly what f holds (normalised when f
+    is: the quotient rule at the lowest index of the maximum); f and status are the same bits, df is NaN where f is."""
     torch = _lib.require_gpu()
     dev = node_ptr.device
     times = [float(t) for t in (times if hasattr(times, "__len__") else [times])]
@@ -302,11 +304,21 @@ def hks_batch(node_ptr, edge_ptr, edges, times, normalise=True, total_nodes=None
         _lib.check(_lib.lib().tlc_hks_batch_work_bytes(C.c_int64(B), C.c_int64(tot_n), C.c_int64(tot_m), C.c_int32(T), C.byref(need)),
                    "tlc_hks_batch_work_bytes")
         work = torch.empty(need.value, dtype=torch.uint8, device=dev)
+        if dt:
+            dout = torch.full((T, tot_n), float("nan"), dtype=torch.float64, device=dev)
+            rc = _lib.lib().tlc_hks_batch_dt(_lib.ptr(node_ptr.contiguous()), _lib.ptr(edge_ptr.contiguous()), _lib.ptr(edges.contiguous()),
+                                             C.c_int64(B), C.c_int64(tot_n), C.c_int64(tot_m), (C.c_double * T)(*times), C.c_int32(T),
+                                             C.c_uint32(_lib.HKS_NORMALISE if normalise else 0), _lib.ptr(out), _lib.ptr(dout), _lib.ptr(status),
+                                             _lib.ptr(work), C.c_int64(need.value), _lib.stream_ptr())
+            _lib.check(rc, "tlc_hks_batch_dt")
+            return out, dout, status[:B]
         rc = _lib.lib().tlc_hks_batch(_lib.ptr(node_ptr.contiguous()), _lib.ptr(edge_ptr.contiguous()), _lib.ptr(edges.contiguous()),
                                       C.c_int64(B), C.c_int64(tot_n), C.c_int64(tot_m), (C.c_double * T)(*times), C.c_int32(T),
                                       C.c_uint32(_lib.HKS_NORMALISE if normalise else 0), _lib.ptr(out), _lib.ptr(status), _lib.ptr(work),
                                       C.c_int64(need.value), _lib.stream_ptr())
         _lib.check(rc, "tlc_hks_batch")
+    if dt:
+        return out, torch.full((T, tot_n), float("nan"), dtype=torch.float64, device=dev), status[:B]
     return out, status[:B]
 
 
@@ -324,7 +336,8 @@ def hks_large_work_bytes(sel_nodes, n_times=1):
 
 
 @_lib.on_device_of
-def hks_large_batch(node_ptr, edge_ptr, edges, sel, sel_nodes, times, normalise=True, total_nodes=None, out=None, status=None, work_bytes=None):
+def hks_large_batch(node_ptr, edge_ptr, edges, sel, sel_nodes, times, normalise=True, total_nodes=None, out=None, status=None, work_bytes=None,
+                    dout=None):
     """Heat-kernel signatures of SELECTED graphs of a packed batch on the device without eigenpairs (tlc_hks_large_batch: exp(-tL) by
     scaling, a degree-14 Taylor series and squarings, fp64 products on the matrix cores) -- the tier for graphs above HKS_NMAX nodes,
     up to HKS_LARGE_NMAX; times inside [0, HKS_LARGE_TIME_MAX].
@@ -334,7 +347,9 @@ def hks_large_batch(node_ptr, edge_ptr, edges, sel, sel_nodes, times, normalise=
     that is not the device's is ST_BAD_INPUT, one above HKS_LARGE_NMAX ST_TOO_LARGE).  out float64[T, sum n] / status uint8[B]: written
     for the selected graphs only (given: e.g. what `hks_batch` returned; not given: NaN-filled / zero-filled).  work_bytes: the
     workspace to allocate, at least min_bytes of `hks_large_work_bytes` (the selection then runs in groups that fit, same bits);
-    None: all_bytes, bounded by HKS_LARGE_WORK_CAP.  Returns (out, status)."""
+    None: all_bytes, bounded by HKS_LARGE_WORK_CAP.  Returns (out, status).
+    dout: True or a contiguous float64[T, sum n] (e.g. the df of `hks_batch(dt=True)`): tlc_hks_large_batch_dt writes the selected graphs'
+    d out / d t into it, out and status the same bits; returns (out, dout, status)."""
     torch = _lib.require_gpu()
     dev = node_ptr.device
     times = [float(t) for t in (times if hasattr(times, "__len__") else [times])]
@@ -353,17 +368,33 @@ def hks_large_batch(node_ptr, edge_ptr, edges, sel, sel_nodes, times, normalise=
     if tuple(out.shape) != (T, tot_n) or out.dtype != torch.float64 or not out.is_contiguous() or status.numel() != B or status.dtype != torch.uint8 \
             or not status.is_contiguous():
         raise ValueError("hks_large_batch: out should be contiguous float64[%d, %d] and status contiguous uint8[%d]" % (T, tot_n, B))
+    want_dt = dout is not None and dout is not False
+    if want_dt:
+        if dout is True:
+            dout = torch.full((T, tot_n), float("nan"), dtype=torch.float64, device=dev)
+        if tuple(dout.shape) != (T, tot_n) or dout.dtype != torch.float64 or not dout.is_contiguous():
+            raise ValueError("hks_large_batch: dout should be contiguous float64[%d, %d]" % (T, tot_n))
     S = len(sel)
     if S > 0:
         lo, hi = hks_large_work_bytes(sel_nodes, T)
         need = max(lo, min(hi, HKS_LARGE_WORK_CAP)) if work_bytes is None else int(work_bytes)
         work = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+        if want_dt:
+            rc = _lib.lib().tlc_hks_large_batch_dt(_lib.ptr(node_ptr.contiguous()), _lib.ptr(edge_ptr.contiguous()), _lib.ptr(edges.contiguous()),
+                                                   C.c_int64(B), C.c_int64(tot_n), C.c_int64(tot_m), (C.c_int64 * S)(*sel), (C.c_int64 * S)(*sel_nodes),
+                                                   C.c_int64(S), (C.c_double * T)(*times), C.c_int32(T),
+                                                   C.c_uint32(_lib.HKS_NORMALISE if normalise else 0), _lib.ptr(out), _lib.ptr(dout), _lib.ptr(status),
+                                                   _lib.ptr(work), C.c_int64(need), _lib.stream_ptr())
+            _lib.check(rc, "tlc_hks_large_batch_dt")
+            return out, dout, status
         rc = _lib.lib().tlc_hks_large_batch(_lib.ptr(node_ptr.contiguous()), _lib.ptr(edge_ptr.contiguous()), _lib.ptr(edges.contiguous()),
                                             C.c_int64(B), C.c_int64(tot_n), C.c_int64(tot_m), (C.c_int64 * S)(*sel), (C.c_int64 * S)(*sel_nodes),
                                             C.c_int64(S), (C.c_double * T)(*times), C.c_int32(T),
                                             C.c_uint32(_lib.HKS_NORMALISE if normalise else 0), _lib.ptr(out), _lib.ptr(status), _lib.ptr(work),
                                             C.c_int64(need), _lib.stream_ptr())
         _lib.check(rc, "tlc_hks_large_batch")
+    if want_dt:
+        return out, dout, status
     return out, status
 
 

@@ -4,6 +4,10 @@ function of the node values f, composed with the imager and the Wasserstein loss
     f (an MLP on node features, an HKS time, ...)  ->  diagrams(f, ...)  ->  images(...) / wasserstein_to(...) /
                                                        sliced_wasserstein_to(...)  ->  loss.backward()
 
+`hks_filtration(time, ...)` is the second of these filtrations: the normalised heat-kernel signature as a differentiable function of its
+diffusion time (`autograd.hks_signature`: values and d / d t from tlc_hks_batch_dt and tlc_hks_large_batch_dt), so a time can be learned
+through everything below.
+
 The diagrams are `engine.pd_from_filtration`'s with TLC_KEEP_ZERO_PERS (what `data_utils_GC.compute_persistence_image` computes),
 bit for bit; their gradient is the selection of `autograd.ExtendedPersistence`: each coordinate is a copy of one
 f[v].  All arguments are CUDA tensors in the packed layout of `engine.pd_from_filtration`: node_offs / edge_offs int64[B + 1], edges
@@ -19,6 +23,16 @@ def check_which(which):
     if which not in WHICH:
         raise ValueError("which should be one of %s, not %r" % (WHICH, which))
     return which
+
+
+def hks_filtration(time, node_offs, edge_offs, edges, normalise=True):
+    """-> float64[sum n]: the heat-kernel-signature filtration of every graph at the diffusion time `time` (a scalar or one-element float
+    tensor, which may require grad), the values of `data_utils_LP.hks_filtration_device(..., hks_large='device')` bit for bit.  It goes
+    straight into `diagrams` / `images` / `wasserstein_to` / `sliced_wasserstein_to` as f, and their gradient reaches `time`.  The time is
+    read to the host once per call; a graph the device tiers do not take raises RuntimeError (`autograd.hks_signature`)."""
+    if not torch.is_tensor(time) or time.numel() != 1:
+        raise ValueError("hks_filtration: time should be a scalar or one-element tensor")
+    return autograd.hks_signature(time.reshape(1), node_offs, edge_offs, edges, normalise=normalise)[0]
 
 
 def diagrams(f, node_offs, edge_offs, edges, pd_large="host"):
