@@ -1014,6 +1014,70 @@ int tlc_ollivier_ricci_otd(int32_t n_nodes, const int32_t* d_rowptr, const int32
                            int32_t alpha_num, int32_t alpha_den, double* d_kappa, int64_t* d_cost, int64_t* d_denom, void* d_work,
                            int64_t work_bytes, int32_t max_support, int64_t max_product, void* stream);
 
+/* ---- The distance filtration of a packed batch, and its vector-Jacobian product in the edge weights (csrc/dist_filt.hip, DESIGN.md
+ * 6.10): filtration.build_fv (sg2dgm/riccidist2dgm.py:20-56) and ricci_filtration.build_fv (Knowledge_Distillation/data_utils_NC.py:34-55,
+ * data_utils_LP.py:35-65) on graphs the caller packs, without a graph handle, a pair list or a size cap.
+ * Input: the packed batch of tlc_struct_batch (d_node_ptr / d_edge_ptr int64[n_graphs + 1], d_edges int32[total_edges, 2] local ids, every
+ * undirected edge ONCE), d_w float64[total_edges] (kappa + 1 of the edge), d_roots int32[n_graphs, 2] local ids; roots[g, 1] == -1: one
+ * root (and TLC_DESC_ROOT1: the first root alone for every graph); equal roots are allowed.
+ * Value, bit for bit the reference's: D_r[x] = the minimum over the paths x -> r of the left-to-right fp64 sum of the weights that
+ * starts at x, 100 where r cannot be reached (TLC_UNREACHABLE_100; without the flag a graph with a node that root 0 does not reach is
+ * TLC_ST_DISCONNECTED, as in tlc_vicinity_filtration); q[x] = 0 at a root, else D_0 + D_1 / min / max by TLC_DESC_*, D_0 for one root;
+ * f = q / max q ('min': / max_x max(D_0, D_1), the roots counting as 0), TLC_NORM_EPS: / (that maximum + 1e-10), TLC_NO_NORM: f = q.
+ * TLC_INCLUDE_ROOTS is accepted and changes nothing: it adds the roots to an EXTRACTED vicinity, and a packed graph holds its roots.
+ * d_f float64[total_nodes].  d_status uint8[n_graphs]: TLC_ST_OK; TLC_ST_BAD_INPUT (the contract of tlc_struct_batch on offsets, ids,
+ * loops and repeated pairs; a weight that is not finite and > 0; a root outside 0 .. n-1); TLC_ST_DISCONNECTED; TLC_ST_ZERO_RANGE (the
+ * maximum is 0 and neither TLC_NORM_EPS nor TLC_NO_NORM is set).  The d_f slice of a graph that is not TLC_ST_OK is left untouched and no
+ * other graph is affected.  A graph without nodes: TLC_ST_OK, nothing written.
+ * d_parent int32[2, total_nodes] (may be NULL), written for every graph that is not TLC_ST_BAD_INPUT: THE TREE of root r.  With R_r the
+ * root-sourced fixpoint (R_r[r] = 0, R_r[x] = min over the neighbours y of fl(R_r[y] + w(x, y))), P_r[x] = the lowest local id y among the
+ * neighbours of x with R_r[y] < R_r[x] and fl(R_r[y] + w(x, y)) == R_r[x] (IEEE ==); -1 for the root, for a node r does not reach, for a
+ * node without such a neighbour (only where rounding absorbs a weight), and in row 1 of a graph with one root.  With pairwise distinct path
+ * lengths (what learned weights have) this is the shortest-path tree and the path behind D_r[x] is x's tree path.  Under ties the
+ * filtration is not differentiable and this tree is the fixed convention (the stance of tlc_pd_point_vertices).
+ * Size classes, cut on the device: up to TLC_DIST_WAVE_NMAX nodes a wavefront per graph; up to TLC_DIST_WG_NMAX nodes and TLC_DIST_WG_MMAX
+ * edges a workgroup per graph, distances in LDS; larger: the whole device, distances in d_work, a launch per Bellman-Ford round, the
+ * "changed" word read back every 8 rounds (the entry then synchronises the stream; a batch of at most TLC_DIST_WG_NMAX nodes and
+ * TLC_DIST_WG_MMAX edges in total never does).  No floating-point atomics: a graph's bits depend neither on the batch, nor on d_work, nor
+ * on the run.  d_work: 256-byte aligned, at least tlc_dist_filtration_work_bytes() bytes (host arithmetic; 16 B per edge + 12 B per graph,
+ * and 56 B per node when the batch can hold a graph of the third class); more bytes = more per-source fallback searches of that class in
+ * flight (8 B per node each, up to 256).  The u64 at byte TLC_DIST_WORK_FALLBACKS_OFF of d_work counts the sources that took the fallback.
+ * TLC_ERR_INVALID_ARG, nothing launched: null required pointers, negative sizes, an unknown flag, a d_work below the minimum or
+ * misaligned.  TLC_ERR_UNSUPPORTED: 2^30 nodes or edges in the batch.  n_graphs == 0: TLC_OK, nothing read.
+ *
+ * tlc_dist_filtration_vjp: the forward's inputs and flags, d_parent of that forward, d_grad_f float64[total_nodes] -> d_grad_w
+ * float64[total_edges], every entry of every TLC_ST_OK graph, zeros included (other graphs: untouched).  d_f is not read (may be NULL):
+ * the values are rebuilt from the tree.  d_status: TLC_ST_OK, TLC_ST_BAD_INPUT, TLC_ST_ZERO_RANGE as above.  The specification, in this
+ * order of operations (fp64, no fused multiply-add); r runs over root 0 and, with two roots, root 1:
+ *   e_r[x]  = the edge (x, P_r[x]) if P_r[x] >= 0 and that edge exists, else none.
+ *   T_r[x]  = t after: t = +0.0; c = x; while c has e_r[c] (at most n steps): t = t + w[e_r[c]], c = P_r[c].  If the walk does not end at
+ *             root r, x "does not arrive" at r and T_r[x] = 100.  depth_r[x] = the steps of that walk.
+ *   q[x]    = 0 at a root; else T_0 + T_1 / min / max / T_0, as the forward.  dm[x] = q[x], but max(T_0, T_1) for 'min' (0 at a root).
+ *   den0    = max_x dm[x];  den = den0, den0 + 1e-10 (TLC_NORM_EPS) or 1 (TLC_NO_NORM);  x* = the lowest x with dm[x] == den0.
+ *   a[x]    = g[x] / den;  corr = (sum over x ascending, from +0.0, of g[x] * q[x]) / (den * den), only with a normalisation.
+ *   sel_r(x): root r contributes to q[x] -- 'sum' and one root: yes; 'min': r == (T_1 < T_0 ? 1 : 0); 'max': r == (T_1 > T_0 ? 1 : 0).
+ *   dsel_r(x): root r contributes to dm[x] -- as sel_r, but for 'min': r == (T_1 > T_0 ? 1 : 0)  (the divisor of 'min' is a 'max').
+ *   c_r[x]  = a[x] if sel_r(x), else +0.0;  with a normalisation and x == x* and dsel_r(x): c_r[x] = c_r[x] - corr;
+ *             c_r[x] = +0.0 where the value is forced: x is a root, or x does not arrive at r (the sentinel).
+ *   S_r[x]  = c_r[x], then + S_r[z] for the tree children z of x (e_r[z] exists and P_r[z] == x) in ascending id; computed level by
+ *             level from the deepest depth_r, every node PULLING over its child list, never a child pushing.
+ *   grad_w[e] = +0.0, then + S_0[z] if e == e_0[z] for one of its ends z, then + S_1[z] likewise.
+ * A group of 64 threads (up to TLC_DIST_WAVE_NMAX nodes) or 256 threads per graph, all state in d_work (tlc_dist_filtration_vjp_work_bytes():
+ * 72 B per node + 16 B per edge + 12 B per graph), no host synchronisation. */
+#define TLC_DIST_WAVE_NMAX          64      /* most nodes of a graph that one wavefront computes */
+#define TLC_DIST_WG_NMAX            2048    /* most nodes ... */
+#define TLC_DIST_WG_MMAX            4096    /* ... and most undirected edges of a graph that one workgroup computes in LDS */
+#define TLC_DIST_WORK_FALLBACKS_OFF 64      /* byte offset in d_work of the u64 count of sources that took the fallback search */
+int tlc_dist_filtration_work_bytes(int64_t n_graphs, int64_t total_nodes, int64_t total_edges, int64_t* bytes);
+int tlc_dist_filtration_vjp_work_bytes(int64_t n_graphs, int64_t total_nodes, int64_t total_edges, int64_t* bytes);
+int tlc_dist_filtration(int64_t n_graphs, const int64_t* d_node_ptr, const int64_t* d_edge_ptr, const int32_t* d_edges,
+                        const double* d_w, const int32_t* d_roots, int64_t total_nodes, int64_t total_edges, uint32_t flags,
+                        double* d_f, uint8_t* d_status, int32_t* d_parent, void* d_work, int64_t work_bytes, void* stream);
+int tlc_dist_filtration_vjp(int64_t n_graphs, const int64_t* d_node_ptr, const int64_t* d_edge_ptr, const int32_t* d_edges,
+                            const double* d_w, const int32_t* d_roots, int64_t total_nodes, int64_t total_edges, uint32_t flags,
+                            const double* d_f, const int32_t* d_parent, const double* d_grad_f, double* d_grad_w,
+                            uint8_t* d_status, void* d_work, int64_t work_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -4,6 +4,8 @@ classification: whole graph = one diagram) and for the forward-only loop of trai
   compute_persistence_image :98-170 (filt='degree' and 'hks': node functions on the host, the reference's own numpy / scipy calls; 'hks'
   on the device with hks_backend='device'; 'degree', and in the batch call 'centrality' and 'clustering', on the device with
   struct_backend='device'),
+  filt='ricci' with the curvature as an input: `ricci_filtration_device` (tlc_dist_filtration; data_utils_NC's build_fv with root 0 and
+  norm=True -- the reference's own branch :121-124 cannot run, see there),
   original_extended_persistence :78-82, call :228-279 (largest connected component, relabel), evaluate_time :118-143.
 
 The extended persistence of every graph runs in `tlc_pd_from_filtration` (Knowledge_Distillation fork: zero-persistence pairs
@@ -55,11 +57,67 @@ def hks_filtration(n, edges, hks_time):
     return v / (max(v) + 1e-10)
 
 
+def edge_weights(edges, ricci_curv):
+    """kappa + 1 of every row of edges [m, 2] from one graph's curvature in any of the reference's forms: the list of [u, v, kappa] rows
+    that `compute_ricci_curvature` writes (either or both directions), or the dict {(u, v): kappa} that `data_utils_NC` builds of it."""
+    if isinstance(ricci_curv, dict):
+        table = ricci_curv
+    else:
+        table = {}
+        for u, v, k in (ricci_curv.tolist() if hasattr(ricci_curv, "tolist") else ricci_curv):
+            table[(int(u), int(v))] = float(k)
+    out = np.empty(len(edges), dtype=np.float64)
+    for i, (a, b) in enumerate(np.asarray(edges).tolist()):
+        k = table.get((a, b), table.get((b, a)))
+        if k is None:
+            raise KeyError("ricci_curv has no entry for the edge (%d, %d)" % (a, b))
+        out[i] = k + 1.0
+    return out
+
+
+def ricci_filtration_device(node_ptr, edge_ptr, edges, w, total_nodes=None):
+    """filt='ricci' on a packed batch: `data_utils_NC.ricci_filtration(g, 0, hop, curv).build_fv(weight_graph=True, norm=True)` of every
+    graph -- the weighted shortest-path distance to node 0 over the weights w = kappa + 1, 100 where node 0 is not reached, divided by
+    (the maximum + 1e-10) -- from `engine.dist_filtration` (tlc_dist_filtration), bit for bit.
+    This is NOT the reference's own graph-classification branch (data_utils_GC.py:121-124), which cannot run: it hands `build_fv` the
+    curvature as a list of [u, v, kappa] rows, `build_fv` indexes that list with a tuple (:45), and its `except BaseException` turns
+    every distance into 100.  The intended behaviour is the node-classification file's, which builds the dict first."""
+    import torch
+    B = node_ptr.numel() - 1
+    roots = torch.stack([torch.zeros(B, dtype=torch.int32, device=node_ptr.device), torch.full((B,), -1, dtype=torch.int32, device=node_ptr.device)], 1)
+    return engine.dist_filtration(node_ptr, edge_ptr, edges, w, roots.contiguous(), descriptor="sum", norm="max_eps", unreachable_100=True,
+                                  total_nodes=total_nodes)[0]
+
+
+def packed_curvature(node_ptr, edge_ptr, edges, alpha=0.5, method="OTD"):
+    """Ollivier-Ricci curvature of every edge of a packed batch of simple graphs (each undirected edge once, local ids) in ONE call of the
+    curvature engine on the block-diagonal union graph: the curvature of an edge depends on its endpoints' neighbourhoods only, so the
+    union gives each graph's own values.  -> float64[sum m] numpy, aligned with `edges`.  method 'OTD' (`engine.ollivier_ricci_otd`) or
+    'Sinkhorn' (`engine.ollivier_ricci_sinkhorn`).  The engines take host CSR arrays, so the batch is read back once."""
+    from ..synth import edges_to_csr
+    no, eo, e = (np.asarray(t.cpu()) if hasattr(t, "cpu") else np.asarray(t) for t in (node_ptr, edge_ptr, edges))
+    e = e.reshape(-1, 2).astype(np.int64)
+    g = e + np.repeat(no[:-1], np.diff(eo))[:, None]
+    rowptr, col, _ = edges_to_csr(int(no[-1]), g)
+    if method == "OTD":
+        return engine.ollivier_ricci_otd(rowptr, col, g, alpha=alpha)
+    if method == "Sinkhorn":
+        return engine.ollivier_ricci_sinkhorn(rowptr, col, g, alpha=alpha)
+    raise ValueError("packed_curvature: method 'OTD' or 'Sinkhorn', not %r" % (method,))
+
+
+def _need_curvature(what):
+    return NotImplementedError("data_utils_GC (HIP): filt='ricci' takes the curvature as an input (%s); it is not computed here -- "
+                               "`packed_curvature` computes it for a packed batch" % what)
+
+
 def compute_persistence_image_batch(graphs, filt='degree', filtrations=None, hks_time=0.1, hks_backend='host', struct_backend='host',
-                                    hks_large='host', pd_large='host'):
+                                    hks_large='host', pd_large='host', ricci_curv=None):
     """graphs: list of networkx-like graphs with nodes 0..n-1, or (n, edges[m,2]) tuples.
     Returns a list with the reference's 9-tuple per graph (:166), or (None, None) for graphs without an edge / not
     connected (:101-103).  filt: 'degree' or 'hks' (host side, :114-119); `filtrations` supplies f per graph for anything else.
+    filt='ricci' with ricci_curv = one curvature per graph (each in a form `edge_weights` takes): `ricci_filtration_device` on the whole
+    list in one launch (each undirected edge once, like the device backends) -- see there why this is not the reference's GC branch.
     hks_backend='device': filt='hks' from `tlc_hks_batch`, one launch for the whole list (`data_utils_LP.hks_filtration_device`; graphs
     it does not take are counted in `data_utils_LP.hks_host_fallback`); it has no effect on the other filtrations.
     hks_large='device': with filt='hks' and hks_backend='device', the graphs above _lib.HKS_NMAX nodes from `tlc_hks_large_batch` instead of
@@ -82,8 +140,11 @@ def compute_persistence_image_batch(graphs, filt='degree', filtrations=None, hks
     check_hks_large(hks_large)
     engine.check_pd_large(pd_large)
     on_device = filtrations is None and filt in STRUCT_DEVICE_FILTS and struct_backend == 'device'
-    if filt not in ('degree', 'hks') and filtrations is None and not on_device:
-        raise NotImplementedError("data_utils_GC (HIP): filt='degree' and 'hks' are computed here; pass `filtrations` for anything else")
+    ricci = filtrations is None and filt == 'ricci'
+    if ricci and ricci_curv is None:
+        raise _need_curvature("ricci_curv: a list with one curvature per graph")
+    if filt not in ('degree', 'hks') and filtrations is None and not on_device and not ricci:
+        raise NotImplementedError("data_utils_GC (HIP): filt='degree', 'hks' and 'ricci' are computed here; pass `filtrations` for anything else")
     parsed, keep = [], []
     for gi, g in enumerate(graphs):
         n, e = _edges_nodes(g)
@@ -101,6 +162,11 @@ def compute_persistence_image_batch(graphs, filt='degree', filtrations=None, hks
     d_node_offs, d_edge_offs, d_edges = torch.from_numpy(node_offs).to(dev), torch.from_numpy(edge_offs).to(dev), torch.from_numpy(edges).to(dev)
     if filtrations is None and filt == 'hks' and hks_backend == 'device':
         d_f = hks_filtration_device(d_node_offs, d_edge_offs, d_edges, hks_time, int(node_offs[-1]), hks_large=hks_large)
+        f = d_f.cpu().numpy()
+        fs = [f[node_offs[k]:node_offs[k + 1]] for k in range(len(keep))]
+    elif ricci:
+        d_w = torch.from_numpy(np.concatenate([edge_weights(parsed[gi][1], ricci_curv[gi]) for gi in keep])).to(dev)
+        d_f = ricci_filtration_device(d_node_offs, d_edge_offs, d_edges, d_w, int(node_offs[-1]))
         f = d_f.cpu().numpy()
         fs = [f[node_offs[k]:node_offs[k + 1]] for k in range(len(keep))]
     elif on_device:
@@ -145,8 +211,9 @@ def compute_persistence_image_batch(graphs, filt='degree', filtrations=None, hks
 
 def compute_persistence_image(g, filt='hks', hks_time=0.1, hop=2, ricci_curv=None, mode='PI', num_models=5, max_loop_len=10,
                               cycle_the=2, hks_backend='host', struct_backend='host', hks_large='host', pd_large='host'):
-    """Reference signature (:98).  filt='hks' (the default) or 'degree' ('ricci' needs curvatures per graph: pass `filtrations`
-    to compute_persistence_image_batch); mode 'PI' -> 9-tuple, 'filtration' -> (filtration_val, edge_index).
+    """Reference signature (:98).  filt='hks' (the default), 'degree', or 'ricci' with ricci_curv (the graph's curvature in a form
+    `edge_weights` takes; `ricci_filtration_device`: data_utils_NC's build_fv with root 0 and norm=True, not the reference's GC branch,
+    which cannot run); mode 'PI' -> 9-tuple, 'filtration' -> (filtration_val, edge_index).
     hks_backend (not in the reference): 'host' or 'device', see compute_persistence_image_batch: 'device' wants each undirected edge
     once and raises RuntimeError for a tuple that repeats one; 'host' keeps scipy's multigraph semantics (repeats add up to weights).
     struct_backend (not in the reference): 'host' or 'device': filt='degree' from `tlc_struct_batch` (the same bits, the same contract).
@@ -157,14 +224,20 @@ def compute_persistence_image(g, filt='hks', hks_time=0.1, hop=2, ricci_curv=Non
     check_struct_backend(struct_backend)
     check_hks_large(hks_large)
     engine.check_pd_large(pd_large)
-    if filt not in ('degree', 'hks'):
-        raise NotImplementedError("data_utils_GC (HIP): filt='hks' and 'degree' are implemented; for 'ricci' pass the values as "
+    if filt == 'ricci' and ricci_curv is None:
+        raise _need_curvature("ricci_curv")
+    if filt not in ('degree', 'hks', 'ricci'):
+        raise NotImplementedError("data_utils_GC (HIP): filt='hks', 'degree' and 'ricci' are implemented; pass other values as "
                                   "`filtrations` to compute_persistence_image_batch")
     n, e = _edges_nodes(g)
     if len(e) == 0 or not _connected(n, e):
         return None, None
     if mode == 'filtration':
-        if filt == 'hks' and hks_backend == 'device':
+        if filt == 'ricci':
+            ptr = lambda k: torch.tensor([0, k], dtype=torch.int64, device="cuda")
+            f = ricci_filtration_device(ptr(n), ptr(len(e)), torch.from_numpy(e.astype(np.int32)).cuda(),
+                                        torch.from_numpy(edge_weights(e, ricci_curv)).cuda(), n).cpu().numpy()
+        elif filt == 'hks' and hks_backend == 'device':
             ptr = lambda k: torch.tensor([0, k], dtype=torch.int64, device="cuda")
             f = hks_filtration_device(ptr(n), ptr(len(e)), torch.from_numpy(e.astype(np.int32)).cuda(), hks_time, n,
                                       hks_large=hks_large).cpu().numpy()
@@ -175,7 +248,7 @@ def compute_persistence_image(g, filt='hks', hks_time=0.1, hop=2, ricci_curv=Non
             f = hks_filtration(n, e, hks_time) if filt == 'hks' else degree_filtration(n, e)
         return f.tolist(), torch.from_numpy(e.T.copy()).long()
     return compute_persistence_image_batch([(n, e)], filt=filt, hks_time=hks_time, hks_backend=hks_backend, struct_backend=struct_backend,
-                                           hks_large=hks_large, pd_large=pd_large)[0]
+                                           hks_large=hks_large, pd_large=pd_large, ricci_curv=None if ricci_curv is None else [ricci_curv])[0]
 
 
 def largest_component(n, edges):
@@ -255,7 +328,7 @@ def evaluate_batch(model, samples):
 
 # ---- the packed route: tensors in, tensors out, nothing per graph ---------------------------------------------------------------------
 COMPONENTS = ("largest", "whole")
-PACKED_FILTS = ("degree", "centrality", "clustering", "hks")
+PACKED_FILTS = ("degree", "centrality", "clustering", "hks", "ricci")
 
 
 def _item(data):
@@ -307,13 +380,15 @@ class PackedGroundTruth:
 
 
 def ground_truth_packed(node_ptr, edge_ptr, edges, filt='degree', hks_time=10, component='largest', filtrations=None, hks_large='host',
-                        pd_large='host'):
+                        pd_large='host', kappa=None):
     """The ground truth of a packed batch of RAW graphs (`pack_dataset`) without a loop over graphs -> `PackedGroundTruth`.
     component='largest': `call`'s semantics -- the largest connected component of every graph, renumbered (`largest_component`, here
     `engine.graph_components`), a ground truth where it has an edge.  component='whole': `compute_persistence_image_batch`'s semantics on
     the deduplicated graph -- a ground truth where the graph is connected and has an edge (the component then IS the graph).
     filt 'degree' / 'centrality' / 'clustering': `engine.struct_batch` on the extracted batch; 'hks': `data_utils_LP.hks_filtration_device`
     at hks_time (hks_large as there); `filtrations`: a packed float64 tensor over the ORIGINAL nodes instead, gathered through old_id.
+    filt='ricci' with kappa float64[sum m], one curvature per RAW packed edge (rows that repeat a pair carry the same value; the first
+    one in the input's order is read): `ricci_filtration_device` on the extracted batch with the weights kappa + 1 and the root new id 0.
     Diagrams from `engine.pd_from_filtration` (zero-persistence pairs kept; pd_large as there), the three images from `engine.pi_raster`
     with the batch function's rule for an empty Ord0 or Ext1 (:128-137).  The values are those of `compute_persistence_image_batch` with
     the device backends on the same graphs, bit for bit: the same kernels on the same packed input.
@@ -329,6 +404,8 @@ def ground_truth_packed(node_ptr, edge_ptr, edges, filt='degree', hks_time=10, c
     engine.check_pd_large(pd_large)
     if filtrations is None and filt not in PACKED_FILTS:
         raise NotImplementedError("data_utils_GC (HIP): filt is one of %s here; pass `filtrations` for anything else" % (PACKED_FILTS,))
+    if filtrations is None and filt == 'ricci' and kappa is None:
+        raise _need_curvature("kappa: a float64 tensor with one value per packed edge")
     dev, B = node_ptr.device, node_ptr.numel() - 1
     i64 = dict(dtype=torch.int64, device=dev)
     zero, ar = torch.zeros(1, **i64), torch.arange(B, **i64)
@@ -364,6 +441,16 @@ def ground_truth_packed(node_ptr, edge_ptr, edges, filt='degree', hks_time=10, c
                                  img=img, PI0=PI0, PI1=PI1)
     if filtrations is not None:
         f = filtrations.to(torch.float64)[node_ptr[sel][gn] + old_id].contiguous()
+    elif filt == 'ricci':
+        # the raw row of every extracted edge: both as keys (lo, hi) over the input's node numbers, the raw ones sorted (stable: the
+        # first of equal rows), the extracted ones looked up
+        base = node_ptr[torch.repeat_interleave(ar, edge_ptr[1:] - edge_ptr[:-1], output_size=edges.shape[0])]
+        raw = edges.to(torch.int64)
+        raw_key = (base + raw.min(1).values) * (tot_n + 1) + base + raw.max(1).values
+        raw_key, raw_row = torch.sort(raw_key, stable=True)
+        e2 = old_id[node_ptr2[ge][:, None] + edges2.to(torch.int64)] + node_ptr[sel][ge][:, None]
+        row = raw_row[torch.searchsorted(raw_key, e2.min(1).values * (tot_n + 1) + e2.max(1).values)]
+        f = ricci_filtration_device(node_ptr2, edge_ptr2, edges2, (kappa.to(torch.float64)[row] + 1.0).contiguous(), K)
     elif filt == 'hks':
         f = hks_filtration_device(node_ptr2, edge_ptr2, edges2, hks_time, K, hks_large=hks_large)
     else:

@@ -244,6 +244,37 @@ def hks_signature(times, node_ptr, edge_ptr, edges, normalise=True):
     return HksSignature.apply(times, node_ptr, edge_ptr, edges, bool(normalise))
 
 
+class DistanceFiltration(torch.autograd.Function):
+    """The distance filtration of a packed batch as a differentiable function of the edge weights: the values of
+    `engine.dist_filtration` bit for bit, the gradient of `engine.dist_filtration_vjp` (tlc_dist_filtration_vjp: along the
+    shortest-path tree of each root, through the descriptor and the division by the maximum).  w may be float32 or
+    float64: the filtration is computed in float64 and returned in w's dtype, and so is the gradient."""
+
+    @staticmethod
+    def forward(ctx, w, node_offs, edge_offs, edges, roots, descriptor, norm, include_roots, unreachable_100):
+        w64 = w.detach().to(torch.float64).contiguous()
+        f, _, parent = engine.dist_filtration(node_offs, edge_offs, edges, w64, roots, descriptor=descriptor, norm=norm,
+                                              include_roots=include_roots, unreachable_100=unreachable_100)
+        ctx.save_for_backward(w64, node_offs, edge_offs, edges, roots, parent)
+        ctx.opts, ctx.dtype = (descriptor, norm, include_roots, unreachable_100), w.dtype
+        return f.to(w.dtype)
+
+    @staticmethod
+    def backward(ctx, grad):
+        w64, node_offs, edge_offs, edges, roots, parent = ctx.saved_tensors
+        descriptor, norm, include_roots, unreachable_100 = ctx.opts
+        gw, _ = engine.dist_filtration_vjp(node_offs, edge_offs, edges, w64, roots, parent, grad.to(torch.float64).contiguous(),
+                                           descriptor=descriptor, norm=norm, include_roots=include_roots, unreachable_100=unreachable_100)
+        return gw.to(ctx.dtype), None, None, None, None, None, None, None, None
+
+
+def distance_filtration(w, node_offs, edge_offs, edges, roots, descriptor="sum", norm="max", include_roots=False, unreachable_100=False):
+    """-> [sum n]: the distance filtration of every graph of the packed batch (node_offs / edge_offs int64[B + 1], edges int32[sum m, 2]
+    local ids, each undirected edge once; roots int32[B, 2] local ids, column 1 == -1 for one root), differentiable in the edge weights
+    w [sum m] (> 0) only.  A graph that is not computed raises RuntimeError naming it and its status."""
+    return DistanceFiltration.apply(w, node_offs, edge_offs, edges, roots, descriptor, norm, bool(include_roots), bool(unreachable_100))
+
+
 def packed_points(points, slot_offs, n_points):
     """The first n_points[g] rows of every slot of `points` [sum slots, 2] (slot g starts at slot_offs[g]), packed:
     -> (pts [K, 2], offs int64[B + 1]) -- what `diagram_image` and `diagram_loss` take.  Index ops on the device, no loop over graphs;

@@ -121,6 +121,40 @@ struct TlcGraphComponentsScratch {
     }
 };
 
+// tlc_dist_filtration / tlc_dist_filtration_vjp (dist_filt.hip).  In BYTES, every array on a multiple of 256: the control words [HEAD
+// bytes] | the three classes' graph lists int[3][B] | the repeated-edge hash u64[2 M] (graph g owns the slots 2 e0 .. 2 e1) | the
+// owner graph of every edge int[M] (-1 unless its graph is of the whole-device class) | and, only when the batch can hold a graph of
+// that class (N > wg_nmax or M > wg_mmax) or for the VJP (which keeps its per-node state in d_work in every class), per node PER_NODE
+// bytes, per graph PER_GRAPH bytes.  The forward then needs at least one fallback slice u64[N]; a larger d_work holds up to
+// MAX_GROUPS of them (`groups_in`).  `least` is what the entry requires and the *_work_bytes call returns.
+struct TlcDistFiltScratch {
+    static constexpr int64_t HEAD = 2048, MAX_GROUPS = 256;
+    // forward: R u64[2] | q f64 | cnt u32[2] | nxt u32[2] | the fallback list int | the owner graph int  (9 arrays)
+    // VJP:     T f64[2] | S f64[2] | depth, tree edge, child count, row start, children int[2] each        (14 arrays)
+    // per graph: the largest distance u64 | the divisor u64 | the status int                               (3 arrays)
+    static constexpr int64_t FWD_PER_NODE = 8 * 2 + 8 + 4 * 2 + 4 * 2 + 4 + 4, VJP_PER_NODE = 8 * 2 + 8 * 2 + 4 * 2 * 5, PER_GRAPH = 8 * 2 + 4;
+    static constexpr int64_t NODE_ARRAYS = 16, GRAPH_ARRAYS = 3;      // room for each array's rounding up to 256 bytes
+    static int64_t up256(int64_t v) { return (v + 255) & ~(int64_t)255; }
+    bool wide;
+    int64_t head = 0, lists, hash, egraph, node, graph, slices, slice_bytes, least;
+    TlcDistFiltScratch(int64_t B, int64_t N, int64_t M, int64_t wg_nmax, int64_t wg_mmax, bool vjp)
+        : wide(vjp || N > wg_nmax || M > wg_mmax) {
+        int64_t o = HEAD;
+        lists = o; o += up256(3 * B * 4);
+        hash = o; o += up256(2 * M * 8);
+        egraph = o; o += up256(M * 4);
+        node = o; o += wide ? up256(N * (vjp ? VJP_PER_NODE : FWD_PER_NODE)) + 256 * NODE_ARRAYS : 0;
+        graph = o; o += wide ? up256(B * PER_GRAPH) + 256 * GRAPH_ARRAYS : 0;
+        slices = o;
+        slice_bytes = (wide && !vjp) ? up256(N * 8) : 0;
+        least = o + slice_bytes;
+    }
+    int64_t groups_in(int64_t work_bytes) const {
+        if (!slice_bytes) return 0;
+        return std::min<int64_t>(MAX_GROUPS, (work_bytes - slices) / slice_bytes);
+    }
+};
+
 // tlc_pi_image: the partial images [slices][res_b * res_p] of the diagrams above SLICE points, one per slice of SLICE points (the second
 // pass adds a pixel's slices ascending).  In float64 elements.  `least` holds the slices of the largest diagram, `total` those of
 // MAX_GROUP such diagrams (the most one launch takes); diagrams of up to SLICE points need none.

@@ -1107,3 +1107,110 @@ def ollivier_ricci_otd(rowptr, col, edges, alpha=0.5, device=None, want_cost=Fal
     if strict and np.isnan(out).any():
         raise _lib.TlcError("tlc_ollivier_ricci_otd: an edge exceeded the workspace or the solver's bound (edge %d)" % int(np.flatnonzero(np.isnan(out))[0]))
     return (out, w, d) if want_cost else out
+
+
+DIST_NORMS = {"max": 0, "max_eps": _lib.NORM_EPS, "none": _lib.NO_NORM}
+DIST_STATUS_NAMES = {_lib.ST_DISCONNECTED: "ST_DISCONNECTED (a node root 0 does not reach, without unreachable_100)",
+                     _lib.ST_ZERO_RANGE: "ST_ZERO_RANGE (all values 0 under norm='max')",
+                     _lib.ST_BAD_INPUT: "ST_BAD_INPUT (offsets, an id or a root out of range, a loop, a repeated edge, a weight not finite and > 0)"}
+
+
+def dist_filtration_flags(descriptor="sum", norm="max", include_roots=False, unreachable_100=False):
+    """The flag word of tlc_dist_filtration for a descriptor of DESCRIPTOR_FLAG and a norm of DIST_NORMS."""
+    if descriptor not in _lib.DESCRIPTOR_FLAG or norm not in DIST_NORMS:
+        raise ValueError("dist_filtration: descriptor one of %s and norm one of %s, not %r / %r"
+                         % (tuple(_lib.DESCRIPTOR_FLAG), tuple(DIST_NORMS), descriptor, norm))
+    return (_lib.DESCRIPTOR_FLAG[descriptor] | DIST_NORMS[norm] | (_lib.INCLUDE_ROOTS if include_roots else 0)
+            | (_lib.UNREACHABLE_100 if unreachable_100 else 0))
+
+
+def dist_filtration_work_bytes(n_graphs, total_nodes, total_edges, vjp=False):
+    """Least bytes of workspace of tlc_dist_filtration (vjp=True: of tlc_dist_filtration_vjp) for a batch of these totals: host
+    arithmetic, no device."""
+    need = C.c_int64(0)
+    fn = _lib.lib().tlc_dist_filtration_vjp_work_bytes if vjp else _lib.lib().tlc_dist_filtration_work_bytes
+    _lib.check(fn(C.c_int64(int(n_graphs)), C.c_int64(int(total_nodes)), C.c_int64(int(total_edges)), C.byref(need)),
+               "tlc_dist_filtration_work_bytes")
+    return need.value
+
+
+def _dist_raise(what, status):
+    bad = status.nonzero().flatten().tolist()
+    if bad:
+        codes = status[bad].tolist()
+        raise RuntimeError("%s: graph(s) %s are not computed: status %s (%s)"
+                           % (what, bad[:16], codes[:16], "; ".join("%d = %s" % (c, DIST_STATUS_NAMES.get(c, "?")) for c in sorted(set(codes)))))
+
+
+def _dist_work(work, need, dev, torch):
+    """A 256-byte aligned view of at least `need` bytes: of the caller's uint8 tensor, or of a fresh one."""
+    if work is None:
+        work = torch.empty(need + 256, dtype=torch.uint8, device=dev)
+    off = (-work.data_ptr()) % 256
+    return work[off:]
+
+
+@_lib.on_device_of
+def dist_filtration(node_offs, edge_offs, edges, w, roots, descriptor="sum", norm="max", include_roots=False, unreachable_100=False,
+                    work=None, total_nodes=None, check=True):
+    """The distance filtration of a packed batch on the device (tlc_dist_filtration; `filtration.build_fv` /
+    `ricci_filtration.build_fv` of the reference bit for bit): per node the weighted shortest-path distance to the root(s) of its graph.
+
+    node_offs / edge_offs int64[B + 1], edges int32[sum m, 2] local ids (each undirected edge once), w float64[sum m] > 0, roots
+    int32[B, 2] local ids (column 1 == -1: one root): CUDA tensors.  descriptor 'sum' / 'min' / 'max' over the two distances; norm 'max'
+    (/ the maximum), 'max_eps' (/ (the maximum + 1e-10)) or 'none'; unreachable_100: an unreachable root costs 100 instead of
+    ST_DISCONNECTED; include_roots: TLC_INCLUDE_ROOTS, accepted for flag parity with the vicinity pipeline, no effect on a packed graph.
+    work: a uint8 CUDA tensor of at least `dist_filtration_work_bytes` (+ 255 for alignment) bytes, or None.
+    Returns (f float64[sum n], status uint8[B], parent int32[2, sum n]: the tree of include/tlcgnn.h).  check=True raises RuntimeError
+    naming the graphs whose status is not ST_OK (their slice of f holds NaN); check=False returns the status for the caller to read."""
+    torch = _lib.require_gpu()
+    dev = node_offs.device
+    flags = dist_filtration_flags(descriptor, norm, include_roots, unreachable_100)
+    B = node_offs.numel() - 1
+    tot_m = int(edges.shape[0])
+    tot_n = int(total_nodes) if total_nodes is not None else (int(node_offs[-1]) if B > 0 else 0)
+    f = torch.full((tot_n,), float("nan"), dtype=torch.float64, device=dev)
+    parent = torch.full((2, tot_n), -1, dtype=torch.int32, device=dev)
+    status = torch.zeros(max(B, 1), dtype=torch.uint8, device=dev)[:B]
+    if B > 0:
+        need = dist_filtration_work_bytes(B, tot_n, tot_m)
+        if work is None and (tot_n > _lib.DIST_WG_NMAX or tot_m > _lib.DIST_WG_MMAX):
+            # room for more fallback searches of the whole-device class in flight: up to 255 further slices of 8 B per node, 256 MiB at the most
+            need += min(255 * (((8 * tot_n + 255) // 256) * 256), 1 << 28)
+        wk = _dist_work(work, need, dev, torch)
+        rc = _lib.lib().tlc_dist_filtration(C.c_int64(B), _lib.ptr(node_offs.contiguous()), _lib.ptr(edge_offs.contiguous()),
+                                            _lib.ptr(edges.contiguous()), _lib.ptr(w.contiguous()), _lib.ptr(roots.contiguous()),
+                                            C.c_int64(tot_n), C.c_int64(tot_m), C.c_uint32(flags), _lib.ptr(f), _lib.ptr(status),
+                                            _lib.ptr(parent), _lib.ptr(wk), C.c_int64(wk.numel()), _lib.stream_ptr())
+        _lib.check(rc, "tlc_dist_filtration")
+        if check:
+            _dist_raise("dist_filtration", status)
+    return f, status, parent
+
+
+@_lib.on_device_of
+def dist_filtration_vjp(node_offs, edge_offs, edges, w, roots, parent, grad_f, descriptor="sum", norm="max", include_roots=False,
+                        unreachable_100=False, work=None, total_nodes=None, check=True):
+    """d (sum grad_f . f) / d w of `dist_filtration` (tlc_dist_filtration_vjp: the specification in include/tlcgnn.h): the same inputs
+    and options, `parent` of that forward, grad_f float64[sum n] -> (grad_w float64[sum m], status uint8[B]); zeros for an edge off both
+    trees.  Under ties among path lengths the tree is a convention, not a derivative."""
+    torch = _lib.require_gpu()
+    dev = node_offs.device
+    flags = dist_filtration_flags(descriptor, norm, include_roots, unreachable_100)
+    B = node_offs.numel() - 1
+    tot_m = int(edges.shape[0])
+    tot_n = int(total_nodes) if total_nodes is not None else (int(node_offs[-1]) if B > 0 else 0)
+    gw = torch.full((tot_m,), float("nan"), dtype=torch.float64, device=dev)
+    status = torch.zeros(max(B, 1), dtype=torch.uint8, device=dev)[:B]
+    if B > 0:
+        need = dist_filtration_work_bytes(B, tot_n, tot_m, vjp=True)
+        wk = _dist_work(work, need, dev, torch)
+        rc = _lib.lib().tlc_dist_filtration_vjp(C.c_int64(B), _lib.ptr(node_offs.contiguous()), _lib.ptr(edge_offs.contiguous()),
+                                                _lib.ptr(edges.contiguous()), _lib.ptr(w.contiguous()), _lib.ptr(roots.contiguous()),
+                                                C.c_int64(tot_n), C.c_int64(tot_m), C.c_uint32(flags), None, _lib.ptr(parent.contiguous()),
+                                                _lib.ptr(grad_f.contiguous()), _lib.ptr(gw), _lib.ptr(status), _lib.ptr(wk),
+                                                C.c_int64(wk.numel()), _lib.stream_ptr())
+        _lib.check(rc, "tlc_dist_filtration_vjp")
+        if check:
+            _dist_raise("dist_filtration_vjp", status)
+    return gw, status

@@ -35,6 +35,21 @@ def hks_filtration(time, node_offs, edge_offs, edges, normalise=True):
     return autograd.hks_signature(time.reshape(1), node_offs, edge_offs, edges, normalise=normalise)[0]
 
 
+def distance_filtration(w, node_offs, edge_offs, edges, roots=None, descriptor="sum", norm="max", include_roots=False, unreachable_100=False):
+    """-> [sum n]: the distance filtration of every graph -- per node the weighted shortest-path distance to the root(s) of its graph,
+    the filtration of `filtration.build_fv` / `ricci_filtration.build_fv` bit for bit -- as a differentiable function of the edge
+    weights w [sum m] (kappa + 1 of every packed edge, > 0; `autograd.distance_filtration`, tlc_dist_filtration and its VJP).  roots:
+    int32[B, 2] local ids (column 1 == -1: one root), None: node 0 of every graph.  descriptor 'sum' / 'min' / 'max' over two roots; norm
+    'max', 'max_eps' or 'none'.  It goes straight into `diagrams` / `images` / `wasserstein_to` / `sliced_wasserstein_to` as f, and their
+    gradient reaches w along the shortest-path trees.  Under ties among path lengths the tree is a fixed convention (include/tlcgnn.h)."""
+    if roots is None:
+        B = node_offs.numel() - 1
+        roots = torch.stack([torch.zeros(B, dtype=torch.int32, device=node_offs.device),
+                             torch.full((B,), -1, dtype=torch.int32, device=node_offs.device)], 1).contiguous()
+    return autograd.distance_filtration(w, node_offs, edge_offs, edges, roots, descriptor=descriptor, norm=norm,
+                                        include_roots=include_roots, unreachable_100=unreachable_100)
+
+
 def diagrams(f, node_offs, edge_offs, edges, pd_large="host"):
     """-> dict(ord0, ord0_offs, rel1, rel1_offs, ext1, ext1_offs, ext0, counts): the three diagrams of every graph packed
     ([K, 2] points with int64[B + 1] offsets: the input `autograd.diagram_image` and `autograd.diagram_loss` take) and ext0 [B, 2]
