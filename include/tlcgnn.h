@@ -1078,6 +1078,67 @@ int tlc_dist_filtration_vjp(int64_t n_graphs, const int64_t* d_node_ptr, const i
                             const double* d_f, const int32_t* d_parent, const double* d_grad_f, double* d_grad_w,
                             uint8_t* d_status, void* d_work, int64_t work_bytes, void* stream);
 
+/* ---- Vicinity images differentiable in the GRAPH's edge weights (csrc/vic_grad.hip): what lies between the kappa of the
+ * graph's edges and the packed weights of tlc_dist_filtration, and between the decoder's loss and the image table.  Every call is
+ * asynchronous on `stream`, reads nothing back and uses no floating-point atomics.
+ *
+ * tlc_packed_edge_lookup: d_graph_edges int32[n_graph_edges, 2], every undirected edge once with lo < hi, ascending by (lo, hi) (what
+ * np.unique or tlc_graph_components produces).  The packed vicinity batch of Vicinities.batch / tlc_pack_vicinities / tlc_vicinity_filtration
+ * with exact offsets: d_node_ptr / d_edge_ptr int64[n_vicinities + 1], d_ids the global ids, ascending inside a vicinity, int64[total_nodes]
+ * (ids_int64 = 1) or int32 (0), d_edges int32[total_edges, 2] local ids.  d_pairs int32[n_vicinities, 2] global ids, or NULL (d_roots NULL too).
+ * Out: d_eid int32[total_edges] = the index in d_graph_edges of the packed edge (either order of its ends), by binary search;
+ * d_roots int32[n_vicinities, 2] = the local ids of the pair's ends in the vicinity's slice of d_ids, by binary search; one_root = 1:
+ * only the first end is looked up and d_roots[:, 1] = -1, as tlc_dist_filtration reads one root.  d_status uint8[n_vicinities]: TLC_ST_OK, or
+ * TLC_ST_BAD_INPUT -- a packed edge that is not in the list or has a local id outside its vicinity, or a looked-up end that is not in
+ * the vicinity: every d_eid of that vicinity is -1 and its d_roots row is (-1, -1) -- or offsets that are negative, decrease or pass the
+ * totals (d_roots (-1, -1), no d_eid written).  No other vicinity is affected.  n_vicinities == 0: TLC_OK, nothing read.
+ * TLC_ERR_INVALID_ARG, nothing launched: a negative size, 2^31 edges, a flag other than 0 / 1, a null required pointer, d_pairs without
+ * d_roots or the reverse. */
+int tlc_packed_edge_lookup(int64_t n_graph_edges, const int32_t* d_graph_edges, int64_t n_vicinities, const int64_t* d_node_ptr,
+                           const int64_t* d_edge_ptr, const void* d_ids, int32_t ids_int64, const int32_t* d_edges, int64_t total_nodes,
+                           int64_t total_edges, const int32_t* d_pairs, int32_t one_root, int32_t* d_eid, int32_t* d_roots,
+                           uint8_t* d_status, void* stream);
+
+/* tlc_segment_index (one-off per pair list): d_key int32[n_items], the key of every item; a key outside 0 .. n_keys-1 (negative: the -1
+ * of a refused vicinity) is skipped.  Out: d_seg_ptr int64[n_keys + 1], d_seg_pos int32[n_items]: the items of key k are
+ * d_seg_pos[d_seg_ptr[k] .. d_seg_ptr[k + 1]), ascending; behind d_seg_ptr[n_keys] lie the skipped items, ascending.  A stable radix
+ * sort of (key, position) (two 8-bit digits while n_keys < 2^16, else four) and one binary search per key: integers only, the same
+ * output on every run.  d_work: 256-byte aligned, tlc_segment_index_work_bytes() bytes (12 B per item and the sort's histograms).
+ * TLC_ERR_INVALID_ARG, nothing launched: a size outside 0 .. 2^31 - 1, a null required pointer, a d_work too small or misaligned.
+ *
+ * tlc_segment_sum_f64 (per step): d_out[k] = the sum of v_j = d_val[d_seg_pos[d_seg_ptr[k] + j]], j = 0 .. L-1, L the segment's length;
+ * d_val float64[n_items].  THE ORDER, operation by operation (fp64, round to nearest, no fused multiply-add); it depends on L alone:
+ *   L <= TLC_SEG_LANE_MAX (one lane):        s = +0.0; for j = 0 .. L-1: s = s + v_j.  d_out[k] = s  (L = 0: +0.0).
+ *   L <= TLC_SEG_WAVE_MAX (one wavefront):   for l = 0 .. 63: p[l] = +0.0; for j = l, l + 64, l + 128, ... < L: p[l] = p[l] + v_j.
+ *                                            FOLD: for d = 32, 16, 8, 4, 2, 1: for every l < d at once: p[l] = p[l] + p[l + d].
+ *                                            d_out[k] = p[0].
+ *   longer (one workgroup of 256 threads):   for t = 0 .. 255: p[t] = +0.0; for j = t, t + 256, ... < L: p[t] = p[t] + v_j.
+ *                                            For w = 0 .. 3: q[w] = FOLD of p[64 w .. 64 w + 63].  d_out[k] = ((q[0] + q[1]) + q[2]) + q[3].
+ * Every sum starts from +0.0, so no output is -0.0.  The classes are cut on the device: a first kernel (a thread per segment) sums
+ * the first class and lists the segments of the other two in d_work -- in the order of arrival, which decides who sums a segment and
+ * never how.  Neither the batch, nor the grid, nor d_work, nor the run changes a bit.  A d_seg_pos entry outside 0 .. n_items-1 counts as
+ * +0.0 and a segment whose offsets decrease or leave 0 .. n_items as empty: a damaged index reads nothing out of bounds.
+ * d_work: 256-byte aligned, tlc_segment_sum_work_bytes() bytes (8 B per key + 256).  n_keys == 0: TLC_OK.  Refusals as above. */
+#define TLC_SEG_LANE_MAX  16     /* longest segment that one lane sums */
+#define TLC_SEG_WAVE_MAX  2048   /* longest segment that one wavefront sums; longer ones take a workgroup */
+int tlc_segment_index_work_bytes(int64_t n_items, int64_t n_keys, int64_t* bytes);
+int tlc_segment_index(int64_t n_items, const int32_t* d_key, int64_t n_keys, int64_t* d_seg_ptr, int32_t* d_seg_pos, void* d_work,
+                      int64_t work_bytes, void* stream);
+int tlc_segment_sum_work_bytes(int64_t n_keys, int64_t* bytes);
+int tlc_segment_sum_f64(int64_t n_keys, const int64_t* d_seg_ptr, const int32_t* d_seg_pos, int64_t n_items, const double* d_val,
+                        double* d_out, void* d_work, int64_t work_bytes, void* stream);
+
+/* d loss / d PI of tlc_lp_decode_fused_f32: the inputs of tlc_lp_decode_bwd_f32 up to d_gprob (d_emb_pre is not read: the renorm lies in
+ * front of the embedding) -> d_gpi float32[n_pairs, 25].  With gz[k], k = 0 .. 24, the gradient at the hidden layer's pre-activation
+ * that tlc_lp_decode_bwd_f32 forms (the Fermi-Dirac derivative -gprob p^2 exp(z), the clamp: 0 beyond 40, the sign of the abs, times
+ * W2[k], times 1 or 0.2 by the sign of h[k]), in f32: d_gpi[i][j] = acc after acc = +0.0; for k = 0 .. 24: acc = acc + W1[k][16 + j] * gz[k]
+ * (the product rounded, then the sum: no fused multiply-add).  A pair with an end outside 0 .. n_nodes-1 gets zeros.  emb_dim 16 / pi_dim
+ * 25, else TLC_ERR_UNSUPPORTED; null pointers and negative sizes: TLC_ERR_INVALID_ARG; n_pairs == 0: TLC_OK.  One thread per pair, no
+ * scratch, bit-identical from run to run. */
+int tlc_lp_decode_bwd_pi_f32(int64_t n_pairs, const int32_t* d_pairs, const float* d_emb_pre, const float* d_emb, int32_t n_nodes,
+                             int32_t emb_dim, const float* d_pi, int32_t pi_dim, const float* d_W1, const float* d_b1, const float* d_W2,
+                             const float* d_b2, const float* d_gprob, float* d_gpi, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

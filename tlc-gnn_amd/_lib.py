@@ -38,6 +38,7 @@ SW_WAVE_NMAX, SW_LDS_NMAX, SW_MAX_DIRS = 64, 2048, 128              # TLC_SW_*: 
 PI_MAX_RES, PI_GRAD_WEIGHT, PI_GRAD_FULL = 128, 0, 1                # TLC_PI_*: the general imager of csrc/pi_general.hip
 PI_SLICE, PI_CHUNK, PI_GROUP = 1024, 32, 32                         # points per K-slice / per LDS chunk, K-split diagrams per launch
 DIST_WAVE_NMAX, DIST_WG_NMAX, DIST_WG_MMAX, DIST_WORK_FALLBACKS_OFF = 64, 2048, 4096, 64   # TLC_DIST_*: the size classes of csrc/dist_filt.hip
+SEG_LANE_MAX, SEG_WAVE_MAX, SEG_WG_THREADS = 16, 2048, 256           # TLC_SEG_*: the size classes of csrc/vic_grad.hip by segment length
 DESCRIPTOR_FLAG ={"sum": 0, "min": DESC_MIN, "max": DESC_MAX}      # the three node values of filtration.build_fv
 
 # every symbol include/tlcgnn.h declares (tests check that the library exports all of them)
@@ -58,6 +59,8 @@ SYMBOLS = [
     "tlc_pi_image_work_bytes", "tlc_pi_image", "tlc_pi_image_vjp",
     "tlc_graph_components_work_bytes", "tlc_graph_components",
     "tlc_dist_filtration_work_bytes", "tlc_dist_filtration_vjp_work_bytes", "tlc_dist_filtration", "tlc_dist_filtration_vjp",
+    "tlc_packed_edge_lookup", "tlc_segment_index_work_bytes", "tlc_segment_index", "tlc_segment_sum_work_bytes", "tlc_segment_sum_f64",
+    "tlc_lp_decode_bwd_pi_f32",
     "tlc_gcn2_encode_work_floats", "tlc_gemm_tn_work_floats", "tlc_lp_decode_bwd_work_floats", "tlc_nc_linear_bwd_work_floats",
     "tlc_gat_layer_fwd_work_floats", "tlc_gat_layer_tiled_fwd_work_floats", "tlc_gat_tile_cut_work_ints", "tlc_gat_tile_cut_max_tiles",
     "tlc_csr_by_target_work_ints", "tlc_gat_layer_bwd_work_floats", "tlc_edge_head_fwd_work_floats", "tlc_edge_head_bwd_work_floats",
@@ -206,6 +209,14 @@ def lib():
         L.tlc_dist_filtration_vjp_work_bytes.argtypes = L.tlc_dist_filtration_work_bytes.argtypes
         L.tlc_dist_filtration.argtypes = [C.c_int64] + [C.c_void_p] * 5 + [C.c_int64, C.c_int64, C.c_uint32] + [C.c_void_p] * 4 + [C.c_int64, C.c_void_p]
         L.tlc_dist_filtration_vjp.argtypes = [C.c_int64] + [C.c_void_p] * 5 + [C.c_int64, C.c_int64, C.c_uint32] + [C.c_void_p] * 6 + [C.c_int64, C.c_void_p]
+        L.tlc_packed_edge_lookup.argtypes = ([C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64,
+                                              C.c_int64, C.c_void_p, C.c_int32] + [C.c_void_p] * 4)
+        L.tlc_segment_index_work_bytes.argtypes = [C.c_int64, C.c_int64, C.POINTER(C.c_int64)]
+        L.tlc_segment_index.argtypes = [C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+        L.tlc_segment_sum_work_bytes.argtypes = [C.c_int64, C.POINTER(C.c_int64)]
+        L.tlc_segment_sum_f64.argtypes = [C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+        L.tlc_lp_decode_bwd_pi_f32.argtypes = ([C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32]
+                                               + [C.c_void_p] * 7)
         L.tlc_ollivier_ricci_otd_work_bytes.argtypes = [C.c_int64, C.c_int32, C.c_int64, C.POINTER(C.c_int64)]
         L.tlc_ollivier_ricci_otd.argtypes = ([C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 4
                                              + [C.c_int64, C.c_int32, C.c_int64, C.c_void_p])

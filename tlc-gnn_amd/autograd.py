@@ -5,7 +5,7 @@ classifier of Knowledge_Distillation/ConvCurv_GIN.py: CurvConv and NcLinear (nc_
 
 torch.autograd only carries the graph: every forward and every backward below is one C-ABI call (`tlc_gat_layer_fwd/_bwd`,
 `tlc_edge_head_fwd/_bwd`, `tlc_w2_partial_matching`, `tlc_sliced_wasserstein`, `tlc_pi_raster` / `tlc_pi_raster_wgrad`, `tlc_pi_image` / `tlc_pi_image_vjp`, `tlc_hks_batch_dt` + `tlc_hks_large_batch_dt`) or a few (`tlc_gemm_f32` /
-`tlc_spmm_csr_f32` / `tlc_gemm_tn_f32`, `tlc_lp_decode_fused_f32` / `tlc_lp_decode_bwd_f32`); nothing is recomputed with torch ops
+`tlc_spmm_csr_f32` / `tlc_gemm_tn_f32`, `tlc_lp_decode_fused_f32` / `tlc_lp_decode_bwd_f32` / `tlc_lp_decode_bwd_pi_f32`, `tlc_segment_sum_f64`); nothing is recomputed with torch ops
 and there is no CPU path.
 """
 import torch
@@ -275,6 +275,33 @@ def distance_filtration(w, node_offs, edge_offs, edges, roots, descriptor="sum",
     return DistanceFiltration.apply(w, node_offs, edge_offs, edges, roots, descriptor, norm, bool(include_roots), bool(unreachable_100))
 
 
+class GatherEdgeValues(torch.autograd.Function):
+    """w[eid]: the value of its graph edge for every packed vicinity edge (0 where eid < 0: an edge of a refused vicinity).  Backward:
+    every graph edge gets the sum of the gradients of its copies, by `engine.segment_sum` (tlc_segment_sum_f64) over the segment index
+    of eid -- fp64, in an order that depends on the number of copies alone, no atomics (torch's index_add_ has neither property)."""
+
+    @staticmethod
+    def forward(ctx, w, eid, seg_ptr, seg_pos):
+        ctx.save_for_backward(seg_ptr, seg_pos)
+        ctx.dtype = w.dtype
+        idx = eid.to(torch.int64)
+        return torch.where(idx >= 0, w.detach()[idx.clamp(min=0)], torch.zeros((), dtype=w.dtype, device=w.device))
+
+    @staticmethod
+    def backward(ctx, grad):
+        seg_ptr, seg_pos = ctx.saved_tensors
+        g = engine.segment_sum(grad.to(torch.float64).contiguous(), seg_ptr, seg_pos)
+        return g.to(ctx.dtype), None, None, None
+
+
+def gather_edge_values(w, eid, seg_ptr, seg_pos):
+    """-> w[eid] [len(eid)], differentiable in w [M]: eid int32 from `engine.packed_edge_lookup`, (seg_ptr, seg_pos) =
+    `engine.segment_index(eid, M)`, built once per pair list."""
+    if seg_ptr.numel() != w.numel() + 1 or seg_pos.numel() != eid.numel():
+        raise ValueError("gather_edge_values: the segment index is not the one of these %d values and %d positions" % (w.numel(), eid.numel()))
+    return GatherEdgeValues.apply(w, eid, seg_ptr, seg_pos)
+
+
 def packed_points(points, slot_offs, n_points):
     """The first n_points[g] rows of every slot of `points` [sum slots, 2] (slot g starts at slot_offs[g]), packed:
     -> (pts [K, 2], offs int64[B + 1]) -- what `diagram_image` and `diagram_loss` take.  Index ops on the device, no loop over graphs;
@@ -386,7 +413,8 @@ class GcnLayer(torch.autograd.Function):
 class LpDecode(torch.autograd.Function):
     """Net.decode after the pair selection (TLCGNN.py:48-61) on the PRE-renorm embedding: emb.renorm_(2, 0, 1) (on a copy: the
     caller's tensor is left alone, autograd saw it) and the fused decode -- the same two calls as Net.decode, so the same
-    probabilities.  Backward: tlc_lp_decode_bwd_f32 -> d emb (through the renorm), dW1, db1, dW, db."""
+    probabilities.  Backward: tlc_lp_decode_bwd_f32 -> d emb (through the renorm), dW1, db1, dW, db; and, only when pi requires grad,
+    tlc_lp_decode_bwd_pi_f32 -> d pi."""
 
     @staticmethod
     def forward(ctx, emb, pairs, pi, w1, b1, w2, b2):
@@ -402,7 +430,11 @@ class LpDecode(torch.autograd.Function):
         pi32 = pi if pi.dtype == torch.float32 else pi.to(torch.float32)   # (the forward's cast on load: same rounding)
         gemb, gw1, gb1, gw2, gb2 = ops.lp_decode_bwd(pairs, pre, post, pi32, w1.detach(), b1.detach(), w2.detach(), b2.detach(),
                                                      gprob.contiguous())
-        return gemb, None, None, gw1, gb1, gw2, gb2
+        if not ctx.needs_input_grad[2]:
+            return gemb, None, None, gw1, gb1, gw2, gb2
+        # a learned image table (topo.VicinityImages): d loss / d PI from tlc_lp_decode_bwd_pi_f32, in pi's dtype
+        gpi = engine.lp_decode_bwd_pi(pairs, pre, post, pi32, w1.detach(), b1.detach(), w2.detach(), b2.detach(), gprob.contiguous())
+        return gemb, None, gpi.to(pi.dtype), gw1, gb1, gw2, gb2
 
 
 def gcn_layer(x, weight, bias, op, op_t, relu=False):

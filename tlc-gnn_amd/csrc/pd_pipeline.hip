@@ -1311,8 +1311,10 @@ __device__ __forceinline__ int pd_all_stages(Mem<idx_t>& M, Sink& sink, int n, i
     if (TLC_STOP_AFTER <= 6) return TLC_STOPPED;
     // A connected vicinity with n - 1 edges is a tree (30 % of a PubMed batch): every edge is a Neg edge, there is no Pos
     // edge and no 1-dimensional point, and the descending pass would only add Rel1 points, which weigh 0 in the image.
-    // (The batch path is entered for connected vicinities only; tlc_pd_from_filtration reports Rel1 and takes the long way.)
-    if (!Sink::is_global && m == n - 1) return TLC_ST_OK;
+    // (Without TLC_UNREACHABLE_100 the batch path is entered for connected vicinities only; with it a vicinity of two or more nodes
+    // and n - 1 edges may be a component with cycles beside isolated nodes, whose Pos edges the long way finds.
+    // tlc_pd_from_filtration reports Rel1 and takes the long way.)
+    if (!Sink::is_global && m == n - 1 && (n == 1 || !(flags & TLC_UNREACHABLE_100))) return TLC_ST_OK;
     // Many Pos edges (m - n + 1 of them in a connected graph): the cycle swap runs as a divide and conquer (ext1_dc.h), which
     // needs the ascending pass's spanning tree per edge id -- kept in M.rec, the serial walk's record area -- and the descending
     // order with its ties fixed

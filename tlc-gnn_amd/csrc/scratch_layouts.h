@@ -155,6 +155,27 @@ struct TlcDistFiltScratch {
     }
 };
 
+// tlc_segment_index (vic_grad.hip).  In BYTES, every array on a multiple of 256: the sort keys u32[n_items], twice for the radix sort's
+// ping-pong | the second buffer of the positions u32[n_items] (the first is d_seg_pos itself) | the radix sort's hist and tot (ints: the
+// caller passes rk_hist_ints(n_items) and RK_TOT_INTS of radix_passes.h, which is device code and stays out of this header).
+struct TlcSegmentIndexScratch {
+    static int64_t up256(int64_t v) { return (v + 255) & ~(int64_t)255; }
+    int64_t key_a = 0, key_b, pos_b, hist, tot, total;
+    TlcSegmentIndexScratch(int64_t n_items, int64_t hist_ints, int64_t tot_ints)
+        : key_b(up256(n_items * 4)), pos_b(key_b + up256(n_items * 4)), hist(pos_b + up256(n_items * 4)), tot(hist + up256(hist_ints * 4)),
+          total(tot + up256(tot_ints * 4)) {}
+};
+
+// tlc_segment_sum_f64 (vic_grad.hip).  In BYTES: the control words [HEAD bytes]: the lengths of the two lists, int each | the segments
+// of the wavefront class int[n_keys] | those of the workgroup class int[n_keys].  The lists' order is the order of arrival and decides
+// which wavefront sums a segment, never the order of a sum.
+struct TlcSegmentSumScratch {
+    static constexpr int64_t HEAD = 256;
+    static int64_t up256(int64_t v) { return (v + 255) & ~(int64_t)255; }
+    int64_t head = 0, wave_list = HEAD, wg_list, total;
+    explicit TlcSegmentSumScratch(int64_t n_keys) : wg_list(wave_list + up256(n_keys * 4)), total(wg_list + up256(n_keys * 4)) {}
+};
+
 // tlc_pi_image: the partial images [slices][res_b * res_p] of the diagrams above SLICE points, one per slice of SLICE points (the second
 // pass adds a pixel's slices ascending).  In float64 elements.  `least` holds the slices of the largest diagram, `total` those of
 // MAX_GROUP such diagrams (the most one launch takes); diagrams of up to SLICE points need none.

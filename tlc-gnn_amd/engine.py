@@ -1214,3 +1214,90 @@ def dist_filtration_vjp(node_offs, edge_offs, edges, w, roots, parent, grad_f, d
         if check:
             _dist_raise("dist_filtration_vjp", status)
     return gw, status
+
+
+# ---- vicinity images differentiable in the graph's edge weights (csrc/vic_grad.hip; topo.VicinityImages) -------------------------------
+@_lib.on_device_of
+def packed_edge_lookup(graph_edges, node_ptr, edge_ptr, ids, edges, pairs=None, one_root=False):
+    """Which edge of the graph is every packed vicinity edge, and where are a pair's ends in their vicinity (tlc_packed_edge_lookup).
+    graph_edges int32[M, 2]: lo < hi, ascending by (lo, hi); the packed batch of `Vicinities.batch` / `pack_vicinities` /
+    `vicinity_filtration(offsets=...)`: node_ptr / edge_ptr int64[B + 1], ids int64 or int32 [sum n] global ids, edges int32[sum m, 2]
+    local ids; pairs int32[B, 2] global ids or None.  -> (eid int32[sum m], roots int32[B, 2] or None, status uint8[B]); one_root:
+    roots[:, 1] = -1.  A vicinity with an edge outside the list or a missing end: ST_BAD_INPUT, its eid and roots -1."""
+    torch = _lib.require_gpu()
+    dev = node_ptr.device
+    B = node_ptr.numel() - 1
+    assert graph_edges.dtype == torch.int32 and edges.dtype == torch.int32 and ids.dtype in (torch.int32, torch.int64)
+    assert pairs is None or (pairs.dtype == torch.int32 and tuple(pairs.shape) == (B, 2))
+    tot_n, tot_m = int(ids.numel()), int(edges.shape[0])
+    eid = torch.full((max(tot_m, 1),), -1, dtype=torch.int32, device=dev)
+    roots = torch.full((max(B, 1), 2), -1, dtype=torch.int32, device=dev) if pairs is not None else None
+    status = torch.zeros(max(B, 1), dtype=torch.uint8, device=dev)
+    rc = _lib.lib().tlc_packed_edge_lookup(C.c_int64(int(graph_edges.shape[0])), _lib.ptr(graph_edges.contiguous()), C.c_int64(B),
+                                           _lib.ptr(node_ptr.contiguous()), _lib.ptr(edge_ptr.contiguous()), _lib.ptr(ids.contiguous()),
+                                           C.c_int32(int(ids.dtype == torch.int64)), _lib.ptr(edges.contiguous()), C.c_int64(tot_n),
+                                           C.c_int64(tot_m), _lib.ptr(pairs.contiguous()) if pairs is not None else None,
+                                           C.c_int32(int(bool(one_root))), _lib.ptr(eid), _lib.ptr(roots), _lib.ptr(status), _lib.stream_ptr())
+    _lib.check(rc, "tlc_packed_edge_lookup")
+    return eid[:tot_m], (roots[:B] if roots is not None else None), status[:B]
+
+
+def segment_index_work_bytes(n_items, n_keys):
+    need = C.c_int64(0)
+    _lib.check(_lib.lib().tlc_segment_index_work_bytes(C.c_int64(int(n_items)), C.c_int64(int(n_keys)), C.byref(need)),
+               "tlc_segment_index_work_bytes")
+    return need.value
+
+
+def segment_sum_work_bytes(n_keys):
+    need = C.c_int64(0)
+    _lib.check(_lib.lib().tlc_segment_sum_work_bytes(C.c_int64(int(n_keys)), C.byref(need)), "tlc_segment_sum_work_bytes")
+    return need.value
+
+
+@_lib.on_device_of
+def segment_index(key, n_keys, work=None):
+    """The items of every key (tlc_segment_index, one-off): key int32[n_items], keys outside 0 .. n_keys-1 skipped -> (seg_ptr
+    int64[n_keys + 1], seg_pos int32[n_items]): key k's items are seg_pos[seg_ptr[k]:seg_ptr[k + 1]], ascending."""
+    torch = _lib.require_gpu()
+    assert key.dtype == torch.int32 and key.dim() == 1
+    dev, n = key.device, int(key.numel())
+    seg_ptr = torch.empty(int(n_keys) + 1, dtype=torch.int64, device=dev)
+    seg_pos = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+    wk = _dist_work(work, segment_index_work_bytes(n, n_keys), dev, torch)
+    rc = _lib.lib().tlc_segment_index(C.c_int64(n), _lib.ptr(key.contiguous()), C.c_int64(int(n_keys)), _lib.ptr(seg_ptr), _lib.ptr(seg_pos),
+                                      _lib.ptr(wk), C.c_int64(wk.numel()), _lib.stream_ptr())
+    _lib.check(rc, "tlc_segment_index")
+    return seg_ptr, seg_pos[:n]
+
+
+@_lib.on_device_of
+def segment_sum(val, seg_ptr, seg_pos, work=None, out=None):
+    """out[k] = the sum of val[seg_pos[j]] over key k's segment (tlc_segment_sum_f64): float64, in the order include/tlcgnn.h states,
+    which depends on the segment's length alone -- the deterministic adjoint of the gather val = w[key]."""
+    torch = _lib.require_gpu()
+    assert val.dtype == torch.float64 and val.numel() == seg_pos.numel()
+    dev, M = val.device, seg_ptr.numel() - 1
+    if out is None:
+        out = torch.empty(max(M, 1), dtype=torch.float64, device=dev)[:M]
+    wk = _dist_work(work, segment_sum_work_bytes(M), dev, torch)
+    rc = _lib.lib().tlc_segment_sum_f64(C.c_int64(M), _lib.ptr(seg_ptr.contiguous()), _lib.ptr(seg_pos.contiguous()), C.c_int64(int(val.numel())),
+                                        _lib.ptr(val.contiguous()), _lib.ptr(out), _lib.ptr(wk), C.c_int64(wk.numel()), _lib.stream_ptr())
+    _lib.check(rc, "tlc_segment_sum_f64")
+    return out
+
+
+@_lib.on_device_of
+def lp_decode_bwd_pi(pairs, emb_pre, emb, pi, w1, b1, w2, b2, gprob):
+    """d loss / d PI of `ops.lp_decode` (tlc_lp_decode_bwd_pi_f32): the arguments of `ops.lp_decode_bwd` -> float32[E, 25]."""
+    torch = _lib.require_gpu()
+    assert pairs.dtype == torch.int32 and pi.dtype == torch.float32
+    E, n = pairs.shape[0], emb_pre.shape[0]
+    pre, post, w1, b1, w2, b2, gprob = (t.detach().to(torch.float32).contiguous() for t in (emb_pre, emb, w1, b1, w2.reshape(-1), b2, gprob))
+    pairs, pi = pairs.contiguous(), pi.contiguous()
+    gpi = torch.empty((E, pi.shape[1]), dtype=torch.float32, device=post.device)
+    rc = _lib.lib().tlc_lp_decode_bwd_pi_f32(C.c_int64(E), _lib.ptr(pairs), _lib.ptr(pre), _lib.ptr(post), C.c_int32(n), C.c_int32(pre.shape[1]),
+                                             _lib.ptr(pi), C.c_int32(pi.shape[1]), _lib.ptr(w1), _lib.ptr(b1), _lib.ptr(w2), _lib.ptr(b2),
+                                             _lib.ptr(gprob), _lib.ptr(gpi), _lib.stream_ptr())
+    _lib.check(rc, "tlc_lp_decode_bwd_pi_f32")
+    return gpi

@@ -54,6 +54,37 @@ def train(model, data, optimizer):
     return x
 
 
+def train_curvature(model, data, optimizer, images):
+    """The step of train() with a LEARNED image table: the image rows of the step's pairs come from `images()` -- a
+    `topo.VicinityImages` over the training part of data.total_edges (its first train_pos + train_neg rows, or the whole list) --
+    instead of model.PI, so loss.backward() also reaches `images.kappa`, the graph's curvature.  `optimizer` holds
+    the model's parameters and images.kappa (one optimizer or a parameter group).  The negatives are drawn as Net.decode draws them
+    (np.random.randint over the same fixed pair list); the stored table model.PI takes no part in the step.  Returns the predictions x."""
+    from . import autograd as ag
+    model.train()
+    optimizer.zero_grad()
+    emb = model._encode_train(data)
+    dev = emb.device
+    _, pairs_all = model._tables(data, dev)
+    if not isinstance(pairs_all, torch.Tensor):
+        raise TypeError("train_curvature: a streamed pair list (pi_cache.LazyPairList) is not taken: the images need the fixed list")
+    tp, tn = data.train_pos, data.train_neg
+    n_img = images.structure.n_pairs
+    if n_img < tp + tn or not torch.equal(images.structure.pairs[:tp + tn], pairs_all[:tp + tn]):
+        raise ValueError("train_curvature: images should be built over data.total_edges[:train_pos + train_neg] (or the whole list)")
+    index = np.random.randint(0, tn, tp)                               # same RNG call as TLCGNN.py:31
+    idx = torch.cat((torch.arange(tp, device=dev), tp + torch.from_numpy(index).to(dev)))
+    y = data.total_edges_y[idx.to(data.total_edges_y.device)].float()
+    table, _ = images()
+    # (table[idx]: its backward is index_put_(accumulate=True), which sorts -- repeated negatives add up in a fixed order)
+    pi = table[idx].to(torch.float32)
+    x = ag.lp_decode(emb, pairs_all[idx].contiguous(), pi, model.linear_1.weight, model.linear_1.bias, model.linear.weight, model.linear.bias)
+    loss = F.binary_cross_entropy(x, y.to(x.device))
+    loss.backward()
+    optimizer.step()
+    return x
+
+
 def fit(model, data, optimizer, total_epochs=2000, wait_total=200, metrics="sklearn"):
     """The epoch loop of :111-126: train, then test; the test numbers of the best validation ROC-AUC (>=) are kept, and the loop
     stops after `wait_total` epochs without a better one -> (test_acc, test_roc, best_val_acc, best_val_roc, best_val_loss)
