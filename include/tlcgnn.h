@@ -572,6 +572,58 @@ int tlc_hks_large_batch_dt(const int64_t* d_node_ptr, const int64_t* d_edge_ptr,
                            const double* h_times, int32_t n_times, uint32_t flags, double* d_out, double* d_dout, uint8_t* d_status,
                            void* d_work, int64_t work_bytes, void* stream);
 
+/* ---- Heat-kernel signatures of sparse graphs of any size ---------------------------------------------------------------------------------
+ * The same values for SELECTED graphs of the packed batch of tlc_hks_batch, without eigenpairs and without a dense matrix: with
+ * M = D^-1/2 A D^-1/2, L = I - M and tau = t / 2, a node v of degree > 0 has
+ *   y_v = exp(-tau L) e_v = exp(-tau) sum_{k = 0 .. K} z_k,   z_0 = e_v,   z_k = (tau / k) M z_{k-1},
+ *   hks_t(v) = sum_u y_v[u]^2,        d/dt hks_t(v) = -(sum_u y_v[u]^2 - y_v^T M y_v);
+ * a node of degree 0 has value 1 and derivative 0.  M has no negative entry, so no term cancels.  The work is n K 2m multiply-adds per
+ * graph and time.  The contract of tlc_hks_large_batch holds (selection, 1 .. TLC_HKS_TMAX times, TLC_HKS_NORMALISE with the maximum at
+ * its lowest index, the quotient rule of tlc_hks_batch_dt, a status byte per selected graph, slices of graphs that are not TLC_ST_OK
+ * untouched, row k of d_out / d_dout bit-equal to a call with h_times[k] alone), with h_sel_edges (HOST) int64[n_sel], the selected
+ * graphs' edge counts, beside h_sel_nodes: the workspace is laid out from both, nothing is read back, no host wait.  A declared count
+ * (nodes or edges) that is not the device's, offsets out of order, an id out of range, a self loop, an unordered pair listed twice in
+ * either orientation, or more than n (n - 1) / 2 edges: TLC_ST_BAD_INPUT.  There is no node cap and no TLC_ST_TOO_LARGE; ids are 32-bit:
+ * the selected graphs together have fewer than 2^31 - 1 nodes and fewer than 2^30 edges.
+ * K = tlc_hks_sparse_terms(t): the least k >= 0 with k + 2 > tau and
+ *   (tau^(k+1) / (k+1)!) / (1 - tau / (k + 2)) / E * (1 + 2^-40) <= 2^-64,     E = sum_{j = 0 .. 400} tau^j / j!  (j ascending),
+ * a bound on the Poisson(tau) tail beyond k, in IEEE double +, *, / only (term_j = term_{j-1} * tau / j; no libm call): the same K on
+ * every host.  K = 0 at t = 0; 9, 16, 36, 96 at t = 0.1, 1, 10, 64; -1 for a time outside [0, TLC_HKS_SPARSE_TIME_MAX] or not finite.
+ * The operation sequence (fp64, no fused multiply-add, no floating-point atomics; it fixes the bits):
+ *   CSR.  Every edge (a, b) gives the entries (a, b) and (b, a); the entries of the selection are sorted by (row, column) with the
+ *     shared radix driver, so a row's neighbours ascend and a repeat shows as two adjacent equal entries.  deg(u) is the integer length
+ *     of row u, r_u = 1.0 / sqrt((double)deg(u)) (0.0 for degree 0).
+ *   Row sum R_u(x) of a vector x: the neighbours of u in chunks of TLC_HKS_SPARSE_PANEL (64) consecutive ones; a chunk's partial sum
+ *     starts at +0.0 and adds x[w], w ascending; R_u is +0.0 plus the partial sums, chunks ascending.  Rows above
+ *     TLC_HKS_SPARSE_LONG_ROW neighbours are split over wavefronts along these same cuts (the partial sums go through d_work), so a
+ *     hub neither serialises a launch nor changes a bit.
+ *   Column v (one lane; TLC_HKS_SPARSE_PANEL consecutive columns make a panel):  S = e_v, s = r_v e_v; for k = 1 .. K, with
+ *     c_k = tau / k (host):  z[u] = (c_k * r_u) * R_u(s);  S[u] = S[u] + z[u];  s[u] = r_u * z[u]  (all u, then the next k).
+ *     y[u] = exp(-tau) * S[u] (the host's exp), q[u] = r_u * y[u], and for the derivative g[u] = q[u] * R_u(q).
+ *   Sums over u (value: y[u] * y[u]; quadratic form: g[u]): blocks of 64 consecutive rows, a block's partial sum from +0.0 with u
+ *     ascending, then +0.0 plus the partial sums, blocks ascending.  hks = that sum, d hks / dt = quadratic form - value.
+ * One launch per Taylor step (and one for the split rows' partial sums, where a graph of the group can have such a row: min(n - 1, m)
+ * above TLC_HKS_SPARSE_LONG_ROW) serves every panel of a group, and with them every graph of the
+ * group.  d_work: 16-byte aligned; *min_bytes holds the CSR of the selection and the vectors of one panel of the largest graph,
+ * *all_bytes those of every panel of every graph; any work_bytes in between runs the panels in groups that fit -- the same bits.
+ * tlc_hks_sparse_work_bytes is host arithmetic (no device needed); both are 0 for an empty selection.
+ * TLC_ERR_INVALID_ARG (nothing launched): what tlc_hks_large_batch refuses (with TLC_HKS_SPARSE_TIME_MAX), a negative edge count, or a
+ * selection beyond the 32-bit limits above.  Runs on the caller's current device, asynchronous on `stream`. */
+#define TLC_HKS_SPARSE_TIME_MAX  64.0   /* times outside [0, 64] or not finite: TLC_ERR_INVALID_ARG, nothing launched */
+#define TLC_HKS_SPARSE_PANEL     64     /* columns of a panel (lane = column); neighbours of a chunk; rows of a block of the sums over u */
+#define TLC_HKS_SPARSE_LONG_ROW  256    /* rows with more neighbours are split over wavefronts, chunk by chunk */
+int32_t tlc_hks_sparse_terms(double t);
+int tlc_hks_sparse_work_bytes(const int64_t* h_sel_nodes, const int64_t* h_sel_edges, int64_t n_sel, int32_t n_times, int64_t* min_bytes,
+                              int64_t* all_bytes);
+int tlc_hks_sparse_batch(const int64_t* d_node_ptr, const int64_t* d_edge_ptr, const int32_t* d_edges, int64_t n_graphs,
+                         int64_t total_nodes, int64_t total_edges, const int64_t* h_sel, const int64_t* h_sel_nodes,
+                         const int64_t* h_sel_edges, int64_t n_sel, const double* h_times, int32_t n_times, uint32_t flags, double* d_out,
+                         uint8_t* d_status, void* d_work, int64_t work_bytes, void* stream);
+int tlc_hks_sparse_batch_dt(const int64_t* d_node_ptr, const int64_t* d_edge_ptr, const int32_t* d_edges, int64_t n_graphs,
+                            int64_t total_nodes, int64_t total_edges, const int64_t* h_sel, const int64_t* h_sel_nodes,
+                            const int64_t* h_sel_edges, int64_t n_sel, const double* h_times, int32_t n_times, uint32_t flags,
+                            double* d_out, double* d_dout, uint8_t* d_status, void* d_work, int64_t work_bytes, void* stream);
+
 /* ---- Degree / centrality / clustering filtrations (Knowledge_Distillation/data_utils_LP.py:131-133; data_utils_NC.py:124-135: networkx's
  * degree(), degree_centrality and clustering of the vicinity, then / (max + 1e-10)) ------------------------------------------------------
  * For the packed batch of tlc_hks_batch (simple undirected graphs, each edge ONCE, local ids), per node v of a graph of n nodes with

@@ -112,7 +112,7 @@ def _need_curvature(what):
 
 
 def compute_persistence_image_batch(graphs, filt='degree', filtrations=None, hks_time=0.1, hks_backend='host', struct_backend='host',
-                                    hks_large='host', pd_large='host', ricci_curv=None):
+                                    hks_large='host', hks_sparse='host', pd_large='host', ricci_curv=None):
     """graphs: list of networkx-like graphs with nodes 0..n-1, or (n, edges[m,2]) tuples.
     Returns a list with the reference's 9-tuple per graph (:166), or (None, None) for graphs without an edge / not
     connected (:101-103).  filt: 'degree' or 'hks' (host side, :114-119); `filtrations` supplies f per graph for anything else.
@@ -133,11 +133,12 @@ def compute_persistence_image_batch(graphs, filt='degree', filtrations=None, hks
     node cap) instead of one workgroup of `tlc_pd_from_filtration`, which does not compute a graph above 65 535 nodes at all
     (`engine.pd_from_filtration`); the same diagrams as multisets, images within the summation order."""
     import torch
-    from .data_utils_LP import (STRUCT_DEVICE_FILTS, check_hks_backend, check_hks_large, check_struct_backend, hks_filtration_device,
+    from .data_utils_LP import (STRUCT_DEVICE_FILTS, check_hks_backend, check_hks_large, check_hks_sparse, check_struct_backend, hks_filtration_device,
                                 struct_filtration_device)
     check_hks_backend(hks_backend)
     check_struct_backend(struct_backend)
     check_hks_large(hks_large)
+    check_hks_sparse(hks_sparse)
     engine.check_pd_large(pd_large)
     on_device = filtrations is None and filt in STRUCT_DEVICE_FILTS and struct_backend == 'device'
     ricci = filtrations is None and filt == 'ricci'
@@ -161,7 +162,7 @@ def compute_persistence_image_batch(graphs, filt='degree', filtrations=None, hks
     dev = "cuda"
     d_node_offs, d_edge_offs, d_edges = torch.from_numpy(node_offs).to(dev), torch.from_numpy(edge_offs).to(dev), torch.from_numpy(edges).to(dev)
     if filtrations is None and filt == 'hks' and hks_backend == 'device':
-        d_f = hks_filtration_device(d_node_offs, d_edge_offs, d_edges, hks_time, int(node_offs[-1]), hks_large=hks_large)
+        d_f = hks_filtration_device(d_node_offs, d_edge_offs, d_edges, hks_time, int(node_offs[-1]), hks_large=hks_large, hks_sparse=hks_sparse)
         f = d_f.cpu().numpy()
         fs = [f[node_offs[k]:node_offs[k + 1]] for k in range(len(keep))]
     elif ricci:
@@ -210,7 +211,7 @@ def compute_persistence_image_batch(graphs, filt='degree', filtrations=None, hks
 
 
 def compute_persistence_image(g, filt='hks', hks_time=0.1, hop=2, ricci_curv=None, mode='PI', num_models=5, max_loop_len=10,
-                              cycle_the=2, hks_backend='host', struct_backend='host', hks_large='host', pd_large='host'):
+                              cycle_the=2, hks_backend='host', struct_backend='host', hks_large='host', hks_sparse='host', pd_large='host'):
     """Reference signature (:98).  filt='hks' (the default), 'degree', or 'ricci' with ricci_curv (the graph's curvature in a form
     `edge_weights` takes; `ricci_filtration_device`: data_utils_NC's build_fv with root 0 and norm=True, not the reference's GC branch,
     which cannot run); mode 'PI' -> 9-tuple, 'filtration' -> (filtration_val, edge_index).
@@ -219,10 +220,11 @@ def compute_persistence_image(g, filt='hks', hks_time=0.1, hop=2, ricci_curv=Non
     struct_backend (not in the reference): 'host' or 'device': filt='degree' from `tlc_struct_batch` (the same bits, the same contract).
     hks_large, pd_large (not in the reference): 'host' or 'device', see compute_persistence_image_batch."""
     import torch
-    from .data_utils_LP import check_hks_backend, check_hks_large, check_struct_backend, hks_filtration_device, struct_filtration_device
+    from .data_utils_LP import check_hks_backend, check_hks_large, check_hks_sparse, check_struct_backend, hks_filtration_device, struct_filtration_device
     check_hks_backend(hks_backend)
     check_struct_backend(struct_backend)
     check_hks_large(hks_large)
+    check_hks_sparse(hks_sparse)
     engine.check_pd_large(pd_large)
     if filt == 'ricci' and ricci_curv is None:
         raise _need_curvature("ricci_curv")
@@ -240,7 +242,7 @@ def compute_persistence_image(g, filt='hks', hks_time=0.1, hop=2, ricci_curv=Non
         elif filt == 'hks' and hks_backend == 'device':
             ptr = lambda k: torch.tensor([0, k], dtype=torch.int64, device="cuda")
             f = hks_filtration_device(ptr(n), ptr(len(e)), torch.from_numpy(e.astype(np.int32)).cuda(), hks_time, n,
-                                      hks_large=hks_large).cpu().numpy()
+                                      hks_large=hks_large, hks_sparse=hks_sparse).cpu().numpy()
         elif filt == 'degree' and struct_backend == 'device':
             ptr = lambda k: torch.tensor([0, k], dtype=torch.int64, device="cuda")
             f = struct_filtration_device(filt, ptr(n), ptr(len(e)), torch.from_numpy(e.astype(np.int32)).cuda(), n).cpu().numpy()
@@ -248,7 +250,7 @@ def compute_persistence_image(g, filt='hks', hks_time=0.1, hop=2, ricci_curv=Non
             f = hks_filtration(n, e, hks_time) if filt == 'hks' else degree_filtration(n, e)
         return f.tolist(), torch.from_numpy(e.T.copy()).long()
     return compute_persistence_image_batch([(n, e)], filt=filt, hks_time=hks_time, hks_backend=hks_backend, struct_backend=struct_backend,
-                                           hks_large=hks_large, pd_large=pd_large, ricci_curv=None if ricci_curv is None else [ricci_curv])[0]
+                                           hks_large=hks_large, hks_sparse=hks_sparse, pd_large=pd_large, ricci_curv=None if ricci_curv is None else [ricci_curv])[0]
 
 
 def largest_component(n, edges):
@@ -267,7 +269,7 @@ def largest_component(n, edges):
 
 
 def call(dataset, name, filt='degree', hks_time=10, mode='PI', num_models=5, gn=0, save_dir=None, store=None, hks_backend='host',
-         struct_backend='host', hks_large='host', pd_large='host'):
+         struct_backend='host', hks_large='host', hks_sparse='host', pd_large='host'):
     """Reference signature (:228) plus keywords.  For the first `gn` graphs of `dataset` (PyG-like items with num_nodes and edge_index
     [2, m], or (n, edges[m, 2]) tuples): the largest connected component, relabelled (:246-248), through `compute_persistence_image`.
     Returns (total_time_PD, total_time_PI) like the reference (the times are 0 here).  The per-graph results go into the dict `store`
@@ -276,6 +278,8 @@ def call(dataset, name, filt='degree', hks_time=10, mode='PI', num_models=5, gn=
     SBM graphs (:324-325): with pd_large='device' such a component's diagrams come from `tlc_pd_wide`, not from one workgroup."""
     import os
     import pickle
+    from .data_utils_LP import check_hks_sparse
+    check_hks_sparse(hks_sparse)
     engine.check_pd_large(pd_large)
     dict_store = {} if store is None else store
     total_time_PD = total_time_PI = 0
@@ -289,7 +293,7 @@ def call(dataset, name, filt='degree', hks_time=10, mode='PI', num_models=5, gn=
         print("nodes: {}, edges: {}".format(k, len(ce)))
         dict_store[tt] = compute_persistence_image((k, ce), filt=filt, hks_time=hks_time, hop=2, ricci_curv=None, mode=mode,
                                                    num_models=num_models, hks_backend=hks_backend, struct_backend=struct_backend,
-                                                   hks_large=hks_large, pd_large=pd_large)
+                                                   hks_large=hks_large, hks_sparse=hks_sparse, pd_large=pd_large)
         if len(dict_store[tt]) > 2:
             total_time_PD += dict_store[tt][-2]
             total_time_PI += dict_store[tt][-1]
@@ -379,7 +383,7 @@ class PackedGroundTruth:
         return out
 
 
-def ground_truth_packed(node_ptr, edge_ptr, edges, filt='degree', hks_time=10, component='largest', filtrations=None, hks_large='host',
+def ground_truth_packed(node_ptr, edge_ptr, edges, filt='degree', hks_time=10, component='largest', filtrations=None, hks_large='host', hks_sparse='host',
                         pd_large='host', kappa=None):
     """The ground truth of a packed batch of RAW graphs (`pack_dataset`) without a loop over graphs -> `PackedGroundTruth`.
     component='largest': `call`'s semantics -- the largest connected component of every graph, renumbered (`largest_component`, here
@@ -397,10 +401,11 @@ def ground_truth_packed(node_ptr, edge_ptr, edges, filt='degree', hks_time=10, c
     refuses (offsets out of order, an id outside 0 .. n-1) raises RuntimeError naming the first one."""
     import torch
     from ..autograd import pack_rows
-    from .data_utils_LP import STRUCT_DEVICE_FILTS, check_hks_large, hks_filtration_device
+    from .data_utils_LP import STRUCT_DEVICE_FILTS, check_hks_large, check_hks_sparse, hks_filtration_device
     if component not in COMPONENTS:
         raise ValueError("component should be one of %s, not %r" % (COMPONENTS, component))
     check_hks_large(hks_large)
+    check_hks_sparse(hks_sparse)
     engine.check_pd_large(pd_large)
     if filtrations is None and filt not in PACKED_FILTS:
         raise NotImplementedError("data_utils_GC (HIP): filt is one of %s here; pass `filtrations` for anything else" % (PACKED_FILTS,))
@@ -452,7 +457,7 @@ def ground_truth_packed(node_ptr, edge_ptr, edges, filt='degree', hks_time=10, c
         row = raw_row[torch.searchsorted(raw_key, e2.min(1).values * (tot_n + 1) + e2.max(1).values)]
         f = ricci_filtration_device(node_ptr2, edge_ptr2, edges2, (kappa.to(torch.float64)[row] + 1.0).contiguous(), K)
     elif filt == 'hks':
-        f = hks_filtration_device(node_ptr2, edge_ptr2, edges2, hks_time, K, hks_large=hks_large)
+        f = hks_filtration_device(node_ptr2, edge_ptr2, edges2, hks_time, K, hks_large=hks_large, hks_sparse=hks_sparse)
     else:
         # the extracted batch is simple and in range by construction: the status byte is not read back (a refused graph would be NaN)
         f = engine.struct_batch(node_ptr2, edge_ptr2, edges2, filt, normalise=True, total_nodes=K)[0][0]
@@ -475,16 +480,17 @@ def ground_truth_packed(node_ptr, edge_ptr, edges, filt='degree', hks_time=10, c
                              img=img, PI0=PI0, PI1=PI1)
 
 
-def call_packed(dataset, name, filt='degree', hks_time=10, gn=0, save_dir=None, store=None, hks_large='host', pd_large='host'):
+def call_packed(dataset, name, filt='degree', hks_time=10, gn=0, save_dir=None, store=None, hks_large='host', hks_sparse='host', pd_large='host'):
     """`call` through the packed route: the first `gn` graphs of `dataset` in one `pack_dataset` and one `ground_truth_packed`
     (component='largest').  Leaves in `store`, and in <save_dir>/<name>_<filt>_total_test.pkl, what `call` leaves with the device
     backends; returns (0, 0) like it, and prints nothing per graph."""
     import os
     import pickle
-    from .data_utils_LP import check_hks_large
+    from .data_utils_LP import check_hks_large, check_hks_sparse
     check_hks_large(hks_large)
+    check_hks_sparse(hks_sparse)
     engine.check_pd_large(pd_large)
-    gt = ground_truth_packed(*pack_dataset(dataset, gn), filt=filt, hks_time=hks_time, component='largest', hks_large=hks_large, pd_large=pd_large)
+    gt = ground_truth_packed(*pack_dataset(dataset, gn), filt=filt, hks_time=hks_time, component='largest', hks_large=hks_large, hks_sparse=hks_sparse, pd_large=pd_large)
     dict_store = {} if store is None else store
     dict_store.update(enumerate(gt.tuples()))
     if save_dir is not None:

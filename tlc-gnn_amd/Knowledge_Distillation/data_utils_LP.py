@@ -33,6 +33,12 @@ hks_host_fallback = 0
 HKS_LARGE = ("host", "device")
 # graphs of the most recent hks_backend='device' computation that the large tier (hks_large='device') computed
 hks_large_device = 0
+# hks_sparse: who computes what is still TLC_ST_TOO_LARGE after the large tier (more than _lib.HKS_LARGE_NMAX nodes, or hks_large='host')
+# -- 'host' (`hks_signature`, the default) or 'device' (`engine.hks_sparse_batch`: no node cap, hks_time inside
+# [0, _lib.HKS_SPARSE_TIME_MAX]; values to rounding)
+HKS_SPARSE = ("host", "device")
+# graphs of the most recent hks_backend='device' computation that the sparse tier (hks_sparse='device') computed
+hks_sparse_device = 0
 
 
 def check_hks_backend(hks_backend):
@@ -43,6 +49,11 @@ def check_hks_backend(hks_backend):
 def check_hks_large(hks_large):
     if hks_large not in HKS_LARGE:
         raise ValueError("hks_large should be one of %s, not %r" % (HKS_LARGE, hks_large))
+
+
+def check_hks_sparse(hks_sparse):
+    if hks_sparse not in HKS_SPARSE:
+        raise ValueError("hks_sparse should be one of %s, not %r" % (HKS_SPARSE, hks_sparse))
 
 
 def check_struct_backend(struct_backend):
@@ -114,7 +125,7 @@ def structural_filtration(kind, node_ptr, edge_ptr, edges, hks_time=0.1):
     return raw / (mx[owner] + 1e-10) if N else raw
 
 
-def hks_filtration_device(node_ptr, edge_ptr, edges, hks_time, total_nodes, hks_large='host'):
+def hks_filtration_device(node_ptr, edge_ptr, edges, hks_time, total_nodes, hks_large='host', hks_sparse='host'):
     """The 'hks' case of `structural_filtration` on the device: `engine.hks_batch` (tlc_hks_batch) on the CUDA tensors of a packed batch
     -> CUDA float64[sum n], normalised per graph.  Offsets and edges stay on the device.  Graphs the kernel does not take (status
     TLC_ST_TOO_LARGE: more than _lib.HKS_NMAX nodes; TLC_ST_NOT_CONVERGED) are computed by `hks_signature` on the host and scattered
@@ -124,15 +135,20 @@ def hks_filtration_device(node_ptr, edge_ptr, edges, hks_time, total_nodes, hks_
     read-back; their number is left in the module's `hks_large_device` -- and only what is still not TLC_ST_OK afterwards takes the host.
     The device takes SIMPLE graphs, each undirected edge listed once: TLC_ST_BAD_INPUT (offsets out of order, an id outside 0 .. n-1, a
     self loop, an unordered pair listed twice -- in the same or in both directions) raises RuntimeError; nothing is returned for such a
-    batch.  The host route differs there: scipy sums repeated entries into a weighted multigraph."""
-    global hks_host_fallback, hks_large_device
+    batch.  The host route differs there: scipy sums repeated entries into a weighted multigraph.
+    hks_sparse='device' (and 0 <= hks_time <= _lib.HKS_SPARSE_TIME_MAX): what is still TLC_ST_TOO_LARGE after that -- any node count --
+    goes through `engine.hks_sparse_batch` (tlc_hks_sparse_batch), with the edge offsets read back as well; the number of graphs it
+    computed is left in the module's `hks_sparse_device`.  The default 'host' changes nothing."""
+    global hks_host_fallback, hks_large_device, hks_sparse_device
     import torch
     check_hks_large(hks_large)
+    check_hks_sparse(hks_sparse)
     f2, st = engine.hks_batch(node_ptr, edge_ptr, edges, [hks_time], normalise=True, total_nodes=total_nodes)
     f = f2[0]
     rest = torch.nonzero(st != _lib.ST_OK).reshape(-1).cpu().numpy()
     hks_host_fallback = len(rest)
     hks_large_device = 0
+    hks_sparse_device = 0
     if len(rest):
         bad = ("hks_backend='device': a graph has offsets out of order, an edge id out of range, a self loop or a repeated "
                "edge (the device wants each undirected edge once; hks_backend='host' sums repeated edges into weights)")
@@ -151,6 +167,20 @@ def hks_filtration_device(node_ptr, edge_ptr, edges, hks_time, total_nodes, hks_
                     raise RuntimeError(bad)
                 hks_large_device = int((st_l == _lib.ST_OK).sum())
                 rest = np.concatenate([rest[~take], rest[take][st_l != _lib.ST_OK]])
+                rest.sort()
+                hks_host_fallback = len(rest)
+        if hks_sparse == 'device' and 0.0 <= float(hks_time) <= _lib.HKS_SPARSE_TIME_MAX and len(rest):
+            take = st.cpu().numpy()[rest] == _lib.ST_TOO_LARGE
+            if take.any():
+                eptr = edge_ptr.cpu().numpy()
+                sel = rest[take]
+                engine.hks_sparse_batch(node_ptr, edge_ptr, edges, sel.tolist(), (nptr[sel + 1] - nptr[sel]).tolist(),
+                                        (eptr[sel + 1] - eptr[sel]).tolist(), [hks_time], normalise=True, total_nodes=total_nodes, out=f2, status=st)
+                st_s = st.cpu().numpy()[sel]
+                if (st_s == _lib.ST_BAD_INPUT).any():
+                    raise RuntimeError(bad)
+                hks_sparse_device = int((st_s == _lib.ST_OK).sum())
+                rest = np.concatenate([rest[~take], sel[st_s != _lib.ST_OK]])
                 rest.sort()
                 hks_host_fallback = len(rest)
     if len(rest):
@@ -195,7 +225,7 @@ class Vicinities:
             self.inv[new] = old
 
     def batch(self, pairs, hop, node_cap=None, edge_cap=None, flags=None, filt='ricci', hks_time=0.1, hks_backend='host', struct_backend='host',
-              hks_large='host'):
+              hks_large='host', hks_sparse='host'):
         """pairs: [E,2] original labels -> dict of CUDA tensors: node_ptr int64[E+1], edge_ptr int64[E+1], ids int64 (original
         labels, ascending inside a vicinity), f float64, edges int32 [sum m, 2] (local ids, lower first), status uint8[E].
         Vicinities without an edge have empty slices (the reference returns (None, None) for them, :117-118).
@@ -213,6 +243,7 @@ class Vicinities:
         check_hks_backend(hks_backend)
         check_struct_backend(struct_backend)
         check_hks_large(hks_large)
+        check_hks_sparse(hks_sparse)
         dev_graph = self._g2p._device_graph()
         mapped = torch.from_numpy(self._g2p._map_pairs(pairs)).cuda()
         fl = KD_LP_FLAGS if flags is None else flags
@@ -242,9 +273,9 @@ class Vicinities:
             pe = torch.repeat_interleave(owner, counts_m, output_size=int(tot_m))
             out_ids, out_f, out_e = self._inv_dev[ids[:int(tot_n)].long()], f[:int(tot_n)], edges[:int(tot_m)]
             if filt == 'hks' and hks_backend == 'device':
-                out_f = hks_filtration_device(node_ptr, edge_ptr, out_e, hks_time, int(tot_n), hks_large=hks_large)
+                out_f = hks_filtration_device(node_ptr, edge_ptr, out_e, hks_time, int(tot_n), hks_large=hks_large, hks_sparse=hks_sparse)
                 return dict(node_ptr=node_ptr, edge_ptr=edge_ptr, ids=out_ids, f=out_f, edges=out_e, status=st, pair_of_node=pn, pair_of_edge=pe,
-                            hks_host_fallback=hks_host_fallback, hks_large_device=hks_large_device)
+                            hks_host_fallback=hks_host_fallback, hks_large_device=hks_large_device, hks_sparse_device=hks_sparse_device)
             if filt in STRUCT_DEVICE_FILTS and struct_backend == 'device':
                 out_f = struct_filtration_device(filt, node_ptr, edge_ptr, out_e, int(tot_n))
             elif filt != 'ricci':
@@ -264,9 +295,9 @@ class Vicinities:
         out_ids, out_f, out_e, pn, pe = engine.pack_vicinities(offs, ids, f, eoffs, edges, node_ptr, edge_ptr, int(tot_n), int(tot_m),
                                                                label=self._inv_dev)
         if filt == 'hks' and hks_backend == 'device':
-            out_f = hks_filtration_device(node_ptr, edge_ptr, out_e, hks_time, int(tot_n), hks_large=hks_large)
+            out_f = hks_filtration_device(node_ptr, edge_ptr, out_e, hks_time, int(tot_n), hks_large=hks_large, hks_sparse=hks_sparse)
             return dict(node_ptr=node_ptr, edge_ptr=edge_ptr, ids=out_ids, f=out_f, edges=out_e, status=st, pair_of_node=pn, pair_of_edge=pe,
-                        hks_host_fallback=hks_host_fallback, hks_large_device=hks_large_device)
+                        hks_host_fallback=hks_host_fallback, hks_large_device=hks_large_device, hks_sparse_device=hks_sparse_device)
         if filt in STRUCT_DEVICE_FILTS and struct_backend == 'device':
             out_f = struct_filtration_device(filt, node_ptr, edge_ptr, out_e, int(tot_n))
         elif filt != 'ricci':
@@ -298,7 +329,7 @@ def _vicinities(g, ricci_curv):
 
 
 def compute_persistence_image(g, u, v, filt='hks', hks_time=0.1, hop=2, ricci_curv=None, mode='PI', num_models=5,
-                              max_loop_len=10, cycle_the=2, hks_backend='host', struct_backend='host', hks_large='host', pd_large='host'):
+                              max_loop_len=10, cycle_the=2, hks_backend='host', struct_backend='host', hks_large='host', hks_sparse='host', pd_large='host'):
     """Reference signature (:105).  filt='hks' (:128-130), 'degree' (:131-133) or 'ricci'; mode 'filtration' -> (filtration_val
     list, edge_index LongTensor[2,m]) or (None, None); mode 'PI' -> the reference's 9-tuple (times are 0).
     hks_backend, struct_backend, hks_large (not in the reference): 'host' or 'device', see `Vicinities.batch`.
@@ -307,12 +338,13 @@ def compute_persistence_image(g, u, v, filt='hks', hks_time=0.1, hop=2, ricci_cu
     check_hks_backend(hks_backend)
     check_struct_backend(struct_backend)
     check_hks_large(hks_large)
+    check_hks_sparse(hks_sparse)
     engine.check_pd_large(pd_large)
     if filt not in ('ricci', 'degree', 'hks'):
         print("Error: 'filt' should be 'hks', 'degree' or 'ricci'! ")          # :152-153
         sys.exit()
     b = _vicinities(g, ricci_curv).batch([[u, v]], hop, filt=filt, hks_time=hks_time, hks_backend=hks_backend, struct_backend=struct_backend,
-                                         hks_large=hks_large)
+                                         hks_large=hks_large, hks_sparse=hks_sparse)
     if int(b["edge_ptr"][-1]) == 0:
         return None, None
     fv = b["f"].cpu().numpy()

@@ -29,17 +29,18 @@ class NodeVicinities(Vicinities):
     """Device-resident weighted graph for PDGNN's node-centred vicinities; build once, query many nodes."""
 
     def batch(self, nodes, hop, node_cap=None, edge_cap=None, filt='ricci', hks_time=0.1, hks_backend='host', struct_backend='host',
-              hks_large='host'):
+              hks_large='host', hks_sparse='host'):
         """nodes: [B] original labels -> the dict of Vicinities.batch (one vicinity per node).  filt: 'ricci', or 'degree' /
         'centrality' / 'clustering' / 'hks' (:120-135; `data_utils_LP.structural_filtration`); hks_backend, struct_backend and hks_large as in
         `Vicinities.batch`."""
-        from .data_utils_LP import check_hks_backend, check_hks_large, check_struct_backend
+        from .data_utils_LP import check_hks_backend, check_hks_large, check_hks_sparse, check_struct_backend
         check_hks_backend(hks_backend)
         check_struct_backend(struct_backend)
         check_hks_large(hks_large)
+        check_hks_sparse(hks_sparse)
         nodes = np.asarray(nodes, dtype=np.int64).reshape(-1)
         return super().batch(np.stack([nodes, nodes], 1), hop, node_cap=node_cap, edge_cap=edge_cap, flags=KD_NC_FLAGS, filt=filt, hks_time=hks_time,
-                             hks_backend=hks_backend, struct_backend=struct_backend, hks_large=hks_large)
+                             hks_backend=hks_backend, struct_backend=struct_backend, hks_large=hks_large, hks_sparse=hks_sparse)
 
 
 _CACHE = {}
@@ -71,20 +72,21 @@ def _vicinities(g, ricci_curv):
 
 
 def compute_persistence_image(g, u, filt='hks', hks_time=0.1, hop=2, ricci_curv=None, mode='PI', num_models=5, max_loop_len=10,
-                              cycle_the=2, hks_backend='host', struct_backend='host', hks_large='host'):
+                              cycle_the=2, hks_backend='host', struct_backend='host', hks_large='host', hks_sparse='host'):
     """Reference signature (:95).  filt='hks' (the default), 'ricci', 'degree', 'centrality' or 'clustering' (the last two are what the shipped
     train_Teacher_Model.py:158-159 trains on); mode 'filtration' -> (filtration_val list, edge_index LongTensor[2,m]) or
     (None, None) for a ball without an edge (:103-104); mode 'PI' -> the reference's 9-tuple (:183; times are 0).
     hks_backend, struct_backend, hks_large (not in the reference): 'host' or 'device', see `data_utils_LP.Vicinities.batch`."""
-    from .data_utils_LP import STRUCTURAL_FILTS, check_hks_backend, check_hks_large, check_struct_backend
+    from .data_utils_LP import STRUCTURAL_FILTS, check_hks_backend, check_hks_large, check_hks_sparse, check_struct_backend
     check_hks_backend(hks_backend)
     check_struct_backend(struct_backend)
     check_hks_large(hks_large)
+    check_hks_sparse(hks_sparse)
     if filt != 'ricci' and filt not in STRUCTURAL_FILTS:
         print("Error: 'filt' should be 'hks', 'clustering',' centrality', 'degree' or 'ricci'! ")      # :154-155
         sys.exit()
     b = _vicinities(g, ricci_curv).batch([u], hop, filt=filt, hks_time=hks_time, hks_backend=hks_backend, struct_backend=struct_backend,
-                                         hks_large=hks_large)
+                                         hks_large=hks_large, hks_sparse=hks_sparse)
     if int(b["edge_ptr"][-1]) == 0:
         return None, None
     fv = b["f"].cpu().numpy()

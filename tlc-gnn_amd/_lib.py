@@ -21,6 +21,7 @@ ST_NOT_CONVERGED, ST_BAD_INPUT = 6, 7                               # tlc_hks_ba
 HKS_NMAX, HKS_LDS_NMAX, HKS_TMAX, HKS_NORMALISE = 256, 96, 8, 0x1   # TLC_HKS_* of include/tlcgnn.h
 HKS_LARGE_NMAX, HKS_LARGE_TIME_MAX = 4096, 64.0                     # TLC_HKS_LARGE_* of include/tlcgnn.h (tlc_hks_large_batch)
 HKS_LARGE_TILE, HKS_LARGE_KSTEP = 64, 16                            # HKSL_T, HKSL_KS of csrc/hks_large.hip: output-tile side, K-step
+HKS_SPARSE_TIME_MAX, HKS_SPARSE_PANEL, HKS_SPARSE_LONG_ROW = 64.0, 64, 256      # TLC_HKS_SPARSE_* of include/tlcgnn.h (tlc_hks_sparse_batch)
 STRUCT_DEGREE, STRUCT_CENTRALITY, STRUCT_CLUSTERING, STRUCT_NORMALISE = 0x1, 0x2, 0x4, 0x100      # TLC_STRUCT_* of include/tlcgnn.h
 STRUCT_WAVE_NMAX, STRUCT_LDS_SMALL_NMAX, STRUCT_LDS_NMAX, STRUCT_BITMAP_BITS = 64, 256, 1024, 65536
 STRUCT_KINDS = {"degree": STRUCT_DEGREE, "centrality": STRUCT_CENTRALITY, "clustering": STRUCT_CLUSTERING}   # in output-row order
@@ -52,7 +53,8 @@ SYMBOLS = [
     "tlc_lp_decode_fused", "tlc_lp_decode_fused_f32", "tlc_gat_layer_fwd", "tlc_gat_layer_tiled_fwd", "tlc_gat_tile_cut", "tlc_csr_by_target", "tlc_pdgnn_forward", "tlc_pdgnn_forward_work_bytes", "tlc_scatter_f32", "tlc_edge_head_fwd",
     "tlc_complement_rows", "tlc_complement_pairs", "tlc_select_rows", "tlc_pack_vicinities", "tlc_stack_batch", "tlc_ollivier_ricci_sinkhorn",
     "tlc_near_pairs", "tlc_w2_partial_matching", "tlc_w2_inference_matching", "tlc_gat_layer_bwd", "tlc_edge_head_bwd", "tlc_pack_offsets", "tlc_vicinity_sizes", "tlc_debug_dc_stats", "tlc_debug_tier_counts", "tlc_debug_chunk_counters", "tlc_debug_phase_profile", "tlc_debug_set_option", "tlc_debug_pair_times",
-    "tlc_hks_batch", "tlc_hks_batch_work_bytes", "tlc_hks_large_batch", "tlc_hks_large_work_bytes", "tlc_hks_batch_dt", "tlc_hks_large_batch_dt", "tlc_struct_batch", "tlc_struct_batch_work_bytes",
+    "tlc_hks_batch", "tlc_hks_batch_work_bytes", "tlc_hks_large_batch", "tlc_hks_large_work_bytes", "tlc_hks_batch_dt", "tlc_hks_large_batch_dt",
+    "tlc_hks_sparse_terms", "tlc_hks_sparse_work_bytes", "tlc_hks_sparse_batch", "tlc_hks_sparse_batch_dt", "tlc_struct_batch", "tlc_struct_batch_work_bytes",
     "tlc_ollivier_ricci_otd", "tlc_ollivier_ricci_otd_work_bytes", "tlc_pd_wide", "tlc_pd_wide_work_bytes",
     "tlc_pd_grad_work_bytes", "tlc_pd_point_vertices", "tlc_pd_filtration_grad",
     "tlc_sliced_w_work_bytes", "tlc_sliced_wasserstein",
@@ -203,6 +205,13 @@ def lib():
         L.tlc_hks_large_batch_dt.argtypes = ([C.c_void_p] * 3 + [C.c_int64] * 3 + [C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int64,
                                              C.POINTER(C.c_double), C.c_int32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                              C.c_int64, C.c_void_p])
+        L.tlc_hks_sparse_terms.argtypes, L.tlc_hks_sparse_terms.restype = [C.c_double], C.c_int32
+        L.tlc_hks_sparse_work_bytes.argtypes = [C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int64, C.c_int32, C.POINTER(C.c_int64),
+                                                C.POINTER(C.c_int64)]
+        L.tlc_hks_sparse_batch.argtypes = ([C.c_void_p] * 3 + [C.c_int64] * 3 + [C.POINTER(C.c_int64)] * 3 + [C.c_int64, C.POINTER(C.c_double),
+                                           C.c_int32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p])
+        L.tlc_hks_sparse_batch_dt.argtypes = ([C.c_void_p] * 3 + [C.c_int64] * 3 + [C.POINTER(C.c_int64)] * 3 + [C.c_int64, C.POINTER(C.c_double),
+                                              C.c_int32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p])
         L.tlc_struct_batch_work_bytes.argtypes = [C.c_int64, C.c_int64, C.c_int64, C.c_uint32, C.POINTER(C.c_int64)]
         L.tlc_struct_batch.argtypes = [C.c_void_p] * 3 + [C.c_int64] * 3 + [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
         L.tlc_dist_filtration_work_bytes.argtypes = [C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_int64)]
@@ -254,6 +263,29 @@ def lib():
         L.tlc_debug_phase_profile.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p]
         _lib = L
     return _lib
+
+
+def hks_sparse_terms(t):
+    """tlc_hks_sparse_terms in Python, operation for operation (IEEE double +, *, / only): the number of Taylor terms K of the sparse HKS
+    tier at diffusion time t -- the least k with k + 2 > t / 2 whose bound on the Poisson(t / 2) tail beyond k is <= 2^-64; -1 for a
+    time outside [0, HKS_SPARSE_TIME_MAX]."""
+    t = float(t)
+    if not 0.0 <= t <= HKS_SPARSE_TIME_MAX:
+        return -1
+    tau = t * 0.5
+    if tau == 0.0:
+        return 0
+    E = term = 1.0
+    for j in range(1, 401):
+        term = term * tau / float(j)
+        E = E + term
+    bound, slack = 1.0 / 18446744073709551616.0, 1.0 + 1.0 / 1099511627776.0
+    term = 1.0
+    for k in range(1000):
+        term = term * tau / float(k + 1)
+        if float(k + 2) > tau and term / (1.0 - tau / float(k + 2)) / E * slack <= bound:
+            return k
+    return -1
 
 
 def check(rc, what=""):

@@ -191,11 +191,12 @@ def extended_persistence(f, node_offs, edge_offs, edges, flags=_lib.KEEP_ZERO_PE
 class HksSignature(torch.autograd.Function):
     """Heat-kernel signatures of a packed batch as a differentiable function of the diffusion times: float64[T, sum n], the values of
     `engine.hks_batch` / `engine.hks_large_batch` bit for bit, with d / d t from the same kernels (tlc_hks_batch_dt, then
-    tlc_hks_large_batch_dt for the graphs above HKS_NMAX nodes).  The gradient is in `times` only:
+    tlc_hks_large_batch_dt for the graphs above HKS_NMAX nodes, then with hks_sparse='device' tlc_hks_sparse_batch_dt
+    (`engine.hks_sparse_batch`) for what is still ST_TOO_LARGE).  The gradient is in `times` only:
     grad_times[k] = sum(grad[k] * d out[k] / d t)."""
 
     @staticmethod
-    def forward(ctx, times, node_ptr, edge_ptr, edges, normalise):
+    def forward(ctx, times, node_ptr, edge_ptr, edges, normalise, hks_sparse='host'):
         host = [float(t) for t in times.detach().to(torch.float64).cpu().tolist()]    # the one read of the times
         B = node_ptr.numel() - 1
         tot_n = int(node_ptr[-1]) if B > 0 else 0
@@ -214,6 +215,17 @@ class HksSignature(torch.autograd.Function):
                 engine.hks_large_batch(node_ptr, edge_ptr, edges, rest[take].tolist(), sizes[take].tolist(), host, normalise=normalise,
                                        total_nodes=tot_n, out=out, status=st, dout=dout)
                 st_h = st.cpu()
+            wide = torch.nonzero(st_h == _lib.ST_TOO_LARGE).flatten()
+            if hks_sparse == 'device' and wide.numel():        # what the large tier does not take: tlc_hks_sparse_batch_dt, any node count
+                bad_t = [t for t in host if not 0.0 <= t <= _lib.HKS_SPARSE_TIME_MAX]
+                if bad_t:
+                    raise RuntimeError("hks_signature: graph(s) %s are still too large after the other tiers (status %d = ST_TOO_LARGE) and the "
+                                       "sparse tier takes times inside [0, %g], not %s"
+                                       % (wide.tolist(), _lib.ST_TOO_LARGE, _lib.HKS_SPARSE_TIME_MAX, bad_t))
+                engine.hks_sparse_batch(node_ptr, edge_ptr, edges, wide.tolist(), (node_ptr[1:] - node_ptr[:-1]).cpu()[wide].tolist(),
+                                        (edge_ptr[1:] - edge_ptr[:-1]).cpu()[wide].tolist(), host, normalise=normalise, total_nodes=tot_n,
+                                        out=out, status=st, dout=dout)
+                st_h = st.cpu()
             bad = torch.nonzero(st_h != _lib.ST_OK).flatten().tolist()
             if bad:
                 raise RuntimeError("hks_signature: graph(s) %s are not computed: status %s (%d = ST_TOO_LARGE: more than %d nodes; %d = "
@@ -228,20 +240,23 @@ class HksSignature(torch.autograd.Function):
     def backward(ctx, grad):
         dout, = ctx.saved_tensors
         g = (grad.to(torch.float64) * dout).sum(dim=1)
-        return g.to(device=ctx.device, dtype=ctx.dtype), None, None, None, None
+        return g.to(device=ctx.device, dtype=ctx.dtype), None, None, None, None, None
 
 
-def hks_signature(times, node_ptr, edge_ptr, edges, normalise=True):
+def hks_signature(times, node_ptr, edge_ptr, edges, normalise=True, hks_sparse='host'):
     """-> float64[T, sum n]: row k is the heat-kernel signature at times[k] of every graph of the packed batch (node_ptr / edge_ptr
     int64[B + 1], edges int32[sum m, 2] local ids, CUDA tensors; simple graphs, each undirected edge once), normalised per graph by
     (max + 1e-10) unless normalise=False; differentiable in `times`, a 1-D tensor of 1 .. HKS_TMAX entries of any float dtype, on any
     device.  The forward READS THE TIMES TO THE HOST once: both kernels take them as launch arguments, and the number of squarings of
     the large tier depends on them.  Graphs up to HKS_NMAX nodes take the Jacobi tiers, larger ones up to HKS_LARGE_NMAX the large
     tier (times inside [0, HKS_LARGE_TIME_MAX] then); anything else raises RuntimeError naming graph and status -- there is no host
-    fallback, because the host route has no derivative."""
+    fallback, because the host route has no derivative.  hks_sparse='device': the graphs above HKS_LARGE_NMAX nodes take the sparse
+    tier (tlc_hks_sparse_batch_dt; no node cap, times inside [0, HKS_SPARSE_TIME_MAX]) instead of raising; 'host' (the default) raises."""
+    if hks_sparse not in ("host", "device"):
+        raise ValueError("hks_sparse should be one of ('host', 'device'), not %r" % (hks_sparse,))
     if not torch.is_tensor(times) or times.dim() != 1 or not times.is_floating_point() or not 1 <= times.numel() <= _lib.HKS_TMAX:
         raise ValueError("hks_signature: times should be a 1-D float tensor of 1 .. %d entries" % _lib.HKS_TMAX)
-    return HksSignature.apply(times, node_ptr, edge_ptr, edges, bool(normalise))
+    return HksSignature.apply(times, node_ptr, edge_ptr, edges, bool(normalise), hks_sparse)
 
 
 class DistanceFiltration(torch.autograd.Function):

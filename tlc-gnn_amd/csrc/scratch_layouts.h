@@ -186,3 +186,46 @@ struct TlcPiImageScratch {
     TlcPiImageScratch(int64_t n_dgms, int64_t max_points, int64_t res_b, int64_t res_p)
         : least(slices_of(max_points) * res_b * res_p), total(std::min<int64_t>(n_dgms, MAX_GROUP) * least) {}
 };
+
+// tlc_hks_sparse_batch / _dt (hks_sparse.hip).  In BYTES, every array on a multiple of 256.  Once per call, from the declared node and
+// edge counts of the selection (R = their nodes, E = 2 x their edges, the CSR entries): the descriptors [n_sel][DESC] | the graphs'
+// states int[n_sel] | the sort keys u64[E], twice for the radix sort's ping-pong | its payload u8[E], twice | the columns int[E] | the
+// row starts int[R + 1] | r_u f64[R] | the row of every chunk slot of the split rows int[slots] (a graph of e entries owns
+// slots_of(e) of them) | the radix sort's hist and tot (ints: the caller passes rk_hist_ints(E) and RK_TOT_INTS of radix_passes.h,
+// which is device code and stays out of this header).  Then the panels: a panel of a graph of n nodes and e entries holds, in float64,
+// PANEL x (S [n] | s [n] | s' [n] | the split rows' partial sums [slots_of(e)] | the row blocks' partial sums [2][blocks_of(n)]).
+// `least` holds the largest panel, `total` every panel of every graph.  (The three constexpr sizes are also what the setup kernel calls.)
+struct TlcHksSparseScratch {
+    static constexpr int64_t PANEL = 64, DESC = 64, LONG_ROW = 256, SAT = INT64_MAX / 4;
+    static int64_t up256(int64_t v) { return (v + 255) & ~(int64_t)255; }
+    static constexpr int64_t slots_of(int64_t entries) { return entries / PANEL + entries / LONG_ROW + 1; }
+    static constexpr int64_t blocks_of(int64_t n) { return (n + PANEL - 1) / PANEL; }
+    static constexpr int64_t panel_doubles(int64_t n, int64_t entries) { return PANEL * (3 * n + slots_of(entries) + 2 * blocks_of(n)); }
+    static int64_t entries_of(const int64_t* sel_edges, int64_t n_sel) {
+        int64_t e = 0;
+        for (int64_t i = 0; i < n_sel; ++i) e += 2 * sel_edges[i];
+        return e;
+    }
+    int64_t rows = 0, entries = 0, slots = 0, max_n = 0;
+    int64_t descs = 0, state, key_a, key_b, lab_a, lab_b, col, rowptr, rinv, slotrow, hist, tot, panels, max_panel_bytes = 0, all_panel_bytes = 0,
+            least, total;
+    TlcHksSparseScratch(const int64_t* sel_nodes, const int64_t* sel_edges, int64_t n_sel, int64_t hist_ints, int64_t tot_ints) {
+        for (int64_t i = 0; i < n_sel; ++i) {
+            const int64_t n = sel_nodes[i], e = 2 * sel_edges[i], pb = panel_doubles(n, e) * 8;
+            rows += n; entries += e; slots += slots_of(e);
+            max_n = std::max(max_n, n);
+            if (n) max_panel_bytes = std::max(max_panel_bytes, pb);
+            const int64_t nb = blocks_of(n);                 // (saturating: 2^25 panels of 3e12 bytes do not fit an int64)
+            all_panel_bytes = std::min(SAT, all_panel_bytes + (nb && pb > SAT / nb ? SAT : nb * pb));
+        }
+        int64_t o = up256(n_sel * DESC);
+        auto take = [&](int64_t count, int64_t size_of) { const int64_t at = o; o += up256(count * size_of); return at; };
+        state = take(n_sel, 4);
+        key_a = take(entries, 8); key_b = take(entries, 8); lab_a = take(entries, 1); lab_b = take(entries, 1); col = take(entries, 4);
+        rowptr = take(rows + 1, 4); rinv = take(rows, 8); slotrow = take(slots, 4);
+        hist = take(hist_ints, 4); tot = take(tot_ints, 4);
+        panels = o;
+        least = o + max_panel_bytes;
+        total = o + all_panel_bytes;
+    }
+};

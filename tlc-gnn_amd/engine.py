@@ -398,6 +398,73 @@ def hks_large_batch(node_ptr, edge_ptr, edges, sel, sel_nodes, times, normalise=
     return out, status
 
 
+HKS_SPARSE_WORK_CAP = 2 << 30     # hks_sparse_batch(work_bytes=None): the workspace it allocates at most (never below min_bytes)
+
+
+def hks_sparse_work_bytes(sel_nodes, sel_edges, n_times=1):
+    """(min_bytes, all_bytes) of tlc_hks_sparse_work_bytes for the node and edge counts of a selection: host arithmetic, no device needed."""
+    nodes, edges = [int(v) for v in sel_nodes], [int(v) for v in sel_edges]
+    if len(nodes) != len(edges):
+        raise ValueError("hks_sparse_work_bytes: sel_nodes and sel_edges differ in length")
+    lo, hi = C.c_int64(0), C.c_int64(0)
+    _lib.check(_lib.lib().tlc_hks_sparse_work_bytes((C.c_int64 * max(len(nodes), 1))(*nodes), (C.c_int64 * max(len(edges), 1))(*edges),
+                                                    C.c_int64(len(nodes)), C.c_int32(n_times), C.byref(lo), C.byref(hi)),
+               "tlc_hks_sparse_work_bytes")
+    return lo.value, hi.value
+
+
+@_lib.on_device_of
+def hks_sparse_batch(node_ptr, edge_ptr, edges, sel, sel_nodes, sel_edges, times, normalise=True, total_nodes=None, out=None, status=None,
+                     work_bytes=None, dout=None):
+    """Heat-kernel signatures of SELECTED graphs of a packed batch on the device without eigenpairs and without a dense matrix
+    (tlc_hks_sparse_batch: the columns of exp(-t/2 L) by a Taylor chain of sparse products, 64 columns per wavefront) -- the tier for
+    sparse graphs of any size; times inside [0, HKS_SPARSE_TIME_MAX].
+
+    The arguments of `hks_large_batch`, and sel_edges: the selected graphs' edge counts (a HOST sequence like sel_nodes; a count that
+    is not the device's is ST_BAD_INPUT).  work_bytes: at least min_bytes of `hks_sparse_work_bytes` (the panels then run in groups
+    that fit, same bits); None: all_bytes, bounded by HKS_SPARSE_WORK_CAP.  Returns (out, status), with dout (out, dout, status)."""
+    torch = _lib.require_gpu()
+    dev = node_ptr.device
+    times = [float(t) for t in (times if hasattr(times, "__len__") else [times])]
+    T, B = len(times), node_ptr.numel() - 1
+    if not 1 <= T <= _lib.HKS_TMAX:
+        raise ValueError("hks_sparse_batch: 1 .. %d times per call" % _lib.HKS_TMAX)
+    sel, sel_nodes, sel_edges = [int(v) for v in sel], [int(v) for v in sel_nodes], [int(v) for v in sel_edges]
+    if len(sel) != len(sel_nodes) or len(sel) != len(sel_edges):
+        raise ValueError("hks_sparse_batch: sel, sel_nodes and sel_edges differ in length")
+    tot_m = int(edges.shape[0])
+    tot_n = int(total_nodes) if total_nodes is not None else (int(node_ptr[-1]) if B > 0 else 0)
+    if out is None:
+        out = torch.full((T, tot_n), float("nan"), dtype=torch.float64, device=dev)
+    if status is None:
+        status = torch.zeros(max(B, 1), dtype=torch.uint8, device=dev)[:B]
+    if tuple(out.shape) != (T, tot_n) or out.dtype != torch.float64 or not out.is_contiguous() or status.numel() != B or status.dtype != torch.uint8 \
+            or not status.is_contiguous():
+        raise ValueError("hks_sparse_batch: out should be contiguous float64[%d, %d] and status contiguous uint8[%d]" % (T, tot_n, B))
+    want_dt = dout is not None and dout is not False
+    if want_dt:
+        if dout is True:
+            dout = torch.full((T, tot_n), float("nan"), dtype=torch.float64, device=dev)
+        if tuple(dout.shape) != (T, tot_n) or dout.dtype != torch.float64 or not dout.is_contiguous():
+            raise ValueError("hks_sparse_batch: dout should be contiguous float64[%d, %d]" % (T, tot_n))
+    S = len(sel)
+    if S > 0:
+        lo, hi = hks_sparse_work_bytes(sel_nodes, sel_edges, T)
+        need = max(lo, min(hi, HKS_SPARSE_WORK_CAP)) if work_bytes is None else int(work_bytes)
+        work = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+        head = (_lib.ptr(node_ptr.contiguous()), _lib.ptr(edge_ptr.contiguous()), _lib.ptr(edges.contiguous()), C.c_int64(B), C.c_int64(tot_n),
+                C.c_int64(tot_m), (C.c_int64 * S)(*sel), (C.c_int64 * S)(*sel_nodes), (C.c_int64 * S)(*sel_edges), C.c_int64(S),
+                (C.c_double * T)(*times), C.c_int32(T), C.c_uint32(_lib.HKS_NORMALISE if normalise else 0), _lib.ptr(out))
+        tail = (_lib.ptr(status), _lib.ptr(work), C.c_int64(need), _lib.stream_ptr())
+        if want_dt:
+            _lib.check(_lib.lib().tlc_hks_sparse_batch_dt(*head, _lib.ptr(dout), *tail), "tlc_hks_sparse_batch_dt")
+        else:
+            _lib.check(_lib.lib().tlc_hks_sparse_batch(*head, *tail), "tlc_hks_sparse_batch")
+    if want_dt:
+        return out, dout, status
+    return out, status
+
+
 def struct_kinds(kinds):
     """A name or a sequence of names of _lib.STRUCT_KINDS -> (bit mask, the names in output-row order: degree, centrality, clustering)."""
     names = [kinds] if isinstance(kinds, str) else list(kinds)

@@ -29,14 +29,16 @@ def check_which(which):
     return which
 
 
-def hks_filtration(time, node_offs, edge_offs, edges, normalise=True):
+def hks_filtration(time, node_offs, edge_offs, edges, normalise=True, hks_sparse='host'):
     """-> float64[sum n]: the heat-kernel-signature filtration of every graph at the diffusion time `time` (a scalar or one-element float
     tensor, which may require grad), the values of `data_utils_LP.hks_filtration_device(..., hks_large='device')` bit for bit.  It goes
     straight into `diagrams` / `images` / `wasserstein_to` / `sliced_wasserstein_to` as f, and their gradient reaches `time`.  The time is
-    read to the host once per call; a graph the device tiers do not take raises RuntimeError (`autograd.hks_signature`)."""
+    read to the host once per call; a graph the device tiers do not take raises RuntimeError (`autograd.hks_signature`).
+    hks_sparse='device': what the Jacobi and large tiers leave as too large (any node count, a time inside [0, HKS_SPARSE_TIME_MAX])
+    takes the sparse tier, value and derivative from tlc_hks_sparse_batch_dt, instead of raising; 'host', the default, raises."""
     if not torch.is_tensor(time) or time.numel() != 1:
         raise ValueError("hks_filtration: time should be a scalar or one-element tensor")
-    return autograd.hks_signature(time.reshape(1), node_offs, edge_offs, edges, normalise=normalise)[0]
+    return autograd.hks_signature(time.reshape(1), node_offs, edge_offs, edges, normalise=normalise, hks_sparse=hks_sparse)[0]
 
 
 def distance_filtration(w, node_offs, edge_offs, edges, roots=None, descriptor="sum", norm="max", include_roots=False, unreachable_100=False):
