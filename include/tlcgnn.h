@@ -810,6 +810,38 @@ int tlc_w2_inference_matching(int32_t n_problems, const int64_t* d_xoff, const d
                               double* d_wyd, int32_t* d_assign_x, int32_t* d_assign_y, double* d_gradX, uint8_t* d_status,
                               void* stream);
 
+/* ---- The same two losses above 4 096 rows: the workspace tier (csrc/w2_large.hip) --------------------------------
+ * infer = 0: the training form of tlc_w2_partial_matching (n predicted rows onto m targets and n - m copies of the diagonal, N = n);
+ * infer = 1: the evaluation form of tlc_w2_inference_matching (N = n + m).  Cost, loss, the three partial sums, d_assign_x,
+ * d_assign_y and d_gradX are what the two entries above specify; d_wyd and d_assign_y may be null when infer = 0.  The same
+ * shortest-augmenting-path method, one workgroup of 1 024 threads per problem in flight, with the O(N) state (34 bytes per row) in
+ * the caller's workspace instead of LDS, a dual-feasible start (u_i = min_j c_ij, v_j = min_i (c_ij - u_i), then the rows ascending
+ * take their lowest free tight column) and one dual update per augmentation.
+ *   min_rows: a problem with N <= min_rows is LEFT ALONE, none of its outputs is written.  A mixed batch is two calls: the entries
+ *   above give the problems beyond their 4 096 rows status 2 and defined outputs, and this call with min_rows = 4096 overwrites
+ *   exactly those.  min_rows = 0 takes every problem that has a row, -1 the problems without rows too.
+ *   d_status[b]: 0 ok; 1 = n < m in the training form; 2 = N > TLC_W2_LARGE_NMAX; 3 = a NaN / Inf coordinate.  For 1 .. 3 the
+ *   outputs are those of the entries above (loss 0, or NaN for status 3; no matching; zero gradient); the other problems of the batch
+ *   are not affected.  Empty diagrams as above.
+ *   d_work / work_bytes: 256-byte aligned, at least tlc_w2_large_work_bytes(N_max, 1) bytes, N_max = the rows of the largest problem
+ *   this call solves (host arithmetic; -1 for a negative argument; linear in slots).  The workspace holds work_bytes / (the bytes of
+ *   one slot) slots; the grid is min(slots, problems above min_rows) workgroups and a workgroup takes problems by that stride, so the
+ *   least workspace runs them one after another.  A problem's bits depend on the problem alone: not on the batch, the slot, the
+ *   workspace or the run.  Ties take the lowest column, but under tied costs the start may choose another optimal assignment than the
+ *   entries above, and sums are ordered differently (loss equal to rounding, not to the bit).
+ *   The entry reads the offsets back (one copy that waits for `stream`).  TLC_ERR_INVALID_ARG before any launch: order not 1 or 2,
+ *   infer not 0 or 1, min_rows < -1, a null pointer, a misaligned or too small d_work, decreasing offsets.  The first
+ *   TLC_W2_LARGE_COUNTERS int64 of every slot hold what its workgroup did in the call: steps, augmentations, rows the start assigned,
+ *   problems (read by tools/time_w2_large.py).  No floating-point atomics; every loop is bounded by N. */
+#define TLC_W2_LDS_NMAX        4096    /* the rows the two entries above take */
+#define TLC_W2_LARGE_NMAX      65536
+#define TLC_W2_LARGE_COUNTERS  4
+int64_t tlc_w2_large_work_bytes(int64_t max_rows, int32_t slots);
+int tlc_w2_large_matching(int32_t n_problems, const int64_t* d_xoff, const double* d_X, const int64_t* d_yoff, const double* d_Y,
+                          int order, int infer, int32_t min_rows, double* d_loss, double* d_wxy, double* d_wxd, double* d_wyd,
+                          int32_t* d_assign_x, int32_t* d_assign_y, double* d_gradX, uint8_t* d_status, void* d_work,
+                          int64_t work_bytes, void* stream);
+
 /* ---- The sliced Wasserstein diagram loss and its gradient (csrc/sliced_w.hip) ----------------------------------
  * `compute_PD_loss(kernel='sliced')` of Knowledge_Distillation/Teacher_model.py:110-124 (the distance of Carriere et al.), at any
  * diagram size.  The directions and the scale are INPUTS: the reference's angles are made by the caller (ops.sliced_directions).

@@ -98,7 +98,7 @@ class Teacher_Model(torch.nn.Module):
         return not (torch.is_grad_enabled() and (x0.requires_grad or any(p.requires_grad for p in self.parameters())))
 
     def forward(self, x0, edge_index0, PD, kernel='sliced', M=50, p=1, pair_diagonal=False, draw_fig=False, fig_name='',
-                compute_loss=True, grad_PI=True, graph_ptr=None, edge_ptr=None, pd_ptr=None, csr=None):
+                compute_loss=True, grad_PI=True, graph_ptr=None, edge_ptr=None, pd_ptr=None, csr=None, w2_large='refuse'):
         """Reference signature.  compute_loss=True needs kernel='wasserstein' (p = 1 or 2) and returns
         loss0 (differentiable), loss_xy0, loss_xd0, loss_yd0 like :63-66.  pair_diagonal=False (training, :64): every target
         point is matched, loss_yd0 is 0 (wasserstein.py:330-372, num_models=1); pair_diagonal=True (evaluation, :66): the
@@ -113,6 +113,8 @@ class Teacher_Model(torch.nn.Module):
         pd_ptr (int64 [B+1]) gives the rows of PD that belong to each graph; without it every graph must have exactly as
         many target points as edges (PD = Ord0 + Ext1 of the same graph: n - 1 + m - n + 1 = m points, data_utils_GC.py:166).
         csr: a `GraphBatch(edge_index0, n)` the caller built once for this batch (else the CSR by target is built per call).
+        w2_large (kernel='wasserstein'): 'refuse' raises for a graph whose matching has more than 4 096 rows, 'device' matches up to
+        65 536 in the workspace tier (`ops.w2_large_matching`), the range in which the reference still trains with this loss.
         """
         if draw_fig:
             raise NotImplementedError("Teacher_Model (HIP): draw_fig=False only")
@@ -171,7 +173,7 @@ class Teacher_Model(torch.nn.Module):
                 loss0 = autograd.sliced_diagram_loss(x, PD.to(torch.float64), M=M, xoff=xoff, yoff=yoff).sum().reshape(1)
                 loss_xy0, loss_xd0, loss_yd0 = (torch.zeros(1, dtype=loss0.dtype, device=loss0.device) for _ in range(3))
             else:
-                parts = autograd.diagram_loss(x, PD.to(torch.float64), order=p, xoff=xoff, yoff=yoff, infer=bool(pair_diagonal))
+                parts = autograd.diagram_loss(x, PD.to(torch.float64), order=p, xoff=xoff, yoff=yoff, infer=bool(pair_diagonal), large=w2_large)
                 loss0, loss_xy0, loss_xd0 = parts[0].sum().reshape(1), parts[1].sum().reshape(1), parts[2].sum().reshape(1)
                 loss_yd0 = parts[3].sum().reshape(1) if pair_diagonal else torch.zeros(1, dtype=loss0.dtype, device=loss0.device)
         x0_out = x

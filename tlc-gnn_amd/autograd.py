@@ -49,7 +49,8 @@ class EdgeHead(torch.autograd.Function):
         return gx, gw5, gb5, gw6, gb6, None, None, None
 
 
-_W2_STATUS = "1 = fewer predicted than target points, 2 = too many points for one problem (4096), 3 = NaN / Inf coordinates"
+_W2_STATUS = "1 = fewer predicted than target points, 2 = too many points for one problem (%s), 3 = NaN / Inf coordinates"
+_W2_CAP = {"refuse": "4096; large='device' takes up to 65536", "device": "65536"}
 
 
 class DiagramLoss(torch.autograd.Function):
@@ -61,14 +62,14 @@ class DiagramLoss(torch.autograd.Function):
     -> (loss, wxy, wxd, wyd)."""
 
     @staticmethod
-    def forward(ctx, pd_hat, xoff, target, yoff, order, infer):
+    def forward(ctx, pd_hat, xoff, target, yoff, order, infer, large="refuse"):
         if infer:
-            r = ops.w2_inference_matching(xoff, pd_hat.detach(), yoff, target, order=order, want_grad=True)
+            r = ops.w2_inference_matching(xoff, pd_hat.detach(), yoff, target, order=order, want_grad=True, large=large)
         else:
-            r = ops.w2_partial_matching(xoff, pd_hat.detach(), yoff, target, order=order, want_grad=True)
+            r = ops.w2_partial_matching(xoff, pd_hat.detach(), yoff, target, order=order, want_grad=True, large=large)
         bad = r["status"] != 0
         if bool(bad.any()):
-            raise ValueError("diagram loss: status %s (%s)" % (r["status"].tolist(), _W2_STATUS))
+            raise ValueError("diagram loss: status %s (%s)" % (r["status"].tolist(), _W2_STATUS % _W2_CAP[large]))
         ctx.save_for_backward(r["grad"], xoff)
         dt = pd_hat.dtype
         ctx.dtype = dt
@@ -82,7 +83,7 @@ class DiagramLoss(torch.autograd.Function):
         grad, xoff = ctx.saved_tensors
         cnt = xoff[1:] - xoff[:-1]
         per_point = torch.repeat_interleave(gloss.to(torch.float64), cnt)          # d total / d loss[b] for each predicted point
-        return (grad * per_point.unsqueeze(1)).to(ctx.dtype), None, None, None, None, None
+        return (grad * per_point.unsqueeze(1)).to(ctx.dtype), None, None, None, None, None, None
 
 
 class SlicedDiagramLoss(torch.autograd.Function):
@@ -366,14 +367,17 @@ def edge_head(x, w5, b5, w6, b6, src, dst, prelu_slope):
     return EdgeHead.apply(x, w5, b5, w6, b6, src, dst, float(prelu_slope))
 
 
-def diagram_loss(pd_hat, target, order=2, xoff=None, yoff=None, infer=False):
-    """-> (loss, wxy, wxd) per problem; infer=True: (loss, wxy, wxd, wyd) of the evaluation distance."""
+def diagram_loss(pd_hat, target, order=2, xoff=None, yoff=None, infer=False, large="refuse"):
+    """-> (loss, wxy, wxd) per problem; infer=True: (loss, wxy, wxd, wyd) of the evaluation distance.
+    large: 'refuse' raises for a problem of more than 4 096 rows (predicted points; with infer, predicted + target points), 'device'
+    solves those of up to 65 536 in the workspace tier (`ops.w2_large_matching`)."""
+    ops.check_w2_large(large)
     dev = pd_hat.device
     if xoff is None:
         xoff = torch.tensor([0, pd_hat.shape[0]], dtype=torch.int64, device=dev)
     if yoff is None:
         yoff = torch.tensor([0, target.shape[0]], dtype=torch.int64, device=dev)
-    return DiagramLoss.apply(pd_hat, xoff, target, yoff, int(order), bool(infer))
+    return DiagramLoss.apply(pd_hat, xoff, target, yoff, int(order), bool(infer), large)
 
 
 def sliced_diagram_loss(pd_hat, target, M=50, xoff=None, yoff=None, dirs=None, scale=None):

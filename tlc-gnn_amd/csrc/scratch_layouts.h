@@ -187,6 +187,25 @@ struct TlcPiImageScratch {
         : least(slices_of(max_points) * res_b * res_p), total(std::min<int64_t>(n_dgms, MAX_GROUP) * least) {}
 };
 
+// tlc_w2_large_matching (w2_large.hip).  In BYTES.  The workspace is `slots` equal slots and nothing else; a workgroup owns one slot for
+// the whole launch.  A slot for problems of up to max_rows rows / columns, every array on a multiple of 256: the control words [HEAD
+// bytes]: the counters int64[COUNTERS] (steps, augmentations, rows the start assigned, problems) | the row duals u f64[R] | the column
+// duals v f64[R] | the columns' path lengths minv f64[R] | the column -> row map pcol int[R] | the path links way int[R] | the columns'
+// used marks u8[R] | the rows' "the start assigned it" marks u8[R]: 34 bytes per row.  Rows above NMAX are refused and need no state.
+struct TlcW2LargeScratch {
+    static constexpr int64_t HEAD = 256, COUNTERS = 4, NMAX = 65536, PER_ROW = 8 * 3 + 4 * 2 + 1 * 2;
+    static int64_t up256(int64_t v) { return (v + 255) & ~(int64_t)255; }
+    int64_t rows, head = 0, u, v, minv, pcol, way, used, rdone, slot_bytes;
+    explicit TlcW2LargeScratch(int64_t max_rows = 0) : rows(std::min(std::max<int64_t>(max_rows, 0), NMAX)) {
+        int64_t o = HEAD;
+        auto take = [&](int64_t size_of) { const int64_t at = o; o += up256(rows * size_of); return at; };
+        u = take(8); v = take(8); minv = take(8); pcol = take(4); way = take(4); used = take(1); rdone = take(1);
+        slot_bytes = o;
+    }
+    int64_t total(int64_t slots) const { return slots * slot_bytes; }
+    int64_t slots_in(int64_t work_bytes) const { return work_bytes / slot_bytes; }
+};
+
 // tlc_hks_sparse_batch / _dt (hks_sparse.hip).  In BYTES, every array on a multiple of 256.  Once per call, from the declared node and
 // edge counts of the selection (R = their nodes, E = 2 x their edges, the CSR entries): the descriptors [n_sel][DESC] | the graphs'
 // states int[n_sel] | the sort keys u64[E], twice for the radix sort's ping-pong | its payload u8[E], twice | the columns int[E] | the

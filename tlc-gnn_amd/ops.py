@@ -663,10 +663,13 @@ def scatter(src, index, dim_size, reduce="sum"):
 
 
 @_lib.on_device_of
-def w2_partial_matching(xoff, X, yoff, Y, order=2, want_grad=True, max_points=None):
+def w2_partial_matching(xoff, X, yoff, Y, order=2, want_grad=True, max_points=None, large="refuse"):
     """PDGNN's diagram loss for a batch of (predicted, target) diagram pairs (Knowledge_Distillation/wasserstein.py:198-379 with
     num_models = 1): xoff / yoff int64[B+1] offsets, X / Y float64[., 2] CUDA tensors.
-    -> dict(loss[B], wxy[B], wxd[B], assign[sum n] (target index or -1 = diagonal), grad[sum n, 2] (d loss / d X), status[B])."""
+    -> dict(loss[B], wxy[B], wxd[B], assign[sum n] (target index or -1 = diagonal), grad[sum n, 2] (d loss / d X), status[B]).
+    large: 'refuse': a problem of more than 4 096 predicted points gets status 2; 'device': a second call (`w2_large_matching` with
+    min_rows = 4096) solves those of up to 65 536 into the same tensors."""
+    check_w2_large(large)
     torch = _lib.require_gpu()
     B = xoff.numel() - 1
     dev = X.device
@@ -694,14 +697,20 @@ def w2_partial_matching(xoff, X, yoff, Y, order=2, want_grad=True, max_points=No
                                             C.c_int(order), C.c_int32(max_points), _lib.ptr(loss), _lib.ptr(wxy), _lib.ptr(wxd),
                                             _lib.ptr(assign), _lib.ptr(grad), _lib.ptr(status), _lib.stream_ptr())
     _lib.check(rc, "tlc_w2_partial_matching")
+    if large == "device" and max_points > _lib.W2_LDS_NMAX:
+        w2_large_matching(xoff, X, yoff, Y, order=order, infer=False, min_rows=_lib.W2_LDS_NMAX, want_grad=want_grad,
+                          _out=dict(loss=loss, wxy=wxy, wxd=wxd, wyd=None, assign_x=assign, assign_y=None, grad=grad, status=status))
     return dict(loss=loss[:B], wxy=wxy[:B], wxd=wxd[:B], assign=assign[:nx], grad=None if grad is None else grad[:nx], status=status[:B])
 
 
 @_lib.on_device_of
-def w2_inference_matching(xoff, X, yoff, Y, order=2, want_grad=False, max_points=None):
+def w2_inference_matching(xoff, X, yoff, Y, order=2, want_grad=False, max_points=None, large="refuse"):
     """The evaluation distance of PDGNN (`wasserstein_distance_inference`, Knowledge_Distillation/wasserstein.py:93-195: both
     diagrams may use the diagonal) for a batch of (predicted, target) pairs.
-    -> dict(loss[B], wxy[B], wxd[B], wyd[B], assign_x[sum n], assign_y[sum m], grad or None, status[B])."""
+    -> dict(loss[B], wxy[B], wxd[B], wyd[B], assign_x[sum n], assign_y[sum m], grad or None, status[B]).
+    large: 'refuse': a pair of more than 4 096 points in all gets status 2; 'device': a second call (`w2_large_matching` with
+    min_rows = 4096) solves those of up to 65 536 into the same tensors."""
+    check_w2_large(large)
     torch = _lib.require_gpu()
     B = xoff.numel() - 1
     dev = X.device
@@ -727,8 +736,74 @@ def w2_inference_matching(xoff, X, yoff, Y, order=2, want_grad=False, max_points
                                               _lib.ptr(wxy), _lib.ptr(wxd), _lib.ptr(wyd), _lib.ptr(ax), _lib.ptr(ay), _lib.ptr(grad),
                                               _lib.ptr(status), _lib.stream_ptr())
     _lib.check(rc, "tlc_w2_inference_matching")
+    if large == "device" and max_points > _lib.W2_LDS_NMAX:
+        w2_large_matching(xoff, X, yoff, Y, order=order, infer=True, min_rows=_lib.W2_LDS_NMAX, want_grad=want_grad,
+                          _out=dict(loss=loss, wxy=wxy, wxd=wxd, wyd=wyd, assign_x=ax, assign_y=ay, grad=grad, status=status))
     return dict(loss=loss[:B], wxy=wxy[:B], wxd=wxd[:B], wyd=wyd[:B], assign_x=ax[:nx], assign_y=ay[:ny],
                 grad=None if grad is None else grad[:nx], status=status[:B])
+
+
+W2_LARGE_MAX_WORK_BYTES, W2_LARGE_MAX_SLOTS = 2 << 30, 256          # the most workspace w2_large_matching allocates, and slots in it
+
+
+def check_w2_large(large):
+    if large not in ("refuse", "device"):
+        raise ValueError("large / w2_large should be 'refuse' or 'device', not %r" % (large,))
+
+
+def w2_large_rows(xoff, yoff, infer, min_rows=0):
+    """(rows of the largest problem `tlc_w2_large_matching` would solve, number of problems it would take) from the offsets: one host
+    read.  It takes the problems of more than min_rows rows and solves those of them up to W2_LARGE_NMAX (training form: with n >= m)."""
+    n = (xoff[1:] - xoff[:-1]).to("cpu")
+    m = (yoff[1:] - yoff[:-1]).to("cpu")
+    N = n + m if infer else n
+    taken = N > min_rows
+    solved = taken & (N <= _lib.W2_LARGE_NMAX) & ((n >= m) if not infer else (N >= 0))
+    return (int(N[solved].max()) if bool(solved.any()) else 0), int(taken.sum())
+
+
+@_lib.on_device_of
+def w2_large_matching(xoff, X, yoff, Y, order=2, infer=False, min_rows=0, want_grad=True, work=None, _out=None):
+    """The matching loss of `w2_partial_matching` (infer=False) / `w2_inference_matching` (infer=True) for problems of up to 65 536 rows
+    (predicted points; with infer, predicted + target points): `tlc_w2_large_matching`, the workspace tier of csrc/w2_large.hip.
+    A problem of at most min_rows rows is left alone (0: every problem that has a row is solved; -1: those without rows too).
+    work: a uint8 CUDA tensor (256-byte aligned) of at least `tlc_w2_large_work_bytes(largest problem, 1)` bytes; by default one slot
+    per problem taken, up to W2_LARGE_MAX_SLOTS slots and W2_LARGE_MAX_WORK_BYTES.  The result does not depend on it.
+    -> dict(loss[B], wxy[B], wxd[B], wyd[B] or None, assign_x[sum n], assign_y[sum m] or None, grad or None, status[B], work)."""
+    torch = _lib.require_gpu()
+    B = xoff.numel() - 1
+    dev = X.device
+    X = X.to(torch.float64).contiguous()
+    Y = Y.to(torch.float64).contiguous()
+    xoff = xoff.to(torch.int64).contiguous()
+    yoff = yoff.to(torch.int64).contiguous()
+    nx, ny = int(X.shape[0]), int(Y.shape[0])
+    rows = taken = 0
+    if B > 0:
+        ends = torch.stack([xoff[-1], yoff[-1]]).tolist()
+        if ends[0] > nx or ends[1] > ny:
+            raise ValueError("w2_large_matching: offsets end at (%d, %d) but X / Y hold (%d, %d) points" % (ends[0], ends[1], nx, ny))
+        rows, taken = w2_large_rows(xoff, yoff, infer, min_rows)
+    if _out is None:
+        loss = torch.zeros(max(B, 1), dtype=torch.float64, device=dev)
+        _out = dict(loss=loss, wxy=torch.zeros_like(loss), wxd=torch.zeros_like(loss), wyd=torch.zeros_like(loss) if infer else None,
+                    assign_x=torch.full((max(nx, 1),), -1, dtype=torch.int32, device=dev),
+                    assign_y=torch.full((max(ny, 1),), -1, dtype=torch.int32, device=dev) if infer else None,
+                    grad=torch.zeros((max(nx, 1), 2), dtype=torch.float64, device=dev) if want_grad else None,
+                    status=torch.zeros(max(B, 1), dtype=torch.uint8, device=dev))
+    o = _out
+    if work is None:
+        slot = int(_lib.lib().tlc_w2_large_work_bytes(C.c_int64(rows), C.c_int32(1)))
+        slots = max(1, min(taken, W2_LARGE_MAX_SLOTS, W2_LARGE_MAX_WORK_BYTES // slot))
+        work = torch.empty(slot * slots, dtype=torch.uint8, device=dev)
+    rc = _lib.lib().tlc_w2_large_matching(C.c_int32(B), _lib.ptr(xoff), _lib.ptr(X) if nx else None, _lib.ptr(yoff), _lib.ptr(Y) if ny else None,
+                                          C.c_int(order), C.c_int(1 if infer else 0), C.c_int32(min_rows), _lib.ptr(o["loss"]), _lib.ptr(o["wxy"]),
+                                          _lib.ptr(o["wxd"]), _lib.ptr(o["wyd"]), _lib.ptr(o["assign_x"]), _lib.ptr(o["assign_y"]),
+                                          _lib.ptr(o["grad"]), _lib.ptr(o["status"]), _lib.ptr(work), C.c_int64(work.numel()), _lib.stream_ptr())
+    _lib.check(rc, "tlc_w2_large_matching")
+    return dict(loss=o["loss"][:B], wxy=o["wxy"][:B], wxd=o["wxd"][:B], wyd=None if o["wyd"] is None else o["wyd"][:B],
+                assign_x=o["assign_x"][:nx], assign_y=None if o["assign_y"] is None else o["assign_y"][:ny],
+                grad=None if o["grad"] is None else o["grad"][:nx], status=o["status"][:B], work=work)
 
 
 def sliced_directions(M=50):

@@ -102,18 +102,20 @@ def images(f, node_offs, edge_offs, edges, which="ord0+ext1", res=5, pd_large="h
     return autograd.diagram_image(pts, offs, res, imager=imager, grad=grad)
 
 
-def wasserstein_to(f, node_offs, edge_offs, edges, target_pts, target_offs, which="ord0+ext1", order=2, pd_large="host"):
+def wasserstein_to(f, node_offs, edge_offs, edges, target_pts, target_offs, which="ord0+ext1", order=2, pd_large="host", w2_large="refuse"):
     """[B] Wasserstein distances (order `order`, both diagrams may use the diagonal: `autograd.diagram_loss(..., infer=True)`) between
-    every graph's diagram `which` and the fixed target diagrams target_pts [sum k, 2] / target_offs int64[B + 1]; differentiable in f."""
+    every graph's diagram `which` and the fixed target diagrams target_pts [sum k, 2] / target_offs int64[B + 1]; differentiable in f.
+    w2_large: 'refuse' raises for a pair of more than 4 096 points in all, 'device' matches pairs of up to 65 536 (the workspace tier,
+    `ops.w2_large_matching`: exact, but a million and more serial steps per problem)."""
     check_which(which)
     pts, offs = _select(f, node_offs, edge_offs, edges, which, pd_large)
-    return autograd.diagram_loss(pts, target_pts.to(pts.dtype), order=order, xoff=offs, yoff=target_offs, infer=True)[0]
+    return autograd.diagram_loss(pts, target_pts.to(pts.dtype), order=order, xoff=offs, yoff=target_offs, infer=True, large=w2_large)[0]
 
 
 def sliced_wasserstein_to(f, node_offs, edge_offs, edges, target_pts, target_offs, which="ord0+ext1", M=50, pd_large="host"):
     """[B] sliced Wasserstein distances (`autograd.sliced_diagram_loss` over the reference's M directions) between every graph's
     diagram `which` and the target diagrams target_pts [sum k, 2] / target_offs int64[B + 1]; differentiable in f (and in target_pts
-    when it requires grad).  The sibling of `wasserstein_to` without its cap of 4 096 points: sorts instead of an assignment."""
+    when it requires grad).  The sibling of `wasserstein_to` without a cap on the points and at a fraction of its cost: sorts instead of an assignment."""
     check_which(which)
     pts, offs = _select(f, node_offs, edge_offs, edges, which, pd_large)
     return autograd.sliced_diagram_loss(pts, target_pts.to(pts.dtype), M=M, xoff=offs, yoff=target_offs)
