@@ -895,6 +895,51 @@ int tlc_sliced_wasserstein(int32_t n_problems, const int64_t* d_xoff, const doub
                            int32_t n_dirs, const double* d_dirs, double scale, int64_t max_points, double* d_loss, double* d_gradX,
                            double* d_gradY, uint8_t* d_status, void* d_work, int64_t work_bytes, void* stream);
 
+/* ---- The bottleneck distance between diagrams, a witness matching and its gradient (csrc/bottleneck.hip) ----------
+ * THE FUNCTION.  Problem b: diagrams X (n points) and Y (m points), fp64 (birth, death) rows in the packed layout of
+ * tlc_w2_inference_matching; both may use the diagonal, N = n + m.  Rows 0 .. n-1 are X's points and rows n .. N-1 copies of the
+ * diagonal; columns 0 .. m-1 are Y's points and columns m .. N-1 copies of the diagonal.  In plain fp64 subtract, abs, max and multiply
+ * (no FMA, no power, no root):
+ *     c(i, j) = max(|X_i.birth - Y_j.birth|, |X_i.death - Y_j.death|)     i < n,  j < m      (max(a, b) = a > b ? a : b)
+ *     c(i, j) = |X_i.death - X_i.birth| * 0.5                             i < n,  j >= m
+ *     c(i, j) = |Y_j.death - Y_j.birth| * 0.5                             i >= n, j < m
+ *     c(i, j) = +0.0                                                      i >= n, j >= m
+ *   d_dist[b] = the least t for which a perfect matching of the N x N problem uses only costs <= t: one entry of the matrix, exact.  An
+ *   empty diagram on one side gives the largest diagonal cost of the other; both empty (N = 0) give +0.0.
+ *
+ * THE WITNESS.  d_assign_x[i] = the target of predicted point i or -1 = diagonal, d_assign_y[j] = the predicted point of target j or
+ * -1, as tlc_w2_inference_matching writes them: inverse to each other, and the matching they describe (every point left out of a pair
+ * goes to the diagonal) attains d_dist.  Under tied costs it is one of several; it depends on the problem alone.
+ *   d_arg[b] = (i, j): the pair of that matching whose cost equals d_dist; -1 stands for the diagonal side.  Among several pairs of that
+ *   cost the lowest predicted index i wins (a point of X sent to the diagonal counts under its own index; a matching has one pair per
+ *   i), and a pair (-1, j) is taken only if no pair with a predicted point attains the value, then the one of the lowest j.  Pairs of
+ *   two diagonal copies are never named.  N = 0: (-1, -1).
+ *
+ * THE GRADIENT.  d_gradX float64[sum n, 2] / d_gradY float64[sum m, 2] (each may be NULL): every row of every problem is written, and
+ * only the rows d_arg names are non-zero.  With sign(0) = 0:
+ *     (i, j):   e = X_i - Y_j.  |e.birth| >= |e.death| (birth wins an exact tie): gradX[i] = (sign(e.birth), 0), else (0, sign(e.death));
+ *               gradY[j] = the negative of gradX[i].
+ *     (i, -1):  gradX[i] = (-0.5, +0.5) * sign(X_i.death - X_i.birth).          (-1, j):  gradY[j] = (-0.5, +0.5) * sign(Y_j.death - Y_j.birth).
+ * Where the maximum is attained by several pairs, or by both coordinates, d_B is not differentiable and this is a convention (one
+ * subgradient), as elsewhere in `topo`.
+ *
+ * d_status uint8[B]: 0 ok; 2 = N > TLC_BN_NMAX: distance 0, no matching (-1 everywhere), d_arg (-1, -1), zero gradient; 3 = a NaN / Inf
+ * coordinate: distance NaN, otherwise the same.  A bad problem never affects its neighbours.  Finite coordinates whose difference
+ * overflows give +Inf costs, which compare like any other.
+ * max_points: an upper bound of one problem's N.  The entry reads the offsets back once and synchronises the stream before it
+ * launches anything.  TLC_ERR_INVALID_ARG, nothing launched: n_problems < 0, max_points < 0, a null required pointer (the offsets,
+ * d_dist, d_arg, the two maps, d_status; d_X / d_Y where there are points), offsets that decrease or a problem above max_points.
+ * n_problems == 0: TLC_OK, nothing read.
+ *
+ * Size classes by N alone: up to TLC_BN_WAVE_NMAX a wavefront per problem, up to TLC_BN_NMAX a workgroup per problem with the O(N)
+ * state in LDS.  Costs are recomputed from the points, no matrix is stored; every loop is bounded by N; there are no floating-point
+ * atomics; a problem's bits depend on the problem alone: not on the batch, the grid or the run. */
+#define TLC_BN_WAVE_NMAX  512
+#define TLC_BN_NMAX       4096
+int tlc_bottleneck_matching(int32_t n_problems, const int64_t* d_xoff, const double* d_X, const int64_t* d_yoff, const double* d_Y,
+                            int32_t max_points, double* d_dist, int32_t* d_arg /* [n_problems,2] */, int32_t* d_assign_x, int32_t* d_assign_y,
+                            double* d_gradX, double* d_gradY, uint8_t* d_status, void* stream);
+
 /* ---- The general persistence imager and its gradient (csrc/pi_general.hip) --------------------------------------
  * PersistenceImager.transform of Knowledge_Distillation/pimg.py:354-414 (= sg2dgm/PersistenceImager.pyx:352-403) for any grid, ramp
  * and Gaussian kernel; tlc_pi_raster stays the kernel of the one configuration the TLC-GNN pipeline uses.

@@ -303,9 +303,17 @@ def call(dataset, name, filt='degree', hks_time=10, mode='PI', num_models=5, gn=
     return total_time_PD, total_time_PI
 
 
-def evaluate_batch(model, samples):
+def _bottleneck_to_exact(pd_hat, edge_ptr, exact, exact_ptr):
+    """float64[n_kept]: d_B of every kept graph's predicted diagram (one point per edge) against its exact Ord0 ++ Ext1."""
+    from .. import ops
+    return ops.bottleneck_matching(edge_ptr, pd_hat.detach(), exact_ptr, exact)["dist"]
+
+
+def evaluate_batch(model, samples, bottleneck=False):
     """The forward-only loop of train_Teacher_Model_GC.evaluate_time (:118-143) as ONE block-diagonal PDGNN forward.
-    samples: list of 9-tuples / (None, None) as produced above; returns float32 CUDA [n_kept, 25] images + kept indices."""
+    samples: list of 9-tuples / (None, None) as produced above; returns float32 CUDA [n_kept, 25] images + kept indices.
+    bottleneck=True: a third value, float64 CUDA [n_kept]: the bottleneck distance of every kept graph's predicted diagram (the model's
+    point per edge) against its exact one (the sample's Ord0 ++ Ext1), `ops.bottleneck_matching`."""
     import torch
     xs, eis, gptr, eptr, kept = [], [], [0], [0], []
     for si, data in enumerate(samples):
@@ -319,15 +327,22 @@ def evaluate_batch(model, samples):
         eptr.append(eptr[-1] + ei.shape[1])
         kept.append(si)
     if not kept:
-        return torch.zeros(0, 25, device="cuda"), kept
+        empty = torch.zeros(0, 25, device="cuda")
+        return (empty, kept, torch.zeros(0, dtype=torch.float64, device="cuda")) if bottleneck else (empty, kept)
     n = gptr[-1]
     loops = torch.arange(n)
     edge_index = torch.cat([torch.cat(eis, dim=1), torch.stack([loops, loops])], dim=1).cuda()       # add_self_loops (:133)
     x = torch.from_numpy(np.concatenate(xs)).view(-1, 1).cuda()
+    edge_ptr = torch.tensor(eptr).cuda()
     with torch.no_grad():
-        _, img, *_ = model(x, edge_index, None, compute_loss=False, grad_PI=False, graph_ptr=torch.tensor(gptr).cuda(),
-                           edge_ptr=torch.tensor(eptr).cuda())
-    return img, kept
+        pd_hat, img, *_ = model(x, edge_index, None, compute_loss=False, grad_PI=False, graph_ptr=torch.tensor(gptr).cuda(),
+                                edge_ptr=edge_ptr)
+    if not bottleneck:
+        return img, kept
+    exact = [np.concatenate([np.asarray(samples[si][0], dtype=np.float64).reshape(-1, 2), np.asarray(samples[si][1], dtype=np.float64).reshape(-1, 2)])
+             for si in kept]
+    exact_ptr = np.concatenate([[0], np.cumsum([len(e) for e in exact])]).astype(np.int64)
+    return img, kept, _bottleneck_to_exact(pd_hat, edge_ptr, torch.from_numpy(np.concatenate(exact)).cuda(), torch.from_numpy(exact_ptr).cuda())
 
 
 # ---- the packed route: tensors in, tensors out, nothing per graph ---------------------------------------------------------------------
@@ -499,19 +514,28 @@ def call_packed(dataset, name, filt='degree', hks_time=10, gn=0, save_dir=None, 
     return 0, 0
 
 
-def evaluate_packed(model, gt):
+def evaluate_packed(model, gt, bottleneck=False):
     """`evaluate_batch` on a `PackedGroundTruth` without the per-sample loop: the block-diagonal edge_index (the real edges, then one self
     loop per node), x = f.float(), graph_ptr and edge_ptr straight from gt's tensors.  Returns float32 CUDA [n_kept, 25] images + kept
-    indices (one read: the ok flags)."""
+    indices (one read: the ok flags).  bottleneck=True: a third value, float64 CUDA [n_kept]: d_B of every kept graph's predicted diagram
+    against gt's exact Ord0 ++ Ext1, as `evaluate_batch` returns it."""
     import torch
     kept = torch.nonzero(gt.ok).flatten().tolist()
     if not kept:
-        return torch.zeros(0, 25, device="cuda"), kept
+        empty = torch.zeros(0, 25, device="cuda")
+        return (empty, kept, torch.zeros(0, dtype=torch.float64, device="cuda")) if bottleneck else (empty, kept)
     K = gt.f.numel()
     base = torch.repeat_interleave(gt.node_ptr[:-1], gt.edge_ptr[1:] - gt.edge_ptr[:-1], output_size=gt.edges.shape[0])
     loops = torch.arange(K, dtype=torch.int64, device=gt.f.device)
     edge_index = torch.cat([(gt.edges.to(torch.int64) + base[:, None]).t(), torch.stack([loops, loops])], dim=1)
     with torch.no_grad():
-        _, img, *_ = model(gt.f.float().view(-1, 1), edge_index, None, compute_loss=False, grad_PI=False, graph_ptr=gt.node_ptr,
-                           edge_ptr=gt.edge_ptr)
-    return img, kept
+        pd_hat, img, *_ = model(gt.f.float().view(-1, 1), edge_index, None, compute_loss=False, grad_PI=False, graph_ptr=gt.node_ptr,
+                                edge_ptr=gt.edge_ptr)
+    if not bottleneck:
+        return img, kept
+    # Ord0 ++ Ext1 per graph: two slots per graph in the concatenation of the two packed arrays
+    from ..autograd import pack_rows
+    starts = torch.stack([gt.o0[:-1], gt.o1[:-1] + gt.d0.shape[0]], 1).flatten()
+    cnt = torch.stack([gt.o0[1:] - gt.o0[:-1], gt.o1[1:] - gt.o1[:-1]], 1).flatten()
+    exact, offs = pack_rows(torch.cat([gt.d0, gt.d1]), starts, cnt)
+    return img, kept, _bottleneck_to_exact(pd_hat, gt.edge_ptr, exact, offs[::2].contiguous())

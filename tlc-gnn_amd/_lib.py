@@ -37,6 +37,7 @@ PD_WIDE_BLOCK, PD_WIDE_SORT_TILE, PD_WIDE_SCAN_CHUNK = 256, 4096, 2048   # workg
 PD_VERT_WAVE_NMAX, PD_VERT_LDS_NMAX = 64, 2048                       # TLC_PD_VERT_*: the size classes of csrc/pd_grad.hip (wavefront / workgroup per graph)
 SW_WAVE_NMAX, SW_LDS_NMAX, SW_MAX_DIRS = 64, 2048, 128              # TLC_SW_*: the size classes of csrc/sliced_w.hip by n + m, and the most directions
 W2_LDS_NMAX, W2_LARGE_NMAX, W2_LARGE_COUNTERS = 4096, 65536, 4       # TLC_W2_*: the rows the LDS matching kernels take, the workspace tier's cap, its counters per slot
+BN_WAVE_NMAX, BN_NMAX = 512, 4096                                   # TLC_BN_*: the size classes of csrc/bottleneck.hip by n + m (wavefront / workgroup per problem)
 PI_MAX_RES, PI_GRAD_WEIGHT, PI_GRAD_FULL = 128, 0, 1                # TLC_PI_*: the general imager of csrc/pi_general.hip
 PI_SLICE, PI_CHUNK, PI_GROUP = 1024, 32, 32                         # points per K-slice / per LDS chunk, K-split diagrams per launch
 DIST_WAVE_NMAX, DIST_WG_NMAX, DIST_WG_MMAX, DIST_WORK_FALLBACKS_OFF = 64, 2048, 4096, 64   # TLC_DIST_*: the size classes of csrc/dist_filt.hip
@@ -60,6 +61,7 @@ SYMBOLS = [
     "tlc_pd_grad_work_bytes", "tlc_pd_point_vertices", "tlc_pd_filtration_grad",
     "tlc_sliced_w_work_bytes", "tlc_sliced_wasserstein",
     "tlc_w2_large_work_bytes", "tlc_w2_large_matching",
+    "tlc_bottleneck_matching",
     "tlc_pi_image_work_bytes", "tlc_pi_image", "tlc_pi_image_vjp",
     "tlc_graph_components_work_bytes", "tlc_graph_components",
     "tlc_dist_filtration_work_bytes", "tlc_dist_filtration_vjp_work_bytes", "tlc_dist_filtration", "tlc_dist_filtration_vjp",
@@ -244,6 +246,7 @@ def lib():
         L.tlc_w2_large_work_bytes.argtypes, L.tlc_w2_large_work_bytes.restype = [C.c_int64, C.c_int32], C.c_int64
         L.tlc_w2_large_matching.argtypes = ([C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int32]
                                             + [C.c_void_p] * 9 + [C.c_int64, C.c_void_p])
+        L.tlc_bottleneck_matching.argtypes = [C.c_int32] + [C.c_void_p] * 4 + [C.c_int32] + [C.c_void_p] * 8
         L.tlc_pi_image_work_bytes.argtypes = [C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_int64)]
         L.tlc_pi_image_work_bytes.restype = C.c_int64
         L.tlc_pi_image.argtypes = ([C.c_int32, C.c_int64] + [C.c_void_p] * 4 + [C.c_int32, C.c_int32] + [C.c_void_p] * 4 + [C.c_int32, C.c_void_p,

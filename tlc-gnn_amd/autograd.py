@@ -4,7 +4,7 @@
 classifier of Knowledge_Distillation/ConvCurv_GIN.py: CurvConv and NcLinear (nc_curv.hip).
 
 torch.autograd only carries the graph: every forward and every backward below is one C-ABI call (`tlc_gat_layer_fwd/_bwd`,
-`tlc_edge_head_fwd/_bwd`, `tlc_w2_partial_matching`, `tlc_sliced_wasserstein`, `tlc_pi_raster` / `tlc_pi_raster_wgrad`, `tlc_pi_image` / `tlc_pi_image_vjp`, `tlc_hks_batch_dt` + `tlc_hks_large_batch_dt`) or a few (`tlc_gemm_f32` /
+`tlc_edge_head_fwd/_bwd`, `tlc_w2_partial_matching`, `tlc_sliced_wasserstein`, `tlc_bottleneck_matching`, `tlc_pi_raster` / `tlc_pi_raster_wgrad`, `tlc_pi_image` / `tlc_pi_image_vjp`, `tlc_hks_batch_dt` + `tlc_hks_large_batch_dt`) or a few (`tlc_gemm_f32` /
 `tlc_spmm_csr_f32` / `tlc_gemm_tn_f32`, `tlc_lp_decode_fused_f32` / `tlc_lp_decode_bwd_f32` / `tlc_lp_decode_bwd_pi_f32`, `tlc_segment_sum_f64`); nothing is recomputed with torch ops
 and there is no CPU path.
 """
@@ -112,6 +112,31 @@ class SlicedDiagramLoss(torch.autograd.Function):
                 per_point = torch.repeat_interleave(g64, offs[1:] - offs[:-1])   # d total / d loss[b] for each point of problem b
                 out[k] = (g * per_point.unsqueeze(1)).to(ctx.dtypes[k])
         return out[0], None, out[1], None, None, None
+
+
+class BottleneckLoss(torch.autograd.Function):
+    """The bottleneck distance of one or more (predicted, target) diagram pairs (include/tlcgnn.h defines it) -> d_B [B] in pd_hat's
+    dtype.  One `tlc_bottleneck_matching` call computes the distance and the gradients of both diagrams: +-1 or +-1/2 on the one point
+    of each diagram that the attaining pair names (`ops.bottleneck_matching`), a convention where the maximum is tied."""
+
+    @staticmethod
+    def forward(ctx, pd_hat, xoff, target, yoff):
+        r = ops.bottleneck_matching(xoff, pd_hat.detach(), yoff, target.detach(), want_grad=ctx.needs_input_grad[0],
+                                    grad_target=ctx.needs_input_grad[2])
+        ctx.save_for_backward(xoff, yoff, r["grad"], r["grad_target"])
+        ctx.dtypes = (pd_hat.dtype, target.dtype)
+        return r["dist"].to(pd_hat.dtype)
+
+    @staticmethod
+    def backward(ctx, gloss):
+        xoff, yoff, gx, gy = ctx.saved_tensors
+        g64 = gloss.to(torch.float64)
+        out = [None, None]
+        for k, (offs, g) in enumerate(((xoff, gx), (yoff, gy))):
+            if g is not None:
+                per_point = torch.repeat_interleave(g64, offs[1:] - offs[:-1])   # d total / d d_B[b] for each point of problem b
+                out[k] = (g * per_point.unsqueeze(1)).to(ctx.dtypes[k])
+        return out[0], None, out[1], None
 
 
 class DiagramImage(torch.autograd.Function):
@@ -397,6 +422,18 @@ def sliced_diagram_loss(pd_hat, target, M=50, xoff=None, yoff=None, dirs=None, s
     elif scale is None:
         raise ValueError("sliced_diagram_loss: dirs without a scale")
     return SlicedDiagramLoss.apply(pd_hat, xoff, target, yoff, dirs, float(scale))
+
+
+def bottleneck_loss(pd_hat, target, xoff=None, yoff=None):
+    """-> d_B [B]: the bottleneck distance between the diagrams pd_hat and target of every problem (both may use the diagonal; at most
+    4 096 points per pair).  Differentiable in pd_hat and, when it requires grad, in target: the gradient sits on the one pair that
+    attains the distance.  A pair above the cap or with a NaN / Inf coordinate raises RuntimeError."""
+    dev = pd_hat.device
+    if xoff is None:
+        xoff = torch.tensor([0, pd_hat.shape[0]], dtype=torch.int64, device=dev)
+    if yoff is None:
+        yoff = torch.tensor([0, target.shape[0]], dtype=torch.int64, device=dev)
+    return BottleneckLoss.apply(pd_hat, xoff, target, yoff)
 
 
 class GcnLayer(torch.autograd.Function):

@@ -806,6 +806,52 @@ def w2_large_matching(xoff, X, yoff, Y, order=2, infer=False, min_rows=0, want_g
                 grad=None if o["grad"] is None else o["grad"][:nx], status=o["status"][:B], work=work)
 
 
+_BN_STATUS = "2 = more than %d points in one pair (TLC_BN_NMAX, the cap of tlc_bottleneck_matching), 3 = NaN / Inf coordinates" % _lib.BN_NMAX
+
+
+@_lib.on_device_of
+def bottleneck_matching(xoff, X, yoff, Y, want_grad=False, grad_target=False, check=True):
+    """The bottleneck distance d_B (both diagrams may use the diagonal; include/tlcgnn.h defines it) for a batch of (predicted, target)
+    diagram pairs: xoff / yoff int64[B+1] offsets, X / Y float64[., 2] CUDA tensors; a pair holds at most _lib.BN_NMAX = 4 096 points.
+    -> dict(dist[B], arg int32[B, 2] (the pair that attains it, -1 = diagonal), assign_x[sum n], assign_y[sum m] (a matching that attains
+    it), grad[sum n, 2] or None (want_grad), grad_target[sum m, 2] or None (grad_target), status[B]).
+    A pair above the cap (status 2) or with a NaN / Inf coordinate (status 3) raises RuntimeError; check=False returns the statuses
+    instead (one host read less)."""
+    torch = _lib.require_gpu()
+    B = xoff.numel() - 1
+    dev = X.device
+    X = X.to(torch.float64).contiguous()
+    Y = Y.to(torch.float64).contiguous()
+    xoff = xoff.to(torch.int64).contiguous()
+    yoff = yoff.to(torch.int64).contiguous()
+    if yoff.numel() != xoff.numel():
+        raise ValueError("bottleneck_matching: xoff and yoff describe %d and %d problems" % (B, yoff.numel() - 1))
+    nx, ny = int(X.shape[0]), int(Y.shape[0])
+    max_points = 0
+    if B > 0:
+        # (offsets beyond the arrays would be read out of bounds on the device; one host read, with max_points)
+        ends = torch.stack([xoff[-1], yoff[-1], ((xoff[1:] - xoff[:-1]) + (yoff[1:] - yoff[:-1])).max()]).tolist()
+        if ends[0] > nx or ends[1] > ny:
+            raise ValueError("bottleneck_matching: offsets end at (%d, %d) but X / Y hold (%d, %d) points" % (ends[0], ends[1], nx, ny))
+        max_points = min(max(int(ends[2]), 0), 0x7fffffff)
+    dist = torch.zeros(max(B, 1), dtype=torch.float64, device=dev)
+    arg = torch.full((max(B, 1), 2), -1, dtype=torch.int32, device=dev)
+    ax = torch.full((max(nx, 1),), -1, dtype=torch.int32, device=dev)
+    ay = torch.full((max(ny, 1),), -1, dtype=torch.int32, device=dev)
+    gx = torch.zeros((max(nx, 1), 2), dtype=torch.float64, device=dev) if want_grad else None
+    gy = torch.zeros((max(ny, 1), 2), dtype=torch.float64, device=dev) if grad_target else None
+    status = torch.zeros(max(B, 1), dtype=torch.uint8, device=dev)
+    rc = _lib.lib().tlc_bottleneck_matching(C.c_int32(B), _lib.ptr(xoff), _lib.ptr(X) if nx else None, _lib.ptr(yoff), _lib.ptr(Y) if ny else None,
+                                            C.c_int32(max_points), _lib.ptr(dist), _lib.ptr(arg), _lib.ptr(ax), _lib.ptr(ay), _lib.ptr(gx),
+                                            _lib.ptr(gy), _lib.ptr(status), _lib.stream_ptr())
+    _lib.check(rc, "tlc_bottleneck_matching")
+    if check and B > 0 and bool((status[:B] != 0).any()):
+        bad = torch.nonzero(status[:B]).flatten()
+        raise RuntimeError("bottleneck_matching: problem %d has status %d (%s)" % (int(bad[0]), int(status[bad[0]]), _BN_STATUS))
+    return dict(dist=dist[:B], arg=arg[:B], assign_x=ax[:nx], assign_y=ay[:ny], grad=None if gx is None else gx[:nx],
+                grad_target=None if gy is None else gy[:ny], status=status[:B])
+
+
 def sliced_directions(M=50):
     """The directions and the step of the reference's sliced loss, exactly as Knowledge_Distillation/Teacher_model.py:117-124 makes
     them: theta starts at 0.5 and accumulates step = 1.0 / M; direction i is (float32(cos(theta pi)), float32(sin(theta pi))) -- the

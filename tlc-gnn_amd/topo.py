@@ -2,7 +2,7 @@
 function of the node values f, composed with the imager and the Wasserstein loss of `autograd`.
 
     f (an MLP on node features, an HKS time, ...)  ->  diagrams(f, ...)  ->  images(...) / wasserstein_to(...) /
-                                                       sliced_wasserstein_to(...)  ->  loss.backward()
+                                                       sliced_wasserstein_to(...) / bottleneck_to(...)  ->  loss.backward()
 
 `hks_filtration(time, ...)` is the second of these filtrations: the normalised heat-kernel signature as a differentiable function of its
 diffusion time (`autograd.hks_signature`: values and d / d t from tlc_hks_batch_dt and tlc_hks_large_batch_dt), so a time can be learned
@@ -119,6 +119,16 @@ def sliced_wasserstein_to(f, node_offs, edge_offs, edges, target_pts, target_off
     check_which(which)
     pts, offs = _select(f, node_offs, edge_offs, edges, which, pd_large)
     return autograd.sliced_diagram_loss(pts, target_pts.to(pts.dtype), M=M, xoff=offs, yoff=target_offs)
+
+
+def bottleneck_to(f, node_offs, edge_offs, edges, target_pts, target_offs, which="ord0+ext1", pd_large="host"):
+    """[B] bottleneck distances (`autograd.bottleneck_loss`: both diagrams may use the diagonal) between every graph's diagram `which` and
+    the target diagrams target_pts [sum k, 2] / target_offs int64[B + 1]; differentiable in f (and in target_pts when it requires grad).
+    The worst-point sibling of `wasserstein_to`: the gradient reaches the one or two node values behind the pair that attains the
+    distance.  A pair of more than 4 096 points in all raises RuntimeError."""
+    check_which(which)
+    pts, offs = _select(f, node_offs, edge_offs, edges, which, pd_large)
+    return autograd.bottleneck_loss(pts, target_pts.to(pts.dtype), xoff=offs, yoff=target_offs)
 
 
 # ---- the product's own images as a function of the GRAPH's curvature (DESIGN.md 6.11) ------------------------------------------------
