@@ -595,6 +595,101 @@ def test_matching_refuses_non_finite_points_and_too_many_points():
         ops.w2_partial_matching(xoff, Xc[:100], yoff, Yc, order=2)
 
 
+def test_matching_empty_diagrams_and_refusals_in_every_tier():
+    """The branches that csrc/w2_common.h defines once for the three tiers -- the wavefront kernel (N = 40), the workgroup kernel
+    (N = 600) and the workspace tier (N = 4 097, large='device') -- against numpy closed forms: the distance to the empty diagram with
+    its gradient (evaluation form, orders 1 and 2), a non-finite coordinate (status 3), n < m in the training form (status 1), more
+    points than the LDS kernels take without the workspace tier (status 2); a solved problem at either end of the batch gives the bits
+    it gives alone.  No problem above 40 rows is solved, so the batches cost no augmentation."""
+    import torch
+    from tlc_gnn_amd import ops
+    rs = np.random.RandomState(11)
+    tiers = (40, 600, 4097)
+
+    def diagram(n):
+        b = rs.rand(n)
+        P = np.stack([b, b + rs.uniform(-0.2, 0.7, size=n)], 1)           # some points below the diagonal
+        if n:
+            P[n // 2, 1] = P[n // 2, 0]                                   # and one on it: no gradient at p = 1
+        return P
+
+    def pack(ds):
+        off = np.concatenate([[0], np.cumsum([len(d) for d in ds])]).astype(np.int64)
+        return off, torch.as_tensor(off).cuda(), torch.as_tensor(np.concatenate(ds)).cuda()
+
+    def slices(r, off, b, keys):
+        return [r[k].cpu().numpy()[off[b]:off[b + 1]] for k in keys]
+
+    small = (diagram(5), diagram(4) + [0.0, 0.3])
+    # ---- evaluation form: per tier (N, 0), (0, N) and a pair with a NaN, between two copies of a small solved problem ------------
+    X, Y = [small[0]], [small[1]]
+    for N in tiers:
+        bad = diagram(N - 3)
+        bad[N // 3, 1] = np.nan
+        X += [diagram(N), np.zeros((0, 2)), bad]
+        Y += [np.zeros((0, 2)), diagram(N), diagram(3)]
+    X.append(small[0]); Y.append(small[1])
+    xo, xoff, Xc = pack(X)
+    yo, yoff, Yc = pack(Y)
+    s_off = [torch.as_tensor(np.array([0, len(d)], dtype=np.int64)).cuda() for d in small]
+    for order in (2, 1):
+        alone = ops.w2_inference_matching(s_off[0], torch.as_tensor(small[0]).cuda(), s_off[1], torch.as_tensor(small[1]).cuda(), order=order, want_grad=True)
+        assert alone["status"].tolist() == [0] and float(alone["loss"][0]) > 0
+        for large in ("device", "refuse"):
+            r = ops.w2_inference_matching(xoff, Xc, yoff, Yc, order=order, want_grad=True, large=large)
+            torch.cuda.synchronize()
+            parts = np.stack([r[k].cpu().numpy() for k in ("wxy", "wxd", "wyd")])
+            loss, status = r["loss"].cpu().numpy(), r["status"].cpu().tolist()
+            for b in (0, len(X) - 1):                                  # untouched by their neighbours: the bits of the problem alone
+                assert status[b] == 0 and loss[b] == float(alone["loss"][0]) and (parts[:, b] == [float(alone[k][0]) for k in ("wxy", "wxd", "wyd")]).all()
+                ax, g = slices(r, xo, b, ("assign_x", "grad"))
+                assert (ax == alone["assign_x"].cpu().numpy()).all() and (g == alone["grad"].cpu().numpy()).all()
+                assert (slices(r, yo, b, ("assign_y",))[0] == alone["assign_y"].cpu().numpy()).all()
+            for t, N in enumerate(tiers):
+                for b in (1 + 3 * t, 2 + 3 * t, 3 + 3 * t):
+                    ax, g = slices(r, xo, b, ("assign_x", "grad"))
+                    ay = slices(r, yo, b, ("assign_y",))[0]
+                    assert (ax == -1).all() and (ay == -1).all() and (parts[:, b] == 0.0).all(), (order, large, b)
+                    if N > 4096 and large == "refuse":                 # more than 4 096 points and no workspace tier
+                        assert status[b] == 2 and loss[b] == 0.0 and (g == 0.0).all(), (order, b)
+                    elif b == 3 + 3 * t:
+                        assert status[b] == 3 and np.isnan(loss[b]) and (g == 0.0).all(), (order, large, b)
+                    else:
+                        P = X[b] if len(X[b]) else Y[b]
+                        half = (P[:, 1] - P[:, 0]) * 0.5
+                        want = float((np.abs(half) ** order).sum() ** (1.0 / order))
+                        print("order %d %s N %d: loss %.17g, closed form %.17g" % (order, large, N, loss[b], want))
+                        assert status[b] == 0 and abs(loss[b] - want) <= 1e-12 * want, (order, large, b, loss[b], want)
+                        if len(X[b]):
+                            w = half / want if order == 2 else np.sign(half)
+                            assert np.abs(g - np.stack([-0.5 * w, 0.5 * w], 1)).max() <= 1e-12, (order, large, b)
+    # ---- training form: per tier n < m and a pair with an Inf --------------------------------------------------------------------
+    X, Y = [small[0]], [small[1]]
+    for N in tiers:
+        bad = diagram(N // 2)
+        bad[1, 0] = np.inf
+        X += [diagram(N), diagram(N)]
+        Y += [diagram(N + 1), bad]
+    X.append(small[0]); Y.append(small[1])
+    xo, xoff, Xc = pack(X)
+    yo, yoff, Yc = pack(Y)
+    alone = ops.w2_partial_matching(s_off[0], torch.as_tensor(small[0]).cuda(), s_off[1], torch.as_tensor(small[1]).cuda(), order=2)
+    assert alone["status"].tolist() == [0]
+    for large in ("device", "refuse"):
+        r = ops.w2_partial_matching(xoff, Xc, yoff, Yc, order=2, large=large)
+        torch.cuda.synchronize()
+        loss, status = r["loss"].cpu().numpy(), r["status"].cpu().tolist()
+        # (4 097 predicted points without the workspace tier: status 2, but n < m is told first)
+        assert status == [0, 1, 3, 1, 3, 1, 3 if large == "device" else 2, 0], (large, status)
+        for b in (0, len(X) - 1):
+            a, g = slices(r, xo, b, ("assign", "grad"))
+            assert loss[b] == float(alone["loss"][0]) and (a == alone["assign"].cpu().numpy()).all() and (g == alone["grad"].cpu().numpy()).all()
+        for b in range(1, len(X) - 1):
+            a, g = slices(r, xo, b, ("assign", "grad"))
+            assert (a == -1).all() and (g == 0.0).all() and float(r["wxy"][b]) == 0.0 and float(r["wxd"][b]) == 0.0, (large, b)
+            assert np.isnan(loss[b]) if status[b] == 3 else loss[b] == 0.0, (large, b)
+
+
 def test_teacher_evaluation_with_pair_diagonal_and_target_offsets():
     """The reference scores a trained model with pair_diagonal=True (train_Teacher_Model.py:99 -> Teacher_model.py:66 ->
     wasserstein_distance_inference): loss_0 and the three logged parts against the restatement on the predicted diagram.

@@ -49,24 +49,13 @@ __device__ __forceinline__ void bn_sync() {
     else __syncthreads();
 }
 
-__device__ __forceinline__ int bn_wave_min_i32(int v) {
-    int t;
-    t = (int)tlc_lane_xor_u32<1>((unsigned)v);  v = t < v ? t : v;
-    t = (int)tlc_lane_xor_u32<2>((unsigned)v);  v = t < v ? t : v;
-    t = (int)tlc_lane_xor_u32<4>((unsigned)v);  v = t < v ? t : v;
-    t = (int)tlc_lane_xor_u32<8>((unsigned)v);  v = t < v ? t : v;
-    t = (int)tlc_lane_xor_u32<16>((unsigned)v); v = t < v ? t : v;
-    t = (int)tlc_lane_xor_u32<32>((unsigned)v); v = t < v ? t : v;
-    return v;
-}
-
 // The least (MAX: the greatest) val over the threads and, among the threads that hold it, the least code; every thread gets both.
 // T > 64: through row `slot` (0 / 1, alternating between consecutive calls) of red / redi, ONE barrier: a thread that writes row s again
 // has passed the barrier of the call in between, which every reader of row s reaches only after its reads.
 template <int T, bool MAX>
 __device__ __forceinline__ void bn_select(double& val, int& code, double* red, int* redi, int slot) {
     const double w = MAX ? tlc_wave_max_f64(val) : tlc_wave_min_f64(val);
-    const int c = bn_wave_min_i32(val == w ? code : BN_NONE);
+    const int c = tlc_wave_min_i32(val == w ? code : BN_NONE);
     if (T == 64) { val = w; code = c; return; }
     constexpr int NWV = T / 64;
     const int wave = (int)threadIdx.x >> 6;

@@ -116,6 +116,16 @@ __device__ __forceinline__ int tlc_wave_sum_i32(int v) {
     v += (int)tlc_lane_xor_u32<32>((unsigned)v);
     return v;
 }
+__device__ __forceinline__ int tlc_wave_min_i32(int v) {
+    int t;
+    t = (int)tlc_lane_xor_u32<1>((unsigned)v);  v = t < v ? t : v;
+    t = (int)tlc_lane_xor_u32<2>((unsigned)v);  v = t < v ? t : v;
+    t = (int)tlc_lane_xor_u32<4>((unsigned)v);  v = t < v ? t : v;
+    t = (int)tlc_lane_xor_u32<8>((unsigned)v);  v = t < v ? t : v;
+    t = (int)tlc_lane_xor_u32<16>((unsigned)v); v = t < v ? t : v;
+    t = (int)tlc_lane_xor_u32<32>((unsigned)v); v = t < v ? t : v;
+    return v;
+}
 __device__ __forceinline__ long long tlc_wave_sum_i64(long long v) {
     v += (long long)tlc_lane_xor_u64<1>((unsigned long long)v);
     v += (long long)tlc_lane_xor_u64<2>((unsigned long long)v);

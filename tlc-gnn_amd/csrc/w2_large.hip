@@ -2,8 +2,9 @@
 // (tlc_w2_large_matching).  The reference trains and evaluates with this loss up to 30 000 points
 // (train_Teacher_Model.py:46-48, "ot.emd cannot compute loss for large graph" only beyond).
 //
-// The same problem, costs, tie rule and outputs as w2_match.hip (its header comment defines them): the assignment of N rows onto N
-// columns by shortest augmenting paths, every cost recomputed from the two points, no matrix.  What differs:
+// The same problem, costs and outputs as w2_match.hip (its header comment defines them; the code of all three is w2_common.h's): the
+// assignment of N rows onto N columns by shortest augmenting paths, every cost recomputed from the two points, no matrix.  Among
+// several columns at a step's minimum the lowest one is taken (w2l_argmin), the rule of w2_match.hip's workgroup kernel.  What differs:
 //   * the O(N) state (row duals u, column duals v, path lengths minv, column -> row map pcol, path links way, used marks) lies in a
 //     slot of the caller's workspace (TlcW2LargeScratch), 34 B per row: 2.2 MB at the cap, resident in L2.  One workgroup of 1 024
 //     threads per slot; thread t owns the columns t, t + 1 024, ...: v, minv, way and the used mark of a column are only ever touched by
@@ -19,66 +20,25 @@
 #include <vector>
 
 #include "scratch_layouts.h"
-#include "tlc_common.h"
+#include "w2_common.h"
 
 namespace {
 
 constexpr int W2L_THREADS = 1024, W2L_NWV = W2L_THREADS / 64, W2L_NONE = 0x7fffffff;
 
-struct W2LargeParams {
+struct W2LargeParams : W2Problem {
     int n_problems;
-    const long long* xoff;
-    const double* X;
-    const long long* yoff;
-    const double* Y;
-    int order;
     long long min_rows;        // problems of at most this many rows are left alone
-    double* loss;
-    double* wxy;
-    double* wxd;
-    double* wyd;               // INFER only
-    int* assign;               // [sum n]
-    int* assign_y;             // INFER only, [sum m]
-    double* gradX;             // or null
-    unsigned char* status;
     char* work;
     TlcW2LargeScratch L;       // the slot's layout (offsets in bytes)
 };
-
-__device__ __forceinline__ double w2l_pow(double d, int order) { return order == 2 ? d * d : d; }
-
-// what w2_fail of w2_match.hip writes: the outputs of a problem that is not solved (or of one against the empty diagram)
-template <bool INFER>
-__device__ __forceinline__ void w2l_fail(const W2LargeParams& p, int b, long long x0, long long y0, long long n, long long m, int code,
-                                         double lossv, int tid) {
-    if (tid == 0) {
-        p.status[b] = (unsigned char)code; p.loss[b] = lossv; p.wxy[b] = 0.0; p.wxd[b] = 0.0;
-        if (INFER) p.wyd[b] = 0.0;
-    }
-    for (long long i = tid; i < n; i += W2L_THREADS) {
-        p.assign[x0 + i] = -1;
-        if (p.gradX) { p.gradX[2 * (x0 + i)] = 0.0; p.gradX[2 * (x0 + i) + 1] = 0.0; }
-    }
-    if (INFER) for (long long j = tid; j < m; j += W2L_THREADS) p.assign_y[y0 + j] = -1;
-}
-
-__device__ __forceinline__ int w2l_wave_min_i32(int v) {
-    int t;
-    t = (int)tlc_lane_xor_u32<1>((unsigned)v);  v = t < v ? t : v;
-    t = (int)tlc_lane_xor_u32<2>((unsigned)v);  v = t < v ? t : v;
-    t = (int)tlc_lane_xor_u32<4>((unsigned)v);  v = t < v ? t : v;
-    t = (int)tlc_lane_xor_u32<8>((unsigned)v);  v = t < v ? t : v;
-    t = (int)tlc_lane_xor_u32<16>((unsigned)v); v = t < v ? t : v;
-    t = (int)tlc_lane_xor_u32<32>((unsigned)v); v = t < v ? t : v;
-    return v;
-}
 
 // The least (val, j) of the workgroup in lexicographic order, threads without a candidate pass j < 0; -> j = W2L_NONE when nobody has
 // one.  One barrier: the buffers alternate (par), and a wavefront can only reach the call after next, which writes this call's buffer
 // again, through the next call's barrier -- behind every other wavefront's reads of this one.
 __device__ __forceinline__ void w2l_argmin(double& val, int& j, double (*red)[W2L_NWV], int (*redj)[W2L_NWV], int& par, int lane, int wave) {
     const double wmin = tlc_wave_min_f64(j >= 0 ? val : __longlong_as_double(0x7FF0000000000000ll));
-    const int cand = w2l_wave_min_i32((j >= 0 && val == wmin) ? j : W2L_NONE);
+    const int cand = tlc_wave_min_i32((j >= 0 && val == wmin) ? j : W2L_NONE);
     if (lane == 0) { red[par][wave] = wmin; redj[par][wave] = cand; }
     __syncthreads();
     double d = red[par][0];
@@ -93,20 +53,6 @@ __device__ __forceinline__ void w2l_argmin(double& val, int& j, double (*red)[W2
     val = d; j = jj;
 }
 
-// the sum of the workgroup: the butterfly inside each wavefront, then the wavefronts ascending (buf: [W2L_NWV])
-__device__ __forceinline__ double w2l_sum(double s, double* buf, int lane, int wave) {
-    for (int o = 32; o; o >>= 1) s += __shfl_xor(s, o);
-    __syncthreads();
-    if (lane == 0) buf[wave] = s;
-    __syncthreads();
-    double t = 0.0;
-    for (int k = 0; k < W2L_NWV; ++k) t += buf[k];
-    return t;
-}
-
-// INFER = false: n rows (predicted) onto m targets + (n - m) diagonal copies.  INFER = true: N = n + m rows (predicted, then m
-// diagonal rows) onto N columns (targets, then n diagonal columns).  cost(i, j):
-//     i < n, j < m: ||X_i - Y_j||_inf ^ p      i < n, j >= m: cxd_i      i >= n, j < m: cdy_j      i >= n, j >= m: 0
 template <bool INFER>
 __global__ __launch_bounds__(W2L_THREADS) void tlc_w2_large_kernel(W2LargeParams p) {
     __shared__ double red[2][W2L_NWV];
@@ -138,43 +84,16 @@ __global__ __launch_bounds__(W2L_THREADS) void tlc_w2_large_kernel(W2LargeParams
         if ((!INFER && nn < mm) || NN > p.L.rows) {
             // (n < m: the diagonal would need negative mass, wasserstein.py:264.  p.L.rows: the host sized the slots for the largest
             // problem up to TlcW2LargeScratch::NMAX rows, so only a problem above the cap is beyond it)
-            w2l_fail<INFER>(p, b, x0, y0, nn, mm, (!INFER && nn < mm) ? 1 : 2, 0.0, tid);
+            w2_fail<INFER, W>(p, b, x0, y0, nn, mm, (!INFER && nn < mm) ? 1 : 2, 0.0, tid);
             continue;
         }
         const int n = (int)nn, m = (int)mm, N = (int)NN;
-        if (INFER && (n == 0 || m == 0)) {
-            // empty diagram(s) (:98-113): distance to the empty diagram, the parts are reported as 0
-            const double* P = n ? p.X : p.Y;
-            const long long o = n ? x0 : y0;
-            const int cnt = n ? n : m;
-            double s = 0.0;
-            for (int i = tid; i < cnt; i += W) {
-                const double d = fabs((P[2 * (o + i) + 1] - P[2 * (o + i)]) * 0.5);
-                s += p.order == 2 ? d * d : d;
-            }
-            const double t = w2l_sum(s, sumbuf, lane, wave);
-            const double Lv = p.order == 2 ? sqrt(t) : t;
-            w2l_fail<INFER>(p, b, x0, y0, n, m, 0, Lv, tid);
-            if (p.gradX)
-                for (int i = tid; i < n; i += W) {
-                    const double sd = (p.X[2 * (x0 + i) + 1] - p.X[2 * (x0 + i)]) * 0.5;
-                    const double w = p.order == 2 ? (Lv > 0.0 ? sd / Lv : 0.0) : (sd > 0.0 ? 1.0 : (sd < 0.0 ? -1.0 : 0.0));
-                    p.gradX[2 * (x0 + i)] = -0.5 * w; p.gradX[2 * (x0 + i) + 1] = 0.5 * w;
-                }
-            continue;
-        }
+        if (INFER && (n == 0 || m == 0)) { w2_empty<W>(p, b, x0, y0, n, m, sumbuf, tid); continue; }
         bool finite = true;
-        for (int i = tid; i < n; i += W) {
-            const double bx = p.X[2 * (x0 + i)], by = p.X[2 * (x0 + i) + 1];
-            finite = finite && (bx - bx == 0.0) && (by - by == 0.0);
-        }
-        for (int j = tid; j < m; j += W) {
-            const double bx = p.Y[2 * (y0 + j)], by = p.Y[2 * (y0 + j) + 1];
-            finite = finite && (bx - bx == 0.0) && (by - by == 0.0);
-        }
+        for (int i = tid; i < n; i += W) finite = finite && w2_finite(p.X[2 * (x0 + i)], p.X[2 * (x0 + i) + 1]);
+        for (int j = tid; j < m; j += W) finite = finite && w2_finite(p.Y[2 * (y0 + j)], p.Y[2 * (y0 + j) + 1]);
         if (__syncthreads_or(!finite)) {
-            // NaN / Inf coordinates: every reduced cost would be NaN and no column would ever be the minimum
-            w2l_fail<INFER>(p, b, x0, y0, n, m, 3, QNAN, tid);
+            w2_fail<INFER, W>(p, b, x0, y0, n, m, 3, QNAN, tid);
             continue;
         }
         // a row's own values (uniform: every thread loads the same words) and the cost of (row, column) from the two points
@@ -183,19 +102,14 @@ __global__ __launch_bounds__(W2L_THREADS) void tlc_w2_large_kernel(W2LargeParams
             Row r;
             r.real = !INFER || i < n;
             r.x = r.y = r.cd = 0.0;
-            if (r.real) { r.x = p.X[2 * (x0 + i)]; r.y = p.X[2 * (x0 + i) + 1]; r.cd = w2l_pow((r.y - r.x) * 0.5, p.order); }
+            if (r.real) { r.x = p.X[2 * (x0 + i)]; r.y = p.X[2 * (x0 + i) + 1]; r.cd = w2_pow((r.y - r.x) * 0.5, p.order); }
             return r;
         };
+        auto cost_at = [&](const Row& r, bool target, double yx, double yy) -> double {      // (yx, yy) = Y_j, loaded where j < m
+            return w2_cost<INFER>(r.real, r.x, r.y, r.cd, target, yx, yy, w2_pow((yy - yx) * 0.5, p.order), p.order);
+        };
         auto cost_of = [&](const Row& r, int j) -> double {
-            if (j < m) {
-                const double yx = p.Y[2 * (y0 + j)], yy = p.Y[2 * (y0 + j) + 1];
-                if (r.real) {
-                    const double dx = fabs(r.x - yx), dy = fabs(r.y - yy);
-                    return w2l_pow(dx > dy ? dx : dy, p.order);            // chebyshev ^ order (:59-60)
-                }
-                return w2l_pow((yy - yx) * 0.5, p.order);
-            }
-            return r.real ? r.cd : 0.0;
+            return j < m ? cost_at(r, true, p.Y[2 * (y0 + j)], p.Y[2 * (y0 + j) + 1]) : cost_at(r, false, 0.0, 0.0);
         };
         // ---- the start, 1: u_i = min_j c(i, j), a thread per row.  The columns from m on all cost a row the same.
         for (int i = tid; i < N; i += W) {
@@ -210,20 +124,13 @@ __global__ __launch_bounds__(W2L_THREADS) void tlc_w2_large_kernel(W2LargeParams
         for (int j = tid; j < m; j += W) {
             const double yx = p.Y[2 * (y0 + j)], yy = p.Y[2 * (y0 + j) + 1];
             double best = INF;
-            for (int i = 0; i < n; ++i) {
-                const double dx = fabs(p.X[2 * (x0 + i)] - yx), dy = fabs(p.X[2 * (x0 + i) + 1] - yy);
-                const double c = w2l_pow(dx > dy ? dx : dy, p.order) - u[i];
-                best = c < best ? c : best;
-            }
-            if (INFER) { const double c = w2l_pow((yy - yx) * 0.5, p.order) - u[n]; best = c < best ? c : best; }
+            for (int i = 0; i < n; ++i) { const double c = cost_at(row_of(i), true, yx, yy) - u[i]; best = c < best ? c : best; }
+            if (INFER) { const double c = cost_at(row_of(n), true, yx, yy) - u[n]; best = c < best ? c : best; }
             v[j] = best;
         }
         if (N > m) {
             double best = INF;
-            for (int i = tid; i < n; i += W) {
-                const double c = w2l_pow((p.X[2 * (x0 + i) + 1] - p.X[2 * (x0 + i)]) * 0.5, p.order) - u[i];
-                best = c < best ? c : best;
-            }
+            for (int i = tid; i < n; i += W) { const double c = cost_at(row_of(i), false, 0.0, 0.0) - u[i]; best = c < best ? c : best; }
             if (INFER && tid == 0) { const double c = 0.0 - u[n]; best = c < best ? c : best; }
             int any = 0;
             w2l_argmin(best, any, red, redj, par, lane, wave);
@@ -276,12 +183,14 @@ __global__ __launch_bounds__(W2L_THREADS) void tlc_w2_large_kernel(W2LargeParams
                     for (int k = 0; k < 4; ++k) {
                         const int j = jb + k * W;
                         if (us[k]) continue;
-                        double c;                                     // (cost_of on the loaded point)
+                        // (w2_cost on the loaded point, written out: through cost_at this loop measured 1 % slower in the
+                        // evaluation form, 5 408 against 5 352 ms at 2 049 + 2 048 points; like this 5 369)
+                        double c;
                         if (j < m) {
                             if (r.real) {
                                 const double dx = fabs(r.x - yx[k]), dy = fabs(r.y - yy[k]);
-                                c = w2l_pow(dx > dy ? dx : dy, p.order);
-                            } else c = w2l_pow((yy[k] - yx[k]) * 0.5, p.order);
+                                c = w2_pow(dx > dy ? dx : dy, p.order);
+                            } else c = w2_pow((yy[k] - yx[k]) * 0.5, p.order);
                         } else c = r.real ? r.cd : 0.0;
                         const double cur = dist + ((c - ui) - vj[k]);
                         if (cur < mv[k]) { mv[k] = cur; minv[j] = cur; way[j] = j0; }
@@ -321,64 +230,26 @@ __global__ __launch_bounds__(W2L_THREADS) void tlc_w2_large_kernel(W2LargeParams
             __syncthreads();
         }
         if (failed) {
-            w2l_fail<INFER>(p, b, x0, y0, n, m, 3, QNAN, tid);
+            w2_fail<INFER, W>(p, b, x0, y0, n, m, 3, QNAN, tid);
             __syncthreads();
             continue;
         }
-        // ---- the loss and its pieces (:303-372 / :140-195): matched distances d_k, loss = (sum |d_k|^p)^(1/p) -------------------
-        double sxy = 0.0, sxd = 0.0, syd = 0.0;
+        // ---- the loss, its parts and the maps, then d loss / d X, from the finished matching: a thread's own columns ------------------
+        W2Sums sums;
         for (int j = tid; j < N; j += W) {
             const int i = pcol[j];
-            if (i < n) {
-                const double xi = p.X[2 * (x0 + i)], yi = p.X[2 * (x0 + i) + 1];
-                if (j < m) {
-                    const double dx = fabs(xi - p.Y[2 * (y0 + j)]), dy = fabs(yi - p.Y[2 * (y0 + j) + 1]);
-                    const double d = dx > dy ? dx : dy;
-                    sxy += p.order == 2 ? d * d : d;
-                    p.assign[x0 + i] = j;
-                    if (INFER) p.assign_y[y0 + j] = i;
-                } else {
-                    const double d = fabs((yi - xi) * 0.5);
-                    sxd += p.order == 2 ? d * d : d;
-                    p.assign[x0 + i] = -1;
-                }
-            } else if (j < m) {                                       // (INFER) a target sent to the diagonal
-                const double d = fabs((p.Y[2 * (y0 + j) + 1] - p.Y[2 * (y0 + j)]) * 0.5);
-                syd += p.order == 2 ? d * d : d;
-                p.assign_y[y0 + j] = -1;
-            }
+            const Row r = row_of(i);
+            const double yx = j < m ? p.Y[2 * (y0 + j)] : 0.0, yy = j < m ? p.Y[2 * (y0 + j) + 1] : 0.0;
+            sums = w2_pair_loss<INFER>(p, x0, y0, n, m, i, j, r.x, r.y, yx, yy, sums);
         }
-        sxy = w2l_sum(sxy, sumbuf, lane, wave);
-        sxd = w2l_sum(sxd, sumbuf, lane, wave);
-        if (INFER) syd = w2l_sum(syd, sumbuf, lane, wave);
-        const double tot = sxy + sxd + syd;
-        const double Lv = p.order == 2 ? sqrt(tot) : tot;
-        if (tid == 0) {
-            p.status[b] = 0;
-            p.loss[b] = Lv;
-            p.wxy[b] = p.order == 2 ? sqrt(sxy) : sxy;
-            p.wxd[b] = p.order == 2 ? sqrt(sxd) : sxd;
-            if (INFER) p.wyd[b] = p.order == 2 ? sqrt(syd) : syd;
-        }
-        // ---- d loss / d X: through the matched distances only (the matching is piecewise constant) ----------------------------
+        const double Lv = w2_finish<INFER, W>(p, b, sums, sumbuf, tid);
         if (p.gradX) {
             for (int j = tid; j < N; j += W) {
                 const int i = pcol[j];
                 if (i >= n) continue;
-                const double xi = p.X[2 * (x0 + i)], yi = p.X[2 * (x0 + i) + 1];
-                double gx = 0.0, gy = 0.0;
-                if (j < m) {
-                    const double ex = p.Y[2 * (y0 + j)] - xi, ey = p.Y[2 * (y0 + j) + 1] - yi;          // Y - X (:311)
-                    const double ax = fabs(ex), ay = fabs(ey);
-                    const double d = ax > ay ? ax : ay;
-                    const double w = p.order == 2 ? (Lv > 0.0 ? d / Lv : 0.0) : 1.0;                     // dL/dd
-                    if (ax >= ay) gx = -w * (ex > 0.0 ? 1.0 : (ex < 0.0 ? -1.0 : 0.0));
-                    else gy = -w * (ey > 0.0 ? 1.0 : (ey < 0.0 ? -1.0 : 0.0));
-                } else {
-                    const double s = (yi - xi) * 0.5;                                                    // signed distance to the diagonal
-                    const double w = p.order == 2 ? (Lv > 0.0 ? s / Lv : 0.0) : (s > 0.0 ? 1.0 : (s < 0.0 ? -1.0 : 0.0));
-                    gx = -0.5 * w; gy = 0.5 * w;
-                }
+                const double yx = j < m ? p.Y[2 * (y0 + j)] : 0.0, yy = j < m ? p.Y[2 * (y0 + j) + 1] : 0.0;
+                double gx, gy;
+                w2_pair_grad(p.order, Lv, j < m, p.X[2 * (x0 + i)], p.X[2 * (x0 + i) + 1], yx, yy, gx, gy);
                 p.gradX[2 * (x0 + i)] = gx;
                 p.gradX[2 * (x0 + i) + 1] = gy;
             }
