@@ -1268,6 +1268,60 @@ int tlc_lp_decode_bwd_pi_f32(int64_t n_pairs, const int32_t* d_pairs, const floa
                              int32_t emb_dim, const float* d_pi, int32_t pi_dim, const float* d_W1, const float* d_b1, const float* d_W2,
                              const float* d_b2, const float* d_gprob, float* d_gpi, void* stream);
 
+/* ---- The sum-aggregating baselines of the PDGNN teacher (Knowledge_Distillation/Teacher_model.py:148-175,202-208: GINConv, GCNConv,
+ * SAGEConv), one layer form (csrc/gnn_layers.hip) on any CSR BY TARGET, block-diagonal or one big graph:
+ *   agg_i = sum over the in-edges e of i of coef[e] * x_src[e], + self_scale * x_i     z_i = Wa agg_i + Ws x_i + b     y_i = act(z_i)
+ *   GIN: the edge list as given, coef NULL, self_scale 1 (eps = 0), Wa = nn.0.weight, b = nn.0.bias, ReLU or none;
+ *   GCN: tlc_gcn_norm_csr's operator and values, self_scale 0, Wa = weight^T, b = bias;
+ *   SAGE (PyG 1.6.1): coef = 1 / max(in-degree of the target, 1), self_scale 0, Wa = lin_l.weight, Ws = lin_r.weight, b = lin_l.bias.
+ * d_rowptr int32[n + 1], d_src int32[rowptr[n]] (not read, and may be NULL, when every row is empty), d_coef f32[rowptr[n]] or NULL (all 1), d_X f32[n, c_in], d_Wa f32[c_out, c_in], d_Ws
+ * the same or NULL, d_bias f32[c_out] or NULL, act: TLC_GNN_ACT_NONE / _RELU / _PRELU (slope > 0 then, else ignored), d_out f32[n, c_out],
+ * d_agg f32[n, c_in] or NULL: the aggregate, kept for the backward.
+ * Order of operations, all in f32.  Per element k of a row: acc = +0; for the row's entries e ascending: acc = acc + (coef[e] * x_src[e][k])
+ * (the product rounded first; coef NULL: acc + x_src[e][k]); then, with self_scale != 0, acc = acc + (self_scale * x_i[k]).  The projection
+ * is the f32 MFMA's (v_mfma_f32_16x16x4f32) from a zero accumulator: the four-wide steps {16 q + e, 16 q + 4 + e, 16 q + 8 + e, 16 q + 12 + e}
+ * of k for q ascending and e = 0 .. 3 inside, k padded with zeros to a multiple of 16, first all of Wa agg, then all of Ws x; then + b,
+ * then the activation.  No atomics; a row of d_out / d_agg depends on that row's entries alone: the same bits from run to run and for a
+ * graph alone or anywhere in any batch.  A source id outside 0 .. n - 1 makes its row NaN and reads nothing.
+ * c_in in 1 .. 64 and c_out in {8, 16, 32, 64}, else TLC_ERR_UNSUPPORTED; null required pointers, n_nodes < 0, an unknown act or PReLU with
+ * a slope <= 0: TLC_ERR_INVALID_ARG; nothing is written in either case.  n_nodes == 0: TLC_OK. */
+#define TLC_GNN_ACT_NONE   0
+#define TLC_GNN_ACT_RELU   1
+#define TLC_GNN_ACT_PRELU  2
+int tlc_gnn_layer_fwd(int32_t n_nodes, const int32_t* d_rowptr, const int32_t* d_src, const float* d_coef, float self_scale,
+                      const float* d_X, int32_t c_in, int32_t c_out, const float* d_Wa, const float* d_Ws, const float* d_bias,
+                      int32_t act, float slope, float* d_out, float* d_agg, void* stream);
+
+/* Gradients of tlc_gnn_layer_fwd.  dZ = d_gout * act'(d_out) (read off the sign of the output: 1 above 0; at and below it 0 for ReLU and
+ * `slope` for PReLU, as torch does);  G = dZ Wa;  gX = S^T G + self_scale G + dZ Ws;  gWa = dZ^T agg;  gWs = dZ^T X;  gb = colsum dZ.
+ * S^T comes in as a second CSR, BY SOURCE (d_rowptr_t int32[n + 1], d_col_t = the targets, d_coef_t = the forward's coefficient of the
+ * same edge or NULL; for GCN tlc_gcn_norm_csr_t), so the scatter towards the sources is a gather: gX[i][k] = acc after acc = +0; for row
+ * i's entries e ascending: acc = acc + (coef_t[e] * G[col_t[e]][k]); with self_scale != 0: acc = acc + (self_scale * G[i][k]); with Ws:
+ * acc = acc + (dZ Ws)[i][k].  G and dZ Ws are f32 MFMA products as in the forward.  The weight gradients are tlc_gemm_tn_f32 products over
+ * the materialised dZ: split-K partials over a partition that n_nodes and the widths alone fix, added in split order.  No floating-point
+ * atomics anywhere: every output is the same bits from run to run, and a graph's rows of gX the same alone or in any batch.
+ * d_agg: the forward's; d_out: read only with an activation; d_X: read only for d_gWs.  d_gX f32[n, c_in] or NULL (first layer: neither
+ * G nor the CSR by source is touched); d_gWa f32[c_out, c_in]; d_gWs the same or NULL; d_gb f32[c_out] or NULL.
+ * d_work: tlc_gnn_layer_bwd_work_bytes(n_nodes, c_in, c_out) bytes (-1 for a negative size), 16-byte aligned.  Refusals as the forward's,
+ * and TLC_ERR_INVALID_ARG for a d_work too small or misaligned.  n_nodes == 0: the weight gradients are zeros. */
+int64_t tlc_gnn_layer_bwd_work_bytes(int32_t n_nodes, int32_t c_in, int32_t c_out);
+int tlc_gnn_layer_bwd(int32_t n_nodes, const int32_t* d_rowptr_t, const int32_t* d_col_t, const float* d_coef_t, float self_scale,
+                      const float* d_X, const float* d_agg, const float* d_out, const float* d_gout, int32_t c_in, int32_t c_out,
+                      const float* d_Wa, const float* d_Ws, int32_t act, float slope, float* d_gX, float* d_gWa, float* d_gWs,
+                      float* d_gb, void* d_work, int64_t work_bytes, void* stream);
+
+/* The inference forward of Base_Model's four layers (Teacher_model.py:213-241: conv1 -> conv2 -> conv4 -> conv3, in_dim 1, hidden 32) in
+ * ONE launch on a batch cut into self-contained tiles (d_tile_ptr int32[n_tiles + 1] of tlc_gat_tile_cut: at most 192 nodes, no edge
+ * crosses a cut): a workgroup keeps a tile's node rows in LDS through the four layers, so the intermediate rows never reach HBM.
+ * d_x f32[n_nodes]; params: HOST array of 12 device pointers, per layer in the order above {Wa f32[32, c_in], Ws or NULL, bias or NULL},
+ * Ws on all four layers or on none; acts / slopes: HOST int32[4] / float[4]; d_out f32[n_nodes, 32].  The layers run the device code of
+ * tlc_gnn_layer_fwd operation for operation: the rows equal, bit for bit, those of four tlc_gnn_layer_fwd calls.  A caller-made cut with
+ * an empty tile, one above 192 rows or one outside the batch gets NaN rows.  hidden != 32: TLC_ERR_UNSUPPORTED; n_tiles == 0: TLC_OK,
+ * nothing written (no cut, e.g. one big graph: run the layers one by one). */
+int tlc_gnn_stack_fwd(int32_t n_nodes, const int32_t* d_rowptr, const int32_t* d_src, const float* d_coef, float self_scale,
+                      int32_t n_tiles, const int32_t* d_tile_ptr, const float* d_x, int32_t hidden, const float* const* params,
+                      const int32_t* acts, const float* slopes, float* d_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,4 +1,5 @@
-"""Drop-in for the reference's Knowledge_Distillation/Teacher_model.py (PDGNN), type='GAT'.
+"""Drop-in for the reference's Knowledge_Distillation/Teacher_model.py (PDGNN): type='GAT' (the PDGNN layer) and the message-passing
+baselines it is compared against, type='GIN' (the reference's default for Teacher_Model), 'GCN' (its default for Base_Model) and 'SAGE'.
 
   Teacher_Model.__init__ :21-44, forward :46-104 (grad_PI=False: :53-59, :83-84), compute_PD_loss :106-137 (kernel='wasserstein'),
   Base_Model.__init__ :146-211 (GAT branch :182-189), Base_Model.forward :213-229.
@@ -22,6 +23,14 @@ training script passes False, train_Teacher_Model.py:51): the image of the diffe
 Evaluation (train_Teacher_Model.py:85-113: `model(filt, edge_index, PD, p=p, kernel=kernel, pair_diagonal=True, grad_PI=False)`):
 pair_diagonal=True -> compute_PD_loss(type='inference') :66,134-136 -> `wasserstein_distance_inference` (wasserstein.py:93-195)
 -> `tlc_w2_inference_matching`; loss_yd0 is then the targets left to the diagonal.
+
+The baselines (Base_Model.__init__ :148-175,202-208, forward :213-241; gnn_layers.py): one fused HIP layer for the three types
+(`tlc_gnn_layer_fwd`, backward `tlc_gnn_layer_bwd` without atomics); without gradients and dropout the four layers of a batch of small
+graphs run as ONE launch (`tlc_gnn_stack_fwd`), then the edge head and the imager as for 'GAT'.  The GIN branch has no PReLU between its
+layers (:233-241); the other types have F.prelu(0.1) behind conv1, conv2 and conv4.  conv5 (and SAGE's BN) are constructed and unused, as
+in the reference.  Parameter names and initialisations are PyG 1.6.1's as far as SURVEY.md 8(c) records them: torch_geometric is not
+installed where this was written and the reference ships no checkpoint, so this boundary is UNPINNED (gnn_layers.py).  type='PDGNN'
+(PD_conv.py's per-edge MLP message) and 'GAT_original' are not implemented and raise.
 """
 import time
 
@@ -30,19 +39,46 @@ import torch.nn.functional as F
 from torch.nn import Linear
 
 from .. import ops, engine, autograd
+from torch.nn import BatchNorm1d, ReLU, Sequential
+
 from .gat_conv import GATConv, GraphBatch
+from .gnn_layers import GCNConv, GINConv, SAGEConv, GnnBatch
+
+BASELINES = ('GIN', 'GCN', 'SAGE')
 
 
 class Base_Model(torch.nn.Module):
     def __init__(self, in_dim=1, hidden_dim=32, dropout=0.2, type='GCN', out_dim=2, new_node_feat=True, use_edge_attn=True):
         super(Base_Model, self).__init__()
-        if type != 'GAT':
-            raise NotImplementedError("Base_Model (HIP): only type='GAT' (the PDGNN layer) is implemented")
-        self.conv1 = GATConv(in_dim, hidden_dim, concat=False, new_node_feat=new_node_feat, use_edge_attn=use_edge_attn)
-        self.conv2 = GATConv(hidden_dim, hidden_dim, double_input=True, concat=False, new_node_feat=new_node_feat, use_edge_attn=use_edge_attn)
-        self.conv3 = GATConv(hidden_dim, int(out_dim / 2), double_input=True, concat=False, new_node_feat=new_node_feat, use_edge_attn=use_edge_attn)
-        self.conv4 = GATConv(hidden_dim, hidden_dim, double_input=True, concat=False, new_node_feat=new_node_feat, use_edge_attn=use_edge_attn)
-        self.conv5 = GATConv(hidden_dim, hidden_dim, double_input=True, concat=False, new_node_feat=new_node_feat, use_edge_attn=use_edge_attn)
+        if type != 'GAT' and type not in BASELINES:
+            raise NotImplementedError("Base_Model (HIP): type %r is not implemented; implemented are 'GAT' (the PDGNN layer) and the "
+                                      "baselines 'GIN', 'GCN', 'SAGE'" % (type,))
+        if type == 'GCN':                                                                          # :148-153
+            self.conv1 = GCNConv(in_dim, hidden_dim)
+            self.conv2 = GCNConv(hidden_dim, hidden_dim)
+            self.conv3 = GCNConv(hidden_dim, out_dim)
+            self.conv4 = GCNConv(hidden_dim, hidden_dim)
+            self.conv5 = GCNConv(hidden_dim, hidden_dim)
+        elif type == 'GIN':                                                                        # :162-175
+            self.conv1 = GINConv(Sequential(Linear(in_dim, hidden_dim), ReLU()))
+            self.conv2 = GINConv(Sequential(Linear(hidden_dim, hidden_dim), ReLU()))
+            self.conv3 = GINConv(Sequential(Linear(hidden_dim, out_dim)))
+            self.conv4 = GINConv(Sequential(Linear(hidden_dim, hidden_dim), ReLU()))
+            self.conv5 = GINConv(Sequential(Linear(hidden_dim, hidden_dim), ReLU()))
+        elif type == 'SAGE':                                                                       # :202-208
+            self.conv1 = SAGEConv(in_dim, hidden_dim)
+            self.conv2 = SAGEConv(hidden_dim, hidden_dim)
+            self.conv3 = SAGEConv(hidden_dim, out_dim)
+            self.conv4 = SAGEConv(hidden_dim, hidden_dim)
+            self.conv5 = SAGEConv(hidden_dim, hidden_dim)
+            self.BN = BatchNorm1d(hidden_dim)
+        else:
+            self.conv1 = GATConv(in_dim, hidden_dim, concat=False, new_node_feat=new_node_feat, use_edge_attn=use_edge_attn)
+            self.conv2 = GATConv(hidden_dim, hidden_dim, double_input=True, concat=False, new_node_feat=new_node_feat, use_edge_attn=use_edge_attn)
+            self.conv3 = GATConv(hidden_dim, int(out_dim / 2), double_input=True, concat=False, new_node_feat=new_node_feat, use_edge_attn=use_edge_attn)
+            self.conv4 = GATConv(hidden_dim, hidden_dim, double_input=True, concat=False, new_node_feat=new_node_feat, use_edge_attn=use_edge_attn)
+            self.conv5 = GATConv(hidden_dim, hidden_dim, double_input=True, concat=False, new_node_feat=new_node_feat, use_edge_attn=use_edge_attn)
+        self.hidden_dim = hidden_dim
         self.dropout = dropout
         self.type = type
         self.out_dim = out_dim
@@ -55,6 +91,8 @@ class Base_Model(torch.nn.Module):
         # F.dropout of :218-227 (train mode only): on the input and behind the prelu of conv1 / conv2 / conv4.  torch's own op, at the
         # same points and on tensors of the same shapes as the reference, so the same seed draws the same masks
         drop = (lambda t: F.dropout(t, p=self.dropout, training=True)) if (self.training and self.dropout > 0) else (lambda t: t)
+        if self.type in BASELINES:
+            return self._forward_baseline(x, edge_index, csr, drop)
         if csr is None:
             csr = GraphBatch(edge_index, x.shape[0])                   # one CSR (and tile cut) for the four layers of THIS call
         elif isinstance(csr, GraphBatch):
@@ -62,6 +100,29 @@ class Base_Model(torch.nn.Module):
         x = self.conv1(drop(x), edge_index, prelu_slope=0.1, csr=csr)  # conv -> F.prelu(0.1) fused (:218-219)
         x = self.conv2(drop(x), edge_index, prelu_slope=0.1, csr=csr)
         x = self.conv4(drop(x), edge_index, prelu_slope=0.1, csr=csr)
+        x = self.conv3(drop(x), edge_index, csr=csr)
+        return x
+
+
+    def _forward_baseline(self, x, edge_index, csr, drop):
+        """:213-241 for 'GIN' / 'GCN' / 'SAGE': F.dropout in front of every layer (train mode only), F.prelu(0.1) behind conv1 / conv2 /
+        conv4 except in the GIN branch.  csr: a `GnnBatch` of this edge_index and type held by the caller; default: built here."""
+        if csr is None:
+            csr = GnnBatch(edge_index, x.shape[0], self.type)
+        elif isinstance(csr, GnnBatch):
+            csr.check(edge_index, x.shape[0], self.type)
+        else:
+            raise TypeError("Base_Model (HIP): type %r takes csr=GnnBatch(edge_index, n, %r)" % (self.type, self.type))
+        slope = -1.0 if self.type == 'GIN' else 0.1
+        convs = (self.conv1, self.conv2, self.conv4, self.conv3)
+        wants_grad = torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for c in convs for p in c.parameters()))
+        if not wants_grad and not (self.training and self.dropout > 0) and x.is_cuda and x.dtype == torch.float32 \
+                and self.out_dim == self.hidden_dim and ops.gnn_stack_ok(x.shape[1], self.hidden_dim, csr.tiles):
+            layers = [c.layer(s) for c, s in zip(convs, (slope, slope, slope, -1.0))]
+            return ops.gnn_stack(csr.rowptr, csr.src, csr.coef, csr.self_scale, csr.tiles, x, layers)   # the four layers, one launch
+        x = self.conv1(drop(x), edge_index, prelu_slope=slope, csr=csr)
+        x = self.conv2(drop(x), edge_index, prelu_slope=slope, csr=csr)
+        x = self.conv4(drop(x), edge_index, prelu_slope=slope, csr=csr)
         x = self.conv3(drop(x), edge_index, csr=csr)
         return x
 
@@ -91,7 +152,7 @@ class Teacher_Model(torch.nn.Module):
     def _one_call_ok(self, x0, csr):
         """tlc_pdgnn_forward serves the reference's configuration (in_dim 1, hidden 32, float32) when no gradient is wanted and no
         dropout is drawn; everything else takes the layer-by-layer path below."""
-        if not x0.is_cuda or x0.dim() != 2 or x0.shape[1] != 1 or x0.shape[0] == 0 or self.lin5.out_features != 32 \
+        if self.DIM0_Model.type != 'GAT' or not x0.is_cuda or x0.dim() != 2 or x0.shape[1] != 1 or x0.shape[0] == 0 or self.lin5.out_features != 32 \
                 or self.DIM0_Model.conv1.out_channels != 32 or self.DIM0_Model.conv3.out_channels != 16 or self.lin5.weight.dtype != torch.float32 \
                 or (self.training and self.dropout > 0) or not (csr is None or isinstance(csr, GraphBatch)):
             return False
@@ -112,7 +173,8 @@ class Teacher_Model(torch.nn.Module):
         non-self-loop edges) to get one image per graph [B,25]; otherwise one image [25] for the whole input.  With a loss,
         pd_ptr (int64 [B+1]) gives the rows of PD that belong to each graph; without it every graph must have exactly as
         many target points as edges (PD = Ord0 + Ext1 of the same graph: n - 1 + m - n + 1 = m points, data_utils_GC.py:166).
-        csr: a `GraphBatch(edge_index0, n)` the caller built once for this batch (else the CSR by target is built per call).
+        csr: a `GraphBatch(edge_index0, n)` -- for the baselines a `GnnBatch(edge_index0, n, type)` -- the caller built once for this
+        batch (else the CSR by target is built per call).
         w2_large (kernel='wasserstein'): 'refuse' raises for a graph whose matching has more than 4 096 rows, 'device' matches up to
         65 536 in the workspace tier (`ops.w2_large_matching`), the range in which the reference still trains with this loss.
         """
@@ -143,7 +205,7 @@ class Teacher_Model(torch.nn.Module):
         x = self.DIM0_Model(x0, edge_index0, csr=csr)
         n = x0.shape[0]
         m = edge_index0.shape[1] - n
-        if isinstance(csr, GraphBatch):
+        if isinstance(csr, (GraphBatch, GnnBatch)):
             src, dst = csr.edge_ends(m)                               # (int32 copies made once per batch, like its CSR)
         else:
             src = edge_index0[0, :m].to(torch.int32).contiguous()     # strips the appended self loops (:54-55)

@@ -49,6 +49,27 @@ class EdgeHead(torch.autograd.Function):
         return gx, gw5, gb5, gw6, gb6, None, None, None
 
 
+class GnnLayer(torch.autograd.Function):
+    """One layer of the teacher's GIN / GCN / SAGE baselines (Teacher_model.py:148-175,202-208) with the activation that follows it:
+    `tlc_gnn_layer_fwd`, and `tlc_gnn_layer_bwd` on the structure's transpose (no atomics).  `batch`: a gnn_layers.GnnBatch."""
+
+    @staticmethod
+    def forward(ctx, x, wa, ws, bias, batch, act, slope):
+        out, agg = ops.gnn_layer(batch.rowptr, batch.src, batch.coef, batch.self_scale, x, wa, ws, bias, act, slope, want_agg=True)
+        ctx.save_for_backward(x, agg, out, wa, ws)
+        ctx.batch, ctx.act, ctx.slope, ctx.has_bias = batch, act, slope, bias is not None
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        x, agg, out, wa, ws = ctx.saved_tensors
+        b = ctx.batch
+        rowptr_t, col_t, coef_t = b.transpose() if ctx.needs_input_grad[0] else (None, None, None)
+        gx, gwa, gws, gb = ops.gnn_layer_bwd(rowptr_t, col_t, coef_t, b.self_scale, x, agg, out, gout.contiguous(), wa, ws, ctx.has_bias,
+                                             ctx.act, ctx.slope, need_gx=ctx.needs_input_grad[0])
+        return gx, gwa, gws, gb, None, None, None
+
+
 _W2_STATUS = "1 = fewer predicted than target points, 2 = too many points for one problem (%s), 3 = NaN / Inf coordinates"
 _W2_CAP = {"refuse": "4096; large='device' takes up to 65536", "device": "65536"}
 
@@ -386,6 +407,10 @@ def diagram_image(pd_hat, offs=None, res=5, imager=None, grad='weight'):
 
 def gat_layer(x, wl, att, wij, bias, rowptr, src, prelu_slope=-1.0):
     return GatLayer.apply(x, wl, att, wij, bias, rowptr, src, float(prelu_slope))
+
+
+def gnn_layer(x, wa, ws, bias, batch, act=None, slope=0.0):
+    return GnnLayer.apply(x, wa, ws, bias, batch, act, slope)
 
 
 def edge_head(x, w5, b5, w6, b6, src, dst, prelu_slope):

@@ -97,6 +97,16 @@ struct TlcEdgeHeadBwdScratch {
         : hbuf(n_edges * 2 * c), gpre(hbuf + n_edges * hidden), total(gpre + n_edges * hidden) {}
 };
 
+// tlc_gnn_layer_bwd (gnn_layers.hip).  In floats, every array on a multiple of four: dZ [n][c_out] | G = dZ Wa [n][c_in] | H = dZ Ws
+// [n][c_in] | the split-K partials of its tlc_gemm_tn_f32 products (gWa and gWs [c_out][c_in], gb [1][c_out]) one after the other in the
+// same room.  tlc_gnn_layer_bwd_work_bytes returns `total` in BYTES (the entry takes work_bytes and checks it).
+struct TlcGnnLayerBwdScratch {
+    int64_t dz = 0, g, h, tn, total;
+    TlcGnnLayerBwdScratch(int64_t n, int64_t c_in, int64_t c_out)
+        : g(tlc_up4(n * c_out)), h(g + tlc_up4(n * c_in)), tn(h + tlc_up4(n * c_in)),
+          total(tn + std::max(TlcGemmTnScratch(c_out, c_in).total, TlcGemmTnScratch(1, c_out).total)) {}
+};
+
 // tlc_graph_components (gc_prep.hip).  In BYTES, every array on a multiple of 256: the control words [HEAD bytes] | the WAVE class's
 // graph list int[B] | and, only when the batch can hold a WIDE graph (total_nodes > wave_nmax): per graph the class byte u8[B], the
 // winner u64[B], the component count int[B], the first sorted key int[B]; per node the label u32[N], the component size int[N], the

@@ -637,6 +637,92 @@ def edge_head_bwd(src, dst, x, w5, b5, prelu_slope, w6, gpd):
     return gx, gw5, gb5, gw6, gb6
 
 
+# ---- the sum-aggregating baselines of the PDGNN teacher (gnn_layers.hip; autograd.GnnLayer; Knowledge_Distillation/gnn_layers.py) ----
+GNN_ACTS = {None: _lib.GNN_ACT_NONE, "none": _lib.GNN_ACT_NONE, "relu": _lib.GNN_ACT_RELU, "prelu": _lib.GNN_ACT_PRELU}
+
+
+def _opt_f32(t):
+    return None if t is None else _f32(t)
+
+
+@_lib.on_device_of
+def gnn_layer(rowptr, src, coef, self_scale, x, wa, ws=None, bias=None, act=None, slope=0.0, want_agg=False, out=None):
+    """One layer of the teacher's GIN / GCN / SAGE baselines (tlc_gnn_layer_fwd) on a CSR by target:
+    y = act(Wa (sum_e coef[e] x_src[e] + self_scale x_i) + Ws x_i + b).  coef None: all 1; act None / 'relu' / 'prelu' (slope).
+    -> out f32 [n, c_out], or (out, agg f32 [n, c_in]) with want_agg (the aggregate the backward reads)."""
+    torch = _lib.require_gpu()
+    x = _f32(x)
+    n, c_in = x.shape
+    c_out = wa.shape[0]
+    if out is None:
+        out = torch.empty((n, c_out), dtype=torch.float32, device=x.device)
+    agg = torch.empty((n, c_in), dtype=torch.float32, device=x.device) if want_agg else None
+    keep = (_f32(wa), _opt_f32(ws), _opt_f32(bias), _opt_f32(coef))
+    rc = _lib.lib().tlc_gnn_layer_fwd(C.c_int32(n), _lib.ptr(rowptr), _lib.ptr(src), _lib.ptr(keep[3]), C.c_float(self_scale), _lib.ptr(x),
+                                      C.c_int32(c_in), C.c_int32(c_out), _lib.ptr(keep[0]), _lib.ptr(keep[1]), _lib.ptr(keep[2]),
+                                      C.c_int32(GNN_ACTS[act]), C.c_float(slope), _lib.ptr(out), _lib.ptr(agg), _lib.stream_ptr())
+    _lib.check(rc, "tlc_gnn_layer_fwd")
+    return (out, agg) if want_agg else out
+
+
+@_lib.on_device_of
+def gnn_layer_bwd(rowptr_t, col_t, coef_t, self_scale, x, agg, out, gout, wa, ws=None, has_bias=True, act=None, slope=0.0, need_gx=True):
+    """Gradients of `gnn_layer` (tlc_gnn_layer_bwd; no atomics): -> (gX or None, gWa, gWs or None, gb or None).  rowptr_t / col_t /
+    coef_t: the structure's transpose as a CSR by source (GnnBatch holds it); x, agg, out: the forward's input, aggregate and output."""
+    torch = _lib.require_gpu()
+    x, gout = _f32(x), _f32(gout)
+    n, c_in = x.shape
+    c_out = wa.shape[0]
+    dev = x.device
+    gx = torch.empty((n, c_in), dtype=torch.float32, device=dev) if need_gx else None
+    gwa = torch.empty((c_out, c_in), dtype=torch.float32, device=dev)
+    gws = torch.empty((c_out, c_in), dtype=torch.float32, device=dev) if ws is not None else None
+    gb = torch.empty(c_out, dtype=torch.float32, device=dev) if has_bias else None
+    L = _lib.lib()
+    nbytes = int(L.tlc_gnn_layer_bwd_work_bytes(C.c_int32(n), C.c_int32(c_in), C.c_int32(c_out)))
+    if nbytes < 0:
+        raise ValueError("gnn_layer_bwd: negative size")
+    work = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    keep = (_f32(wa), _opt_f32(ws), _opt_f32(coef_t), _f32(agg), _f32(out))
+    rc = L.tlc_gnn_layer_bwd(C.c_int32(n), _lib.ptr(rowptr_t), _lib.ptr(col_t), _lib.ptr(keep[2]), C.c_float(self_scale), _lib.ptr(x),
+                             _lib.ptr(keep[3]), _lib.ptr(keep[4]), _lib.ptr(gout), C.c_int32(c_in), C.c_int32(c_out), _lib.ptr(keep[0]),
+                             _lib.ptr(keep[1]), C.c_int32(GNN_ACTS[act]), C.c_float(slope), _lib.ptr(gx), _lib.ptr(gwa), _lib.ptr(gws),
+                             _lib.ptr(gb), _lib.ptr(work), C.c_int64(nbytes), _lib.stream_ptr())
+    _lib.check(rc, "tlc_gnn_layer_bwd")
+    return gx, gwa, gws, gb
+
+
+def gnn_stack_ok(c_in, hidden, tiles):
+    """Whether `gnn_stack` takes the batch: the reference's widths (in_dim 1, hidden 32) and a tile cut (ops.gat_tiles; None for a batch
+    without close enough cuts, e.g. one big graph).  Everything else runs layer by layer (`gnn_layer`), with the same bits."""
+    return int(c_in) == 1 and int(hidden) == 32 and tiles is not None and tiles.numel() >= 2
+
+
+@_lib.on_device_of
+def gnn_stack(rowptr, src, coef, self_scale, tiles, x, layers, out=None):
+    """conv1 -> conv2 -> conv4 -> conv3 of Base_Model.forward (Teacher_model.py:213-241) without gradients in ONE launch
+    (tlc_gnn_stack_fwd): x f32 [n, 1]; layers: four (wa, ws or None, bias or None, act, slope) in that order -> f32 [n, 32]."""
+    torch = _lib.require_gpu()
+    x = _f32(x).reshape(-1)
+    n = x.shape[0]
+    hidden = layers[0][0].shape[0]
+    if out is None:
+        out = torch.empty((n, hidden), dtype=torch.float32, device=x.device)
+    keep, ptrs = [_opt_f32(coef)], []
+    for wa, ws, b, _a, _s in layers:
+        for t in (wa, ws, b):
+            keep.append(_opt_f32(t))
+            ptrs.append(None if t is None else keep[-1].data_ptr())
+    arr = (C.c_void_p * 12)(*ptrs)
+    acts = (C.c_int32 * 4)(*[GNN_ACTS[l[3]] for l in layers])
+    slopes = (C.c_float * 4)(*[float(l[4]) for l in layers])
+    rc = _lib.lib().tlc_gnn_stack_fwd(C.c_int32(n), _lib.ptr(rowptr), _lib.ptr(src), _lib.ptr(keep[0]), C.c_float(self_scale),
+                                      C.c_int32(tiles.numel() - 1), _lib.ptr(tiles), _lib.ptr(x), C.c_int32(hidden), arr, acts, slopes,
+                                      _lib.ptr(out), _lib.stream_ptr())
+    _lib.check(rc, "tlc_gnn_stack_fwd")
+    return out
+
+
 REDUCE = {"add": 0, "sum": 0, "mean": 1, "min": 2, "max": 3}
 
 
