@@ -1322,6 +1322,63 @@ int tlc_gnn_stack_fwd(int32_t n_nodes, const int32_t* d_rowptr, const int32_t* d
                       int32_t n_tiles, const int32_t* d_tile_ptr, const float* d_x, int32_t hidden, const float* const* params,
                       const int32_t* acts, const float* slopes, float* d_out, void* stream);
 
+/* ---- The PDGNN layer family (csrc/msg_layers.hip): Knowledge_Distillation/gat_conv.py:113-216 with its ablation switches (new_node_feat
+ * :78-79,193-195; use_edge_attn :197-200) and PD_conv.py's PDConv (:179-219), on any CSR BY TARGET with the self loops added
+ * (tlc_csr_by_target).  Per entry e = (j -> i) of row i:
+ *   x_l = X Wl^T     alpha = x_l . att     P = x_l Wij[:, :C]^T     Q = x_l Wij[:, C:]^T                      (C = c_out)
+ *   h_e = leaky_relu(P_i + Q_j, 0.2) with TLC_MSG_NODE_FEAT, else x_l[j]
+ *   a_e = softmax over row i of leaky_relu(alpha_j + alpha_i, 0.2) with TLC_MSG_EDGE_ATTN, else 1           m_e = a_e * h_e
+ *   out_i = [ sum_e m_e || min_e m_e + max_e m_e ] + bias  (TLC_MSG_AGG_SUM_MINMAX, gat_conv.py:216)
+ *   out_i = [ sum_e m_e || min_e m_e             ] + bias  (TLC_MSG_AGG_SUM_MIN,    PD_conv.py:219), then PReLU when prelu_slope >= 0.
+ * Operands as tlc_gat_layer_fwd's: d_Wl f32[C, c_in], d_att f32[C] (may be NULL without EDGE_ATTN), d_Wij f32[C, 2C] (may be NULL without
+ * NODE_FEAT), d_bias f32[2C], d_out f32[n, 2C].  d_work: tlc_msg_layer_fwd_work_bytes(n_nodes, c_in, c_out, mode) bytes (-1 for a negative
+ * size or unknown mode bits), 16-byte aligned: x_l, alpha, P and Q of the call.
+ * Order of operations, all in f32, every product rounded before it is added.  x_l, P and Q are f32 MFMA products (v_mfma_f32_16x16x4f32)
+ * from a zero accumulator: the four-wide steps {16 q + e, 16 q + 4 + e, 16 q + 8 + e, 16 q + 12 + e} of k for q ascending and e = 0 .. 3
+ * inside, k padded with zeros to a multiple of 16.  alpha_i: four chains from +0 over k = 16 q + 4 g + e (q, then e ascending), g = 0 .. 3,
+ * then (g + (g ^ 1)) + the other pair.  A row's softmax: logits leaky_relu(alpha_j + alpha_i); maximum exact; the exponentials
+ * __expf(logit - maximum) are summed in C chains (chain c takes the row's entries c, c + C, ...; from +0, ascending) that meet in a
+ * butterfly over c ^ C/2, ..., c ^ 1; denominator = that + 1e-16 (PyG's softmax); a_e = exponential / denominator.  Per channel: sum = +0,
+ * then + m_e for the row's entries ascending; min / max exact.  An empty row (possible through this ABI only) has sum 0 and min = max = 0
+ * (torch_scatter's value), so out_i = bias.  No atomics; a row's bits depend on that row's entries alone: the same from run to run and for a
+ * graph alone or anywhere in any batch.  A source id outside 0 .. n - 1 makes its row NaN and reads nothing.
+ * c_in in 1 .. 64 and c_out in {8, 16, 32, 64}, else TLC_ERR_UNSUPPORTED; null required pointers, n_nodes < 0, unknown mode / agg bits, a
+ * d_work too small or misaligned: TLC_ERR_INVALID_ARG; nothing is written in either case.  n_nodes == 0: TLC_OK. */
+#define TLC_MSG_NODE_FEAT      1
+#define TLC_MSG_EDGE_ATTN      2
+#define TLC_MSG_AGG_SUM_MINMAX 0
+#define TLC_MSG_AGG_SUM_MIN    1
+int64_t tlc_msg_layer_fwd_work_bytes(int32_t n_nodes, int32_t c_in, int32_t c_out, int32_t mode);
+int tlc_msg_layer_fwd(int32_t n_nodes, const int32_t* d_rowptr, const int32_t* d_src, const float* d_X, int32_t c_in, int32_t c_out,
+                      const float* d_Wl, const float* d_att, const float* d_Wij, const float* d_bias, int32_t mode, int32_t agg,
+                      float prelu_slope, void* d_work, int64_t work_bytes, float* d_out, void* stream);
+
+/* Gradients of tlc_msg_layer_fwd, WITHOUT floating-point atomics.  Nothing of the forward is kept: the node rows are recomputed.
+ * d_rowptr_t / d_col_t / d_pos_t: the same structure as a CSR BY SOURCE -- row j lists the entries (j -> i) as d_col_t = i and d_pos_t =
+ * the entry's position in d_src, positions ascending inside a row -- so that the adjoint of "gather from the sources" is a second gather.
+ * Pass 1, per target row: Gz = d_gout * PReLU'(d_out) (`slope` at d_out <= 0, as torch); the row's softmax statistics; per channel the
+ * FIRST entry of the row attaining the minimum / the maximum (strict comparisons in entry order -- tlc_gat_layer_bwd's convention; torch
+ * splits the gradient of a tie evenly instead, which differs per entry but not per tensor when the tying entries share both ends, as
+ * repeated edges do); with gm_e = Gz_sum + Gz_mm ([e is arg-min] + [e is arg-max]) per channel: S_i = sum_e (sum_c gm_e m_e), the logit
+ * gradient gt_e = ((sum_c gm_e m_e) - a_e S_i) leaky'(alpha_j + alpha_i), gP_i = sum_e gm_e a_e leaky'(P_i + Q_j), and the target side of
+ * galpha_i = sum_e gt_e.  It keeps per row: gP, that sum, the maximum, the denominator, S and the arg entries; nothing per entry.
+ * Pass 2, per source row: every entry's a_e, m_e, gm_e and gt_e again from those; gQ_j = sum_e gm_e a_e leaky'(.), galpha_j = (sum_e gt_e) +
+ * the target side.  Every sum over entries: +0, then the row's entries ascending; every sum over channels: a butterfly over c ^ C/2, ...,
+ * c ^ 1.  Then gx_l = gP Wij[:, :C] + gQ Wij[:, C:] + galpha (x) att (MFMA products as above, the rank-one term added last; without
+ * NODE_FEAT gx_l = gQ + galpha (x) att), gX = gx_l Wl, and the weight gradients gWl = gx_l^T X, gWij = [gP^T x_l | gQ^T x_l], gatt =
+ * galpha^T x_l, gbias = column sums of Gz as tlc_gemm_tn_f32 products: split-K partials over a partition that n_nodes and the widths alone
+ * fix, added in split order.  Every output is the same bits from run to run, and a graph's rows of d_gX the same alone or in any batch.
+ * d_out: read only with prelu_slope >= 0.  d_gX f32[n, c_in] or NULL (first layer: the last product is left out; the source pass still
+ * runs, because the weight gradients need gQ and galpha).  d_gWl f32[C, c_in], d_gbias f32[2C]; d_gatt f32[C] is written only with
+ * EDGE_ATTN, d_gWij f32[C, 2C] only with NODE_FEAT (either may be NULL otherwise).
+ * d_work: tlc_msg_layer_bwd_work_bytes(n_nodes, n_entries, c_in, c_out, mode) bytes, 16-byte aligned; it does not grow with n_entries.
+ * Refusals as the forward's.  n_nodes == 0: TLC_OK, the weight gradients are zeros. */
+int64_t tlc_msg_layer_bwd_work_bytes(int32_t n_nodes, int64_t n_entries, int32_t c_in, int32_t c_out, int32_t mode);
+int tlc_msg_layer_bwd(int32_t n_nodes, const int32_t* d_rowptr, const int32_t* d_src, const int32_t* d_rowptr_t, const int32_t* d_col_t,
+                      const int32_t* d_pos_t, const float* d_X, int32_t c_in, int32_t c_out, const float* d_Wl, const float* d_att,
+                      const float* d_Wij, int32_t mode, int32_t agg, float prelu_slope, const float* d_out, const float* d_gout,
+                      float* d_gX, float* d_gWl, float* d_gatt, float* d_gWij, float* d_gbias, void* d_work, int64_t work_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -29,8 +29,15 @@ The baselines (Base_Model.__init__ :148-175,202-208, forward :213-241; gnn_layer
 graphs run as ONE launch (`tlc_gnn_stack_fwd`), then the edge head and the imager as for 'GAT'.  The GIN branch has no PReLU between its
 layers (:233-241); the other types have F.prelu(0.1) behind conv1, conv2 and conv4.  conv5 (and SAGE's BN) are constructed and unused, as
 in the reference.  Parameter names and initialisations are PyG 1.6.1's as far as SURVEY.md 8(c) records them: torch_geometric is not
-installed where this was written and the reference ships no checkpoint, so this boundary is UNPINNED (gnn_layers.py).  type='PDGNN'
-(PD_conv.py's per-edge MLP message) and 'GAT_original' are not implemented and raise.
+installed where this was written and the reference ships no checkpoint, so this boundary is UNPINNED (gnn_layers.py).
+
+The ablations of the training scripts (train_Teacher_Model.py:169-170: new_node_feat, use_edge_attn) go through type='GAT': every layer
+is built with the two flags (:185-189), and the three configurations with a flag off run on the layer family of csrc/msg_layers.hip
+(`tlc_msg_layer_fwd`, and `tlc_msg_layer_bwd` without floating-point atomics; gat_conv.py).  The one-call inference forward
+(`tlc_pdgnn_forward`) serves the full configuration only -- it reads every layer's lin_ij -- so an ablated model runs layer by layer.
+PD_conv.py's PDConv, the layer behind the reference's type='PDGNN' (:177-181), exists as a layer module (Knowledge_Distillation/PD_conv.py,
+the same family with sum || min).  The `type` strings 'PDGNN' and 'GAT_original' themselves keep raising: the baselines' tests pin that
+refusal, so a PDGNN stack is built from PDConv layers by hand until a change lifts it.
 """
 import time
 
@@ -152,6 +159,9 @@ class Teacher_Model(torch.nn.Module):
     def _one_call_ok(self, x0, csr):
         """tlc_pdgnn_forward serves the reference's configuration (in_dim 1, hidden 32, float32) when no gradient is wanted and no
         dropout is drawn; everything else takes the layer-by-layer path below."""
+        c1 = getattr(self.DIM0_Model, 'conv1', None)
+        if self.DIM0_Model.type == 'GAT' and not (c1.new_node_feat and c1.use_edge_attn):
+            return False                                              # (_one_call_params reads lin_ij and att_l of every layer)
         if self.DIM0_Model.type != 'GAT' or not x0.is_cuda or x0.dim() != 2 or x0.shape[1] != 1 or x0.shape[0] == 0 or self.lin5.out_features != 32 \
                 or self.DIM0_Model.conv1.out_channels != 32 or self.DIM0_Model.conv3.out_channels != 16 or self.lin5.weight.dtype != torch.float32 \
                 or (self.training and self.dropout > 0) or not (csr is None or isinstance(csr, GraphBatch)):

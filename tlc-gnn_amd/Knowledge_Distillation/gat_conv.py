@@ -3,8 +3,14 @@
   GATConv.__init__ :62-104, forward :113-181, message :183-200, aggregate :202-216.
 
 Tensor input, heads=1, new_node_feat=True, use_edge_attn=True, add_self_loops=True (what Teacher_model.py:182-189 builds)
-run as two HIP kernels behind `tlc_gat_layer_fwd` (include/tlcgnn.h); other configurations raise.  With gradients enabled and
-an input or parameter that requires them the call goes through `autograd.GatLayer`, whose backward is `tlc_gat_layer_bwd`.
+run as two HIP kernels behind `tlc_gat_layer_fwd` (include/tlcgnn.h).  With gradients enabled and an input or parameter that
+requires them the call goes through `autograd.GatLayer`, whose backward is `tlc_gat_layer_bwd`.
+
+The ablations (new_node_feat=False: no per-edge linear layer, :78-79,193-195; use_edge_attn=False: the messages are not scaled by the
+attention, :197-200; or both) run on the layer family of csrc/msg_layers.hip: `tlc_msg_layer_fwd`, and through `autograd.MsgLayer`
+`tlc_msg_layer_bwd`, a backward without floating-point atomics.  Parameters as in the reference: no `lin_ij` without new_node_feat;
+`att_l` / `att_r` always (without use_edge_attn they take no part in the output and get no gradient).  Heads > 1, concat=True, attention
+dropout in train mode and tuple input raise.
 """
 import math
 
@@ -33,7 +39,14 @@ class GraphBatch:
     def __init__(self, edge_index, n, tiled=True):
         self.edge_index, self.n, self.version = edge_index, int(n), edge_index._version
         self.rowptr, self.col = GATConv.csr_by_target(edge_index, n)
-        self._tiled, self._tiles, self._cut = bool(tiled and edge_index.is_cuda), None, False
+        self._tiled, self._tiles, self._cut, self._t = bool(tiled and edge_index.is_cuda), None, False, None
+
+    def transpose(self):
+        """(rowptr_t, col_t, pos_t): the same structure as a CSR by source with each entry's position in the CSR by target
+        (ops.csr_transpose_pos) -- what the atomic-free backward of the msg_layers family gathers over.  Built on first use by a backward."""
+        if self._t is None:
+            self._t = ops.csr_transpose_pos(self.rowptr, self.col, self.n)
+        return self._t
 
     @property
     def tiles(self):
@@ -63,17 +76,17 @@ class GATConv(torch.nn.Module):
     def __init__(self, in_channels, out_channels, double_input=False, new_node_feat=True, use_edge_attn=True, heads=1,
                  concat=True, negative_slope=0.2, dropout=0., add_self_loops=True, bias=True, **kwargs):
         super(GATConv, self).__init__()
-        if not isinstance(in_channels, int) or heads != 1 or not new_node_feat or not use_edge_attn or not add_self_loops \
-                or not bias or abs(negative_slope - 0.2) > 1e-12:
-            raise NotImplementedError("GATConv (HIP): only the PDGNN configuration is implemented: int in_channels, heads=1, "
-                                      "new_node_feat, use_edge_attn, add_self_loops, bias, negative_slope=0.2")
+        if not isinstance(in_channels, int) or heads != 1 or not add_self_loops or not bias or abs(negative_slope - 0.2) > 1e-12:
+            raise NotImplementedError("GATConv (HIP): only the PDGNN configuration and its new_node_feat / use_edge_attn ablations are "
+                                      "implemented: int in_channels, heads=1, add_self_loops, bias, negative_slope=0.2")
         if concat:
             # the reference's concat=True path views [N,1,2C] as [-1, C] and then adds a 2C bias (:166-172): a shape error
             raise NotImplementedError("GATConv (HIP): concat=True is not usable in the reference either; use concat=False")
         self.in_channels, self.out_channels, self.heads, self.concat = in_channels, out_channels, heads, concat
         self.negative_slope, self.dropout, self.add_self_loops = negative_slope, dropout, add_self_loops
-        self.new_node_feat, self.use_edge_attn = new_node_feat, use_edge_attn
-        self.lin_ij = Linear(2 * out_channels, out_channels, bias=False)                        # :80-81
+        self.new_node_feat, self.use_edge_attn = bool(new_node_feat), bool(use_edge_attn)
+        if new_node_feat:
+            self.lin_ij = Linear(2 * out_channels, out_channels, bias=False)                    # :78-79
         self.lin_l = Linear((2 if double_input else 1) * in_channels, heads * out_channels, bias=False)   # :83-86
         self.lin_r = self.lin_l
         self.att_l = Parameter(torch.Tensor(1, heads, out_channels))
@@ -106,6 +119,8 @@ class GATConv(torch.nn.Module):
         if isinstance(csr, GraphBatch):
             batch = csr
             csr = csr.check(edge_index, x.shape[0])
+        if not (self.new_node_feat and self.use_edge_attn):
+            return self._forward_ablation(x, edge_index, prelu_slope, batch if batch is not None else csr)
         rowptr, col = csr if csr is not None else self.csr_by_target(edge_index, x.shape[0])
         if torch.is_grad_enabled() and (x.requires_grad or self.lin_l.weight.requires_grad or self.att_l.requires_grad
                                         or self.lin_ij.weight.requires_grad or self.bias.requires_grad):
@@ -116,6 +131,20 @@ class GATConv(torch.nn.Module):
                                        self.lin_ij.weight.detach(), self.bias.detach(), prelu_slope=prelu_slope)
         return ops.gat_layer(rowptr, col, x, self.lin_l.weight.detach(), self.att_l.detach().reshape(-1),
                              self.lin_ij.weight.detach(), self.bias.detach(), prelu_slope=prelu_slope)
+
+    def _forward_ablation(self, x, edge_index, prelu_slope, csr):
+        """new_node_feat and / or use_edge_attn off: the msg_layers family, sum || (min + max) (:216).  csr: a GraphBatch, a
+        (rowptr, col) pair or None."""
+        mode = ops.msg_mode(self.new_node_feat, self.use_edge_attn)
+        att = self.att_l if self.use_edge_attn else None
+        wij = self.lin_ij.weight if self.new_node_feat else None
+        params = [p for p in (self.lin_l.weight, att, wij, self.bias) if p is not None]
+        if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in params)):
+            batch = csr if isinstance(csr, GraphBatch) else GraphBatch(edge_index, x.shape[0], tiled=False)
+            return autograd.msg_layer(x, self.lin_l.weight, att, wij, self.bias, batch, mode, "sum_minmax", prelu_slope)
+        rowptr, col = (csr.rowptr, csr.col) if isinstance(csr, GraphBatch) else (csr if csr is not None else self.csr_by_target(edge_index, x.shape[0]))
+        return ops.msg_layer(rowptr, col, x, self.lin_l.weight.detach(), None if att is None else att.detach(), None if wij is None else wij.detach(),
+                             self.bias.detach(), mode, "sum_minmax", prelu_slope)
 
     def __repr__(self):
         return '{}({}, {}, heads={})'.format(self.__class__.__name__, self.in_channels, self.out_channels, self.heads)

@@ -43,6 +43,7 @@ PI_SLICE, PI_CHUNK, PI_GROUP = 1024, 32, 32                         # points per
 DIST_WAVE_NMAX, DIST_WG_NMAX, DIST_WG_MMAX, DIST_WORK_FALLBACKS_OFF = 64, 2048, 4096, 64   # TLC_DIST_*: the size classes of csrc/dist_filt.hip
 SEG_LANE_MAX, SEG_WAVE_MAX, SEG_WG_THREADS = 16, 2048, 256           # TLC_SEG_*: the size classes of csrc/vic_grad.hip by segment length
 GNN_ACT_NONE, GNN_ACT_RELU, GNN_ACT_PRELU, GNN_ROWS = 0, 1, 2, 64      # TLC_GNN_ACT_*; GN_ROWS of csrc/gnn_layers.hip: node rows per group
+MSG_NODE_FEAT, MSG_EDGE_ATTN, MSG_AGG_SUM_MINMAX, MSG_AGG_SUM_MIN = 1, 2, 0, 1   # TLC_MSG_* of include/tlcgnn.h (csrc/msg_layers.hip)
 DESCRIPTOR_FLAG ={"sum": 0, "min": DESC_MIN, "max": DESC_MAX}      # the three node values of filtration.build_fv
 
 # every symbol include/tlcgnn.h declares (tests check that the library exports all of them)
@@ -72,6 +73,7 @@ SYMBOLS = [
     "tlc_gat_layer_fwd_work_floats", "tlc_gat_layer_tiled_fwd_work_floats", "tlc_gat_tile_cut_work_ints", "tlc_gat_tile_cut_max_tiles",
     "tlc_csr_by_target_work_ints", "tlc_gat_layer_bwd_work_floats", "tlc_edge_head_fwd_work_floats", "tlc_edge_head_bwd_work_floats",
     "tlc_gnn_layer_fwd", "tlc_gnn_layer_bwd_work_bytes", "tlc_gnn_layer_bwd", "tlc_gnn_stack_fwd",
+    "tlc_msg_layer_fwd_work_bytes", "tlc_msg_layer_fwd", "tlc_msg_layer_bwd_work_bytes", "tlc_msg_layer_bwd",
 ]
 
 
@@ -273,6 +275,12 @@ def lib():
                                         + [C.c_void_p] * 2 + [C.c_int32, C.c_float] + [C.c_void_p] * 5 + [C.c_int64, C.c_void_p])
         L.tlc_gnn_stack_fwd.argtypes = ([C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32,
                                          C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.POINTER(C.c_float), C.c_void_p, C.c_void_p])
+        L.tlc_msg_layer_fwd_work_bytes.argtypes, L.tlc_msg_layer_fwd_work_bytes.restype = [C.c_int32] * 4, C.c_int64
+        L.tlc_msg_layer_fwd.argtypes = ([C.c_int32] + [C.c_void_p] * 3 + [C.c_int32, C.c_int32] + [C.c_void_p] * 4 + [C.c_int32, C.c_int32, C.c_float,
+                                        C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p])
+        L.tlc_msg_layer_bwd_work_bytes.argtypes, L.tlc_msg_layer_bwd_work_bytes.restype = [C.c_int32, C.c_int64] + [C.c_int32] * 3, C.c_int64
+        L.tlc_msg_layer_bwd.argtypes = ([C.c_int32] + [C.c_void_p] * 6 + [C.c_int32, C.c_int32] + [C.c_void_p] * 3 + [C.c_int32, C.c_int32, C.c_float]
+                                        + [C.c_void_p] * 8 + [C.c_int64, C.c_void_p])
         L.tlc_debug_set_option.argtypes = [C.c_void_p, C.c_char_p, C.c_int]
         L.tlc_debug_dc_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.tlc_debug_tier_counts.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]

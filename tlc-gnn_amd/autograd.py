@@ -4,7 +4,7 @@
 classifier of Knowledge_Distillation/ConvCurv_GIN.py: CurvConv and NcLinear (nc_curv.hip).
 
 torch.autograd only carries the graph: every forward and every backward below is one C-ABI call (`tlc_gat_layer_fwd/_bwd`,
-`tlc_edge_head_fwd/_bwd`, `tlc_w2_partial_matching`, `tlc_sliced_wasserstein`, `tlc_bottleneck_matching`, `tlc_pi_raster` / `tlc_pi_raster_wgrad`, `tlc_pi_image` / `tlc_pi_image_vjp`, `tlc_hks_batch_dt` + `tlc_hks_large_batch_dt`) or a few (`tlc_gemm_f32` /
+`tlc_msg_layer_fwd/_bwd`, `tlc_edge_head_fwd/_bwd`, `tlc_w2_partial_matching`, `tlc_sliced_wasserstein`, `tlc_bottleneck_matching`, `tlc_pi_raster` / `tlc_pi_raster_wgrad`, `tlc_pi_image` / `tlc_pi_image_vjp`, `tlc_hks_batch_dt` + `tlc_hks_large_batch_dt`) or a few (`tlc_gemm_f32` /
 `tlc_spmm_csr_f32` / `tlc_gemm_tn_f32`, `tlc_lp_decode_fused_f32` / `tlc_lp_decode_bwd_f32` / `tlc_lp_decode_bwd_pi_f32`, `tlc_segment_sum_f64`); nothing is recomputed with torch ops
 and there is no CPU path.
 """
@@ -68,6 +68,29 @@ class GnnLayer(torch.autograd.Function):
         gx, gwa, gws, gb = ops.gnn_layer_bwd(rowptr_t, col_t, coef_t, b.self_scale, x, agg, out, gout.contiguous(), wa, ws, ctx.has_bias,
                                              ctx.act, ctx.slope, need_gx=ctx.needs_input_grad[0])
         return gx, gwa, gws, gb, None, None, None
+
+
+class MsgLayer(torch.autograd.Function):
+    """One layer of the PDGNN family (GATConv's ablations, PDConv) with the PReLU that follows it: `tlc_msg_layer_fwd`, and
+    `tlc_msg_layer_bwd` (no floating-point atomics) on the structure and its transpose.  `batch`: a gat_conv.GraphBatch.  att / wij may
+    be None when their switch is off; their gradient is then None."""
+
+    @staticmethod
+    def forward(ctx, x, wl, att, wij, bias, batch, mode, agg, prelu_slope):
+        out = ops.msg_layer(batch.rowptr, batch.col, x, wl, att, wij, bias, mode, agg, prelu_slope)
+        ctx.save_for_backward(x, wl, att, wij, out)
+        ctx.batch, ctx.mode, ctx.agg, ctx.prelu_slope = batch, mode, agg, prelu_slope
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        x, wl, att, wij, out = ctx.saved_tensors
+        b = ctx.batch
+        rowptr_t, col_t, pos_t = b.transpose()
+        gx, gwl, gatt, gwij, gbias = ops.msg_layer_bwd(b.rowptr, b.col, rowptr_t, col_t, pos_t, x, wl, att, wij, ctx.mode, ctx.agg, ctx.prelu_slope,
+                                                       out, gout.contiguous(), need_gx=ctx.needs_input_grad[0])
+        # (ops.msg_layer_bwd returns None for gatt / gwij exactly when att / wij were None: their switch is off)
+        return gx, gwl, (None if gatt is None else gatt.reshape(att.shape)), gwij, gbias, None, None, None, None
 
 
 _W2_STATUS = "1 = fewer predicted than target points, 2 = too many points for one problem (%s), 3 = NaN / Inf coordinates"
@@ -411,6 +434,10 @@ def gat_layer(x, wl, att, wij, bias, rowptr, src, prelu_slope=-1.0):
 
 def gnn_layer(x, wa, ws, bias, batch, act=None, slope=0.0):
     return GnnLayer.apply(x, wa, ws, bias, batch, act, slope)
+
+
+def msg_layer(x, wl, att, wij, bias, batch, mode, agg="sum_minmax", prelu_slope=-1.0):
+    return MsgLayer.apply(x, wl, att, wij, bias, batch, int(mode), agg, float(prelu_slope))
 
 
 def edge_head(x, w5, b5, w6, b6, src, dst, prelu_slope):

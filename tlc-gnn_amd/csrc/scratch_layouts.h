@@ -107,6 +107,34 @@ struct TlcGnnLayerBwdScratch {
           total(tn + std::max(TlcGemmTnScratch(c_out, c_in).total, TlcGemmTnScratch(1, c_out).total)) {}
 };
 
+// tlc_msg_layer_fwd (msg_layers.hip).  In floats, every array on a multiple of four: x_l [n][C] | alpha [n] (EDGE_ATTN) | P, Q [n][C]
+// each (NODE_FEAT; without it x_l is the message part).  tlc_msg_layer_fwd_work_bytes returns `total` in BYTES.
+struct TlcMsgLayerFwdScratch {
+    int64_t xl = 0, alpha, p, q, total;
+    TlcMsgLayerFwdScratch(int64_t n, int64_t C, bool node_feat, bool edge_attn)
+        : alpha(tlc_up4(n * C)), p(alpha + (edge_attn ? tlc_up4(n) : 0)), q(p + (node_feat ? tlc_up4(n * C) : 0)),
+          total(q + (node_feat ? tlc_up4(n * C) : 0)) {}
+};
+
+// tlc_msg_layer_bwd (msg_layers.hip).  In floats, every array on a multiple of four: the forward's node rows again (`f`) | Gz [n][2C] |
+// the arg-min and arg-max entries int[n][C] each | gx_l [n][C] | with EDGE_ATTN the row scalars (maximum, denominator, softmax-backward
+// dot) [n][4], the target-side logit sums [n] and galpha [n] | with NODE_FEAT gP, gQ [n][C] each and the two halves of gWij [2][C][C] |
+// the split-K partials of its tlc_gemm_tn_f32 products one after the other in the same room.  Nothing of the size of the entries.
+// tlc_msg_layer_bwd_work_bytes returns `total` in BYTES.
+struct TlcMsgLayerBwdScratch {
+    TlcMsgLayerFwdScratch f;
+    int64_t gz, emn, emx, gxl, stat, gtgt, gal, gp, gq, halves, tn, total;
+    TlcMsgLayerBwdScratch(int64_t n, int64_t c_in, int64_t C, bool node_feat, bool edge_attn) : f(n, C, node_feat, edge_attn) {
+        int64_t o = f.total;
+        auto take = [&](int64_t count) { const int64_t at = o; o += tlc_up4(count); return at; };
+        gz = take(n * 2 * C); emn = take(n * C); emx = take(n * C); gxl = take(n * C);
+        stat = take(edge_attn ? 4 * n : 0); gtgt = take(edge_attn ? n : 0); gal = take(edge_attn ? n : 0);
+        gp = take(node_feat ? n * C : 0); gq = take(node_feat ? n * C : 0); halves = take(node_feat ? 2 * C * C : 0);
+        tn = o;
+        total = o + std::max(std::max(TlcGemmTnScratch(C, C).total, TlcGemmTnScratch(C, c_in).total), TlcGemmTnScratch(1, 2 * C).total);
+    }
+};
+
 // tlc_graph_components (gc_prep.hip).  In BYTES, every array on a multiple of 256: the control words [HEAD bytes] | the WAVE class's
 // graph list int[B] | and, only when the batch can hold a WIDE graph (total_nodes > wave_nmax): per graph the class byte u8[B], the
 // winner u64[B], the component count int[B], the first sorted key int[B]; per node the label u32[N], the component size int[N], the

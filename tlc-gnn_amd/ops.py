@@ -723,6 +723,111 @@ def gnn_stack(rowptr, src, coef, self_scale, tiles, x, layers, out=None):
     return out
 
 
+# ---- the PDGNN layer family: GATConv's ablations and PDConv (msg_layers.hip; autograd.MsgLayer; gat_conv.py, PD_conv.py) ----
+MSG_AGGS = {"sum_minmax": _lib.MSG_AGG_SUM_MINMAX, "sum_min": _lib.MSG_AGG_SUM_MIN}
+
+
+def msg_mode(new_node_feat, use_edge_attn):
+    return (_lib.MSG_NODE_FEAT if new_node_feat else 0) | (_lib.MSG_EDGE_ATTN if use_edge_attn else 0)
+
+
+def csr_transpose_pos(rowptr, col, n):
+    """The CSR by source of a `csr_by_target` structure (rowptr int32 [n + 1], col = the sources, of which the first rowptr[n] count):
+    -> (rowptr_t int32 [n + 1], col_t int32 [nnz] = the targets, pos_t int32 [nnz] = each entry's position in `col`).  A stable sort, so a
+    source's entries keep the order of their positions.  Torch ops on the tensors' device (CPU tensors work too); one host read, of nnz:
+    built once per batch (GraphBatch.transpose)."""
+    import torch
+    n = int(n)
+    nnz = int(rowptr[n]) if n > 0 else 0
+    src = col[:nnz].to(torch.int64)
+    counts = (rowptr[1:n + 1] - rowptr[:n]).to(torch.int64)
+    tgt = torch.repeat_interleave(torch.arange(n, dtype=torch.int64, device=rowptr.device), counts)
+    order = torch.sort(src, stable=True).indices
+    rowptr_t = torch.zeros(n + 1, dtype=torch.int32, device=rowptr.device)
+    rowptr_t[1:] = torch.cumsum(torch.bincount(src, minlength=n), 0)
+    return rowptr_t, tgt[order].to(torch.int32).contiguous(), order.to(torch.int32).contiguous()
+
+
+def _msg_operands(x, wl, att, wij, mode):
+    """(wl, att or None, wij or None) as the C ABI reads them, shapes checked against x [n, c_in] and c_out = wl.shape[0]: the library
+    cannot see a tensor's size, so a wrong-shaped operand would be read out of bounds on the device."""
+    c_out = wl.shape[0]
+    if x.dim() != 2 or tuple(wl.shape) != (c_out, x.shape[1]):
+        raise ValueError("msg_layer: x %s and wl %s do not fit [n, c_in] and [c_out, c_in]" % (tuple(x.shape), tuple(wl.shape)))
+    att = _f32(att).reshape(-1) if mode & _lib.MSG_EDGE_ATTN else None
+    wij = _f32(wij) if mode & _lib.MSG_NODE_FEAT else None
+    if att is not None and att.numel() != c_out:
+        raise ValueError("msg_layer: att has %d elements for c_out %d" % (att.numel(), c_out))
+    if wij is not None and tuple(wij.shape) != (c_out, 2 * c_out):
+        raise ValueError("msg_layer: wij %s is not [c_out, 2 c_out] = [%d, %d]" % (tuple(wij.shape), c_out, 2 * c_out))
+    return _f32(wl), att, wij
+
+
+def _msg_rows(name, t, n, c_out):
+    if t is not None and tuple(t.shape) != (n, 2 * c_out):
+        raise ValueError("msg_layer: %s %s is not [n, 2 c_out] = [%d, %d]" % (name, tuple(t.shape), n, 2 * c_out))
+
+
+@_lib.on_device_of
+def msg_layer(rowptr, src, x, wl, att, wij, bias, mode, agg="sum_minmax", prelu_slope=-1.0, out=None):
+    """One layer of the PDGNN family (tlc_msg_layer_fwd) on a CSR by target with self loops (`csr_by_target`): mode = msg_mode(new_node_feat,
+    use_edge_attn); agg 'sum_minmax' (gat_conv.py:216) or 'sum_min' (PD_conv.py:219).  att / wij are not read (and may be None) when their
+    switch is off.  -> f32 [n, 2 c_out]."""
+    torch = _lib.require_gpu()
+    x = _f32(x)
+    n, c_in = x.shape
+    c_out = wl.shape[0]
+    if bias.numel() != 2 * c_out or rowptr.numel() != n + 1:
+        raise ValueError("msg_layer: bias of %d elements / rowptr of %d for c_out %d and %d nodes" % (bias.numel(), rowptr.numel(), c_out, n))
+    if out is None:
+        out = torch.empty((n, 2 * c_out), dtype=torch.float32, device=x.device)
+    _msg_rows("out", out, n, c_out)
+    assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous()
+    L = _lib.lib()
+    nbytes = int(L.tlc_msg_layer_fwd_work_bytes(C.c_int32(n), C.c_int32(c_in), C.c_int32(c_out), C.c_int32(mode)))
+    if nbytes < 0:
+        raise ValueError("msg_layer: negative size or unknown mode bits")
+    work = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=x.device)
+    keep = _msg_operands(x, wl, att, wij, mode) + (_f32(bias).reshape(-1),)
+    rc = L.tlc_msg_layer_fwd(C.c_int32(n), _lib.ptr(rowptr), _lib.ptr(src), _lib.ptr(x), C.c_int32(c_in), C.c_int32(c_out), _lib.ptr(keep[0]),
+                             _lib.ptr(keep[1]), _lib.ptr(keep[2]), _lib.ptr(keep[3]), C.c_int32(mode), C.c_int32(MSG_AGGS[agg]),
+                             C.c_float(prelu_slope), _lib.ptr(work), C.c_int64(nbytes), _lib.ptr(out), _lib.stream_ptr())
+    _lib.check(rc, "tlc_msg_layer_fwd")
+    return out
+
+
+@_lib.on_device_of
+def msg_layer_bwd(rowptr, src, rowptr_t, col_t, pos_t, x, wl, att, wij, mode, agg, prelu_slope, out, gout, need_gx=True):
+    """Gradients of `msg_layer` (tlc_msg_layer_bwd; no floating-point atomics): -> (gX or None, gWl, gatt or None, gWij or None, gbias).
+    rowptr_t / col_t / pos_t: `csr_transpose_pos` of the structure; `out`: the forward's output (read for the fused PReLU only)."""
+    torch = _lib.require_gpu()
+    x, gout = _f32(x), _f32(gout)
+    n, c_in = x.shape
+    c_out = wl.shape[0]
+    dev = x.device
+    _msg_rows("gout", gout, n, c_out)
+    _msg_rows("out", out, n, c_out)
+    if rowptr.numel() != n + 1 or rowptr_t.numel() != n + 1 or col_t.numel() != pos_t.numel() or src.numel() < col_t.numel():
+        raise ValueError("msg_layer_bwd: the CSR by target and its transpose (csr_transpose_pos) do not fit %d nodes" % n)
+    gx = torch.empty((n, c_in), dtype=torch.float32, device=dev) if need_gx else None
+    gwl = torch.empty((c_out, c_in), dtype=torch.float32, device=dev)
+    gatt = torch.empty(c_out, dtype=torch.float32, device=dev) if mode & _lib.MSG_EDGE_ATTN else None
+    gwij = torch.empty((c_out, 2 * c_out), dtype=torch.float32, device=dev) if mode & _lib.MSG_NODE_FEAT else None
+    gbias = torch.empty(2 * c_out, dtype=torch.float32, device=dev)
+    L = _lib.lib()
+    nbytes = int(L.tlc_msg_layer_bwd_work_bytes(C.c_int32(n), C.c_int64(col_t.numel()), C.c_int32(c_in), C.c_int32(c_out), C.c_int32(mode)))
+    if nbytes < 0:
+        raise ValueError("msg_layer_bwd: negative size or unknown mode bits")
+    work = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
+    keep = _msg_operands(x, wl, att, wij, mode) + (_opt_f32(out),)
+    rc = L.tlc_msg_layer_bwd(C.c_int32(n), _lib.ptr(rowptr), _lib.ptr(src), _lib.ptr(rowptr_t), _lib.ptr(col_t), _lib.ptr(pos_t), _lib.ptr(x),
+                             C.c_int32(c_in), C.c_int32(c_out), _lib.ptr(keep[0]), _lib.ptr(keep[1]), _lib.ptr(keep[2]), C.c_int32(mode),
+                             C.c_int32(MSG_AGGS[agg]), C.c_float(prelu_slope), _lib.ptr(keep[3]), _lib.ptr(gout), _lib.ptr(gx), _lib.ptr(gwl),
+                             _lib.ptr(gatt), _lib.ptr(gwij), _lib.ptr(gbias), _lib.ptr(work), C.c_int64(nbytes), _lib.stream_ptr())
+    _lib.check(rc, "tlc_msg_layer_bwd")
+    return gx, gwl, gatt, gwij, gbias
+
+
 REDUCE = {"add": 0, "sum": 0, "mean": 1, "min": 2, "max": 3}
 
 
