@@ -14,6 +14,8 @@ tier, scipy on the host), the evaluation form above the cut 10 s, the forty prob
 import numpy as np
 import pytest
 
+from w2_checks import _check_inference, _check_training, _host, _pack, _pair
+
 pytestmark = pytest.mark.gpu
 
 SIZES = (1, 2, 63, 64, 65, 1023, 1024, 1025, 2049)
@@ -24,28 +26,6 @@ def torch_cuda():
     import torch
     assert torch.cuda.is_available(), "GPU tests need an MI355X"
     return torch
-
-
-def _pair(rs, n, m, style="random"):
-    if style == "grid":                                              # coordinates on a coarse grid: many tied costs
-        return rs.randint(0, 6, size=(n, 2)) / 5.0, rs.randint(0, 6, size=(m, 2)) / 5.0
-    b0 = rs.rand(n)
-    X = np.stack([b0, b0 + rs.uniform(-0.1, 0.6, size=n)], 1)        # a few predicted points BELOW the diagonal
-    b1 = rs.rand(m)
-    Y = np.stack([b1, b1 + rs.uniform(0.0, 0.7, size=m)], 1)
-    return X.astype(np.float64), Y.astype(np.float64)
-
-
-def _pack(torch, xs, ys):
-    xoff = np.concatenate([[0], np.cumsum([len(x) for x in xs])]).astype(np.int64)
-    yoff = np.concatenate([[0], np.cumsum([len(y) for y in ys])]).astype(np.int64)
-    X = np.concatenate(list(xs) + [np.zeros((0, 2))]).reshape(-1, 2)
-    Y = np.concatenate(list(ys) + [np.zeros((0, 2))]).reshape(-1, 2)
-    return xoff, yoff, torch.as_tensor(xoff).cuda(), torch.as_tensor(X).cuda(), torch.as_tensor(yoff).cuda(), torch.as_tensor(Y).cuda()
-
-
-def _host(r):
-    return {k: (None if v is None else v.cpu().numpy()) for k, v in r.items() if k != "work"}
 
 
 def _problems(infer, order):
@@ -78,64 +58,6 @@ def _solved(torch, infer, order):
                 v.setflags(write=False)
         _CACHE[key] = dict(xs=xs, ys=ys, xoff=xoff, yoff=yoff, dev=(dxo, dX, dyo, dY), r=r, ref=ref)
     return _CACHE[key]
-
-
-def _check_training(torch, Xb, Yb, order, a, loss, wxy, wxd, grad, ref_cost, unique=True):
-    from oracle import w2_ref
-    n, m = len(Xb), len(Yb)
-    # a valid partial matching: every target exactly once, the rest on the diagonal
-    assert sorted(a[a >= 0].tolist()) == list(range(m)) and (a >= -1).all() and (a < max(m, 1)).all()
-    M = w2_ref.cost_matrix(Xb, Yb, order)
-    cost = float(M[np.arange(n), np.where(a >= 0, a, m)].sum())
-    print("training n=%d m=%d order=%d: cost %.17g scipy %.17g" % (n, m, order, cost, ref_cost))
-    assert abs(cost - ref_cost) <= 1e-9 * max(1.0, abs(ref_cost)), (n, m, cost, ref_cost)
-    if not unique:
-        return
-    l2, wxy2, wxd2 = w2_ref.loss_from_assignment(Xb, Yb, a, order)
-    assert abs(loss - l2) <= 1e-12 * max(1.0, l2) and abs(wxy - wxy2) <= 1e-12 * max(1.0, wxy2) and abs(wxd - wxd2) <= 1e-12 * max(1.0, wxd2)
-    if n:
-        Xt = torch.tensor(Xb, requires_grad=True)
-        w2_ref.loss_torch(Xt, torch.tensor(Yb), a, order).backward()
-        assert np.abs(grad - Xt.grad.numpy()).max() <= 1e-12
-
-
-def _check_inference(torch, Xb, Yb, order, ax, ay, loss, wxy, wxd, wyd, grad, ref, unique=True):
-    from oracle import w2_ref
-    n, m = len(Xb), len(Yb)
-    if n == 0 or m == 0:
-        # (:98-113) total persistence of the other diagram, the parts reported as 0, nothing matched
-        assert abs(loss - ref[0]) <= 1e-12 * max(1.0, ref[0]) and wxy == 0 and wxd == 0 and wyd == 0
-        assert (ax == -1).all() and (ay == -1).all()
-        if n:
-            d = (Xb[:, 1] - Xb[:, 0]) * 0.5
-            want = np.stack([-0.5 * d / loss, 0.5 * d / loss], 1) if order == 2 else np.stack([-0.5 * np.sign(d), 0.5 * np.sign(d)], 1)
-            assert np.abs(grad - want).max() <= 1e-12
-        return
-    on = ax >= 0
-    # the two maps are each other's inverse on the matched points
-    assert (ax < m).all() and (ax >= -1).all() and (ay < n).all() and (ay >= -1).all()
-    assert (ay[ax[on]] == np.flatnonzero(on)).all() and (ay >= 0).sum() == on.sum()
-    C = w2_ref.inference_cost_matrix(Xb, Yb, order)
-    cost = float(C[np.flatnonzero(on), ax[on]].sum() + C[np.flatnonzero(~on), m].sum() + C[n, np.flatnonzero(ay < 0)].sum())
-    print("evaluation n=%d m=%d order=%d: cost %.17g scipy %.17g" % (n, m, order, cost, ref[6]))
-    assert abs(cost - ref[6]) <= 1e-9 * max(1.0, abs(ref[6])), (n, m, cost, ref[6])
-    if not unique:
-        return
-    for got, want in zip((loss, wxy, wxd, wyd), w2_ref.inference_loss_from_assignment(Xb, Yb, ax, ay, order)):
-        assert abs(got - want) <= 1e-12 * max(1.0, want)
-    Xt = torch.tensor(Xb, requires_grad=True)
-    Yt = torch.tensor(Yb)
-    parts = []
-    if on.any():
-        parts.append((Yt[torch.as_tensor(ax[on]).long()] - Xt[torch.as_tensor(on)]).abs().amax(dim=1))
-    if (~on).any():
-        q = Xt[torch.as_tensor(~on)]
-        parts.append(((q[:, 1] - q[:, 0]) * 0.5).abs())
-    if (ay < 0).any():
-        q = Yt[torch.as_tensor(ay < 0)]
-        parts.append(((q[:, 1] - q[:, 0]) * 0.5).abs())
-    ((torch.cat(parts) ** order).sum() ** (1.0 / order)).backward()
-    assert np.abs(grad - Xt.grad.numpy()).max() <= 1e-12
 
 
 @pytest.mark.parametrize("order", [2, 1])
