@@ -993,6 +993,53 @@ int tlc_pi_image_vjp(int32_t n_dgms, int64_t n_pts, const int64_t* d_offs, const
                      const double* h_bpnts, const double* h_ppnts, const double* h_ramp, const double* h_sigma, int32_t skew,
                      int32_t mode, const double* d_grad_img, double* d_grad_pts, void* stream);
 
+/* ---- Persistence landscapes of packed diagrams and their gradient (csrc/landscape.hip) ---------------------------
+ * The landscape of Bubenik: the top K of the points' tent functions on a grid of sample values (PersLay's triangle layer under a
+ * top-k pooling).  No smoothing parameter; the samples are INPUTS (a linspace is the caller's business).
+ *
+ * THE FUNCTION.  Diagram b: n points (birth_i, death_i), fp64 rows in the packed layout of tlc_sliced_wasserstein (d_offs
+ * int64[B + 1]).  d_ts float64[T], any finite values, 1 <= T <= TLC_LS_TMAX; 1 <= K <= TLC_LS_KMAX.  In plain fp64:
+ *     v_i(t) = min(t - birth_i, death_i - t)                                          (min(a, b) = a < b ? a : b)
+ *   Point i is present at t iff v_i(t) > 0: a point with death <= birth is never present.  The present points are ordered by
+ *   (v descending, i ascending), a strict total order.  d_out[b, k, j] is the v of the k-th point of that order at t_j (k = 0 .. K-1)
+ *   and d_winner[b, k, j] its index, local to the diagram; with fewer than k + 1 points present the value is +0.0 and the winner -1.
+ *   d_out float64[B, K, T], d_winner int32[B, K, T] (may be NULL): every cell of every diagram is written.
+ *   Every value is one subtraction and one min of the inputs, and the K best under a strict total order do not depend on how the
+ *   points are divided: the bits of a diagram depend on its own points, the samples and K alone -- not on the run, the batch around
+ *   it or the workspace.
+ * d_status uint8[B]: 0 ok (n = 0 is an ordinary diagram of zero rows); 3 = a NaN / Inf coordinate in the diagram: its values NaN, its
+ *   winners -1, and so its gradient zero; its neighbours are untouched.
+ *
+ * THE GRADIENT (tlc_landscape_vjp).  d_grad_pts float64[sum n, 2], every row written.  A cell (k, j) with winner i and upstream g =
+ *   d_grad_out[b, k, j] contributes (-g, 0) to point i when  t_j - birth_i <= death_i - t_j  (the birth side wins the exact tie at the
+ *   peak), else (0, +g).  A point's contributions are added from +0.0 over the cells in ascending (k, j); one owner sums a point and
+ *   there is no floating-point atomic.  The side is recomputed from the points; d_winner is the forward's output (an index outside
+ *   0 .. n-1 names nobody).  Points that win nothing get zero rows.  Under ties (duplicate points, a sample on a peak) the landscape is
+ *   not differentiable and this convention is the subgradient.
+ *
+ * Size classes by n, cut on the device: up to TLC_LS_WAVE_NMAX one wavefront per diagram (the points broadcast from its lanes); up
+ * to TLC_LS_LDS_NMAX one workgroup per diagram and block of 256 samples (the points in LDS); above, the whole device, one diagram
+ * after the other: slices of TLC_LS_LDS_NMAX points write their K-lists to d_work and a second kernel merges a cell's lists, the
+ * slices ascending.  No cap below 2^27 points.
+ * max_points: an upper bound of one diagram's n.  Both entries read the offsets and the samples back once and synchronise the
+ * stream before they launch anything.
+ * tlc_landscape_work_bytes (host arithmetic): the d_work that runs the slices of the largest diagram in the fewest launches; 0 (d_work
+ * may be NULL) when max_points <= TLC_LS_LDS_NMAX; -1 for a negative size or K / T out of range.  *least (may be NULL): the size that
+ * runs one slice at a time; any d_work of at least *least gives the same bits.
+ * TLC_ERR_INVALID_ARG, nothing launched: negative sizes, K or T out of range, null required pointers, a NaN / Inf sample, offsets
+ * that decrease or a diagram above max_points, a d_work below *least.  TLC_ERR_UNSUPPORTED: a diagram above 2^27 points.
+ * n_dgms == 0: TLC_OK, nothing read. */
+#define TLC_LS_WAVE_NMAX  64
+#define TLC_LS_LDS_NMAX   4096
+#define TLC_LS_KMAX       16
+#define TLC_LS_TMAX       4096
+int64_t tlc_landscape_work_bytes(int32_t n_dgms, int64_t max_points, int32_t K, int32_t T, int64_t* least);
+int tlc_landscape(int32_t n_dgms, const int64_t* d_offs, const double* d_pts, int32_t T, const double* d_ts, int32_t K,
+                  int64_t max_points, double* d_out, int32_t* d_winner, uint8_t* d_status, void* d_work, int64_t work_bytes,
+                  void* stream);
+int tlc_landscape_vjp(int32_t n_dgms, const int64_t* d_offs, const double* d_pts, int32_t T, const double* d_ts, int32_t K,
+                      int64_t max_points, const int32_t* d_winner, const double* d_grad_out, double* d_grad_pts, void* stream);
+
 /* ---- what `loss.backward()` runs through the PDGNN layer and the edge head ---------------------------
  * (Knowledge_Distillation/train_Teacher_Model.py:55-62 through gat_conv.py:113-216 and Teacher_model.py:53-59.)
  * tlc_gat_layer_bwd: gradients of one layer, same operands as tlc_gat_layer_fwd.  Nothing of the forward is kept: the node rows,

@@ -4,7 +4,7 @@
 classifier of Knowledge_Distillation/ConvCurv_GIN.py: CurvConv and NcLinear (nc_curv.hip).
 
 torch.autograd only carries the graph: every forward and every backward below is one C-ABI call (`tlc_gat_layer_fwd/_bwd`,
-`tlc_msg_layer_fwd/_bwd`, `tlc_edge_head_fwd/_bwd`, `tlc_w2_partial_matching`, `tlc_sliced_wasserstein`, `tlc_bottleneck_matching`, `tlc_pi_raster` / `tlc_pi_raster_wgrad`, `tlc_pi_image` / `tlc_pi_image_vjp`, `tlc_hks_batch_dt` + `tlc_hks_large_batch_dt`) or a few (`tlc_gemm_f32` /
+`tlc_msg_layer_fwd/_bwd`, `tlc_edge_head_fwd/_bwd`, `tlc_w2_partial_matching`, `tlc_sliced_wasserstein`, `tlc_bottleneck_matching`, `tlc_pi_raster` / `tlc_pi_raster_wgrad`, `tlc_pi_image` / `tlc_pi_image_vjp`, `tlc_landscape` / `tlc_landscape_vjp`, `tlc_hks_batch_dt` + `tlc_hks_large_batch_dt`) or a few (`tlc_gemm_f32` /
 `tlc_spmm_csr_f32` / `tlc_gemm_tn_f32`, `tlc_lp_decode_fused_f32` / `tlc_lp_decode_bwd_f32` / `tlc_lp_decode_bwd_pi_f32`, `tlc_segment_sum_f64`); nothing is recomputed with torch ops
 and there is no CPU path.
 """
@@ -221,6 +221,26 @@ class GeneralDiagramImage(torch.autograd.Function):
         return g.to(ctx.dtype), None, None, None
 
 
+class DiagramLandscape(torch.autograd.Function):
+    """Persistence landscapes of one or more diagrams (include/tlcgnn.h defines them), [B, K, T] in the diagrams' dtype:
+    `tlc_landscape` forward, `tlc_landscape_vjp` backward over the forward's winners -- a +-1 selection, so the gradient of a cell
+    reaches one coordinate of one point.  The points are computed in float64 whatever their dtype; the samples get no gradient."""
+
+    @staticmethod
+    def forward(ctx, pd_hat, offs, ts, K):
+        pts = pd_hat.detach().to(torch.float64).contiguous()
+        r = ops.landscape(pts, offs, ts, K=K, winners=True)
+        ctx.save_for_backward(pts, offs, r["winner"])
+        ctx.ts, ctx.K, ctx.dtype = ts.detach().to(torch.float64).contiguous(), K, pd_hat.dtype
+        return r["out"].to(pd_hat.dtype)
+
+    @staticmethod
+    def backward(ctx, gout):
+        pts, offs, winner = ctx.saved_tensors
+        g = engine.landscape_vjp(pts, offs, ctx.ts, ctx.K, winner, gout.to(torch.float64).contiguous())
+        return g.to(ctx.dtype), None, None, None
+
+
 class ExtendedPersistence(torch.autograd.Function):
     """The exact extended persistence as a differentiable function of the filtration values: (up, down, one, ext0, counts) in the slot
     layout of `engine.pd_from_filtration`, the same values bit for bit.  Every coordinate is a copy of one f[v], so the backward is a
@@ -426,6 +446,25 @@ def diagram_image(pd_hat, offs=None, res=5, imager=None, grad='weight'):
                              "(use imager.transform_batch on detached points)")
         spec = imager.spec(skew=True)
     return GeneralDiagramImage.apply(pd_hat, offs, spec, grad)
+
+
+def diagram_landscape(pd_hat, offs=None, ts=None, K=5):
+    """Persistence landscapes [B, K, T] of one or more diagrams (pd_hat [sum n, 2] float32 or float64, offs int64[B + 1] or None for
+    one diagram), differentiable in the points: out[b, k, j] is the (k + 1)-th largest tent value min(t_j - birth, death - t_j) > 0
+    of diagram b, +0.0 where fewer points are present.  ts: a 1-D tensor of sample values without grad (the caller's linspace);
+    1 <= K <= _lib.LS_KMAX, 1 <= T <= _lib.LS_TMAX; any diagram size.  A NaN / Inf coordinate raises RuntimeError naming the diagram."""
+    if not torch.is_tensor(ts) or ts.dim() != 1:
+        raise ValueError("diagram_landscape: ts should be a 1-D tensor of sample values")
+    if ts.requires_grad:
+        raise ValueError("diagram_landscape: ts requires grad, but the samples get no gradient (detach them)")
+    K = int(K)
+    if not 1 <= K <= _lib.LS_KMAX:
+        raise ValueError("diagram_landscape: K = %d, outside 1 .. %d" % (K, _lib.LS_KMAX))
+    if not 1 <= ts.numel() <= _lib.LS_TMAX:
+        raise ValueError("diagram_landscape: %d samples, outside 1 .. %d" % (ts.numel(), _lib.LS_TMAX))
+    if offs is None:
+        offs = torch.tensor([0, pd_hat.shape[0]], dtype=torch.int64, device=pd_hat.device)
+    return DiagramLandscape.apply(pd_hat, offs, ts, K)
 
 
 def gat_layer(x, wl, att, wij, bias, rowptr, src, prelu_slope=-1.0):

@@ -225,6 +225,41 @@ struct TlcPiImageScratch {
         : least(slices_of(max_points) * res_b * res_p), total(std::min<int64_t>(n_dgms, MAX_GROUP) * least) {}
 };
 
+// tlc_landscape (landscape.hip): only the diagrams above SLICE points use it, one after the other.  In BYTES, carved by the shared carver
+// (TlcCarver of tlc_common.h, handed in: this header stays host arithmetic): the control word | `slots` equal slots, each the K-lists
+// of one slice of SLICE points -- the values f64[K * T] | the indices int[K * T].  Slot 0 is the running list (the K best per cell over
+// the slices merged so far), slots 1 .. G the slices in flight.  `least` holds the running list and one slice, `total` as many slices
+// as the largest diagram has (at most MAX_GROUP at once).
+struct TlcLandscapeScratch {
+    static constexpr int64_t SLICE = 4096, MAX_GROUP = 64;
+    static int64_t slices_of(int64_t n_points) { return n_points > SLICE ? (n_points + SLICE - 1) / SLICE : 0; }
+    int64_t ctl = 0, slots = 0, val = 0, idx = 0, slot_bytes = 0, group = 0, least = 0, total = 0;
+    // in_flight: the slices of one launch; slots_for(g) is the size that runs g of them
+    template <class Carver>
+    static int64_t bytes_for(int64_t cells, int64_t in_flight, TlcLandscapeScratch* L) {
+        Carver W;
+        L->ctl = (int64_t)W.take(1, 4);
+        L->slots = (int64_t)W.bytes() - 256;
+        Carver S;
+        L->val = (int64_t)S.take(cells, 8);
+        L->idx = (int64_t)S.take(cells, 4);
+        L->slot_bytes = (int64_t)S.bytes() - 256;
+        return L->slots + (1 + in_flight) * L->slot_bytes + 256;      // (256: tlc_align256 of the caller's pointer)
+    }
+    template <class Carver>
+    TlcLandscapeScratch(int64_t max_points, int64_t K, int64_t T, Carver) {
+        const int64_t s = slices_of(max_points);
+        if (!s) return;
+        group = std::min(s, MAX_GROUP);
+        least = bytes_for<Carver>(K * T, 1, this);
+        total = bytes_for<Carver>(K * T, group, this);
+    }
+    int64_t groups_in(int64_t work_bytes) const {
+        if (!slot_bytes) return 0;
+        return std::min<int64_t>(MAX_GROUP, (work_bytes - 256 - slots) / slot_bytes - 1);
+    }
+};
+
 // tlc_w2_large_matching (w2_large.hip).  In BYTES.  The workspace is `slots` equal slots and nothing else; a workgroup owns one slot for
 // the whole launch.  A slot for problems of up to max_rows rows / columns, every array on a multiple of 256: the control words [HEAD
 // bytes]: the counters int64[COUNTERS] (steps, augmentations, rows the start assigned, problems) | the row duals u f64[R] | the column

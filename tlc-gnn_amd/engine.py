@@ -912,6 +912,84 @@ def pi_image_vjp(offs, pts, grad_img, spec, mode="weight"):
     return out[:pts.shape[0]]
 
 
+def landscape_work_bytes(n_dgms, max_points, K, T):
+    """(full, least) bytes of `landscape`'s workspace (tlc_landscape_work_bytes): 0 unless a diagram has more than _lib.LS_LDS_NMAX
+    points; any size from `least` up gives the same bits."""
+    least = C.c_int64(0)
+    full = _lib.lib().tlc_landscape_work_bytes(C.c_int32(int(n_dgms)), C.c_int64(int(max_points)), C.c_int32(int(K)), C.c_int32(int(T)),
+                                               C.byref(least))
+    if full < 0:
+        _lib.check(1, "tlc_landscape_work_bytes")
+    return int(full), int(least.value)
+
+
+def _landscape_sizes(what, pts, offs, ts, K):
+    """The checks `landscape` and `landscape_vjp` share -> (B, T, max_points); the offsets are read once (offsets beyond the points
+    would be read out of bounds on the device)."""
+    import torch
+    if ts.dim() != 1:
+        raise ValueError("%s: ts should be 1-D, not %s" % (what, tuple(ts.shape)))
+    T, K = int(ts.numel()), int(K)
+    if not 1 <= T <= _lib.LS_TMAX:
+        raise ValueError("%s: %d samples, outside 1 .. %d" % (what, T, _lib.LS_TMAX))
+    if not 1 <= K <= _lib.LS_KMAX:
+        raise ValueError("%s: K = %d, outside 1 .. %d" % (what, K, _lib.LS_KMAX))
+    B = offs.numel() - 1
+    max_points = 0
+    if B > 0:
+        cnt = offs[1:] - offs[:-1]
+        end, max_points = torch.stack([offs[-1], cnt.max()]).tolist()
+        if end > pts.shape[0]:
+            raise ValueError("%s: the offsets end at %d but there are %d points" % (what, end, pts.shape[0]))
+    return B, T, max(int(max_points), 0)
+
+
+@_lib.on_device_of
+def landscape(pts, offs, ts, K, winners=True, work=None):
+    """Persistence landscapes of packed diagrams (tlc_landscape; csrc/landscape.hip; include/tlcgnn.h defines them).
+
+    pts float64[sum n, 2] (birth, death), offs int64[B + 1], ts float64[T] sample values (CUDA tensors), K levels, work an optional
+    uint8 CUDA workspace (only diagrams above _lib.LS_LDS_NMAX points use one) -> (out float64[B, K, T], winner int32[B, K, T] or
+    None, status uint8[B]: 0 ok, 3 = a NaN / Inf coordinate).  The offsets and the samples are read back once."""
+    B, T, max_points = _landscape_sizes("landscape", pts, offs, ts, K)
+    torch = _lib.require_gpu()
+    dev = offs.device
+    pts, offs, ts = pts.contiguous(), offs.contiguous(), ts.contiguous()
+    assert pts.dtype == torch.float64 and offs.dtype == torch.int64 and ts.dtype == torch.float64
+    out = torch.empty((max(B, 1), int(K), T), dtype=torch.float64, device=dev)
+    win = torch.empty((max(B, 1), int(K), T), dtype=torch.int32, device=dev) if winners else None
+    status = torch.zeros(max(B, 1), dtype=torch.uint8, device=dev)
+    nbytes = 0
+    if max_points > _lib.LS_LDS_NMAX:
+        if work is None:
+            work = torch.empty(landscape_work_bytes(B, max_points, K, T)[0], dtype=torch.uint8, device=dev)
+        nbytes = work.numel()
+    rc = _lib.lib().tlc_landscape(C.c_int32(B), _lib.ptr(offs), _lib.ptr(pts) if pts.numel() else None, C.c_int32(T), _lib.ptr(ts),
+                                  C.c_int32(int(K)), C.c_int64(max_points), _lib.ptr(out), _lib.ptr(win), _lib.ptr(status),
+                                  _lib.ptr(work) if nbytes else None, C.c_int64(nbytes), _lib.stream_ptr())
+    _lib.check(rc, "tlc_landscape")
+    return out[:B], (win[:B] if winners else None), status[:B]
+
+
+@_lib.on_device_of
+def landscape_vjp(pts, offs, ts, K, winner, grad_out):
+    """d (sum grad_out * landscape) / d pts -> float64[sum n, 2] (tlc_landscape_vjp): winner int32[B, K, T] is `landscape`'s output,
+    grad_out float64[B, K, T].  A +-1 selection summed in one fixed order by one owner per point."""
+    B, T, max_points = _landscape_sizes("landscape_vjp", pts, offs, ts, K)
+    torch = _lib.require_gpu()
+    pts, offs, ts = pts.contiguous(), offs.contiguous(), ts.contiguous()
+    winner, grad_out = winner.contiguous(), grad_out.contiguous()
+    assert pts.dtype == torch.float64 and offs.dtype == torch.int64 and ts.dtype == torch.float64
+    assert winner.dtype == torch.int32 and grad_out.dtype == torch.float64
+    assert winner.numel() == B * int(K) * T and grad_out.numel() == B * int(K) * T
+    out = torch.zeros((max(pts.shape[0], 1), 2), dtype=torch.float64, device=offs.device)
+    rc = _lib.lib().tlc_landscape_vjp(C.c_int32(B), _lib.ptr(offs), _lib.ptr(pts) if pts.numel() else None, C.c_int32(T), _lib.ptr(ts),
+                                      C.c_int32(int(K)), C.c_int64(max_points), _lib.ptr(winner), _lib.ptr(grad_out), _lib.ptr(out),
+                                      _lib.stream_ptr())
+    _lib.check(rc, "tlc_landscape_vjp")
+    return out[:pts.shape[0]]
+
+
 # size tiers of the PD kernel (csrc/tlc_kernels.h) and what the library's timing slots bracket
 TIER_LIMITS = [("pd_tier_small", 64, 128), ("pd_tier_mid", 128, 256), ("pd_tier_medium", 512, 1024), ("pd_tier_large", 2048, 4096)]
 TINY_LIMITS = (16, 24)          # TLC_T_NMAX / TLC_T_MMAX: lane-per-subgraph kernel (plain image batches at resolution 5)

@@ -1135,6 +1135,25 @@ def sliced_wasserstein(xoff, X, yoff, Y, dirs=None, scale=None, M=50, want_grad=
     return dict(loss=loss[:B], grad_x=None if gx is None else gx[:nx], grad_y=None if gy is None else gy[:ny], status=status[:B])
 
 
+def landscape(pts, offs, ts, K=5, winners=True, work=None, check=True):
+    """Persistence landscapes [B, K, T] of packed diagrams (include/tlcgnn.h defines them; `engine.landscape`): pts [sum n, 2] of any
+    float dtype, offs int64[B + 1] (None: one diagram), ts [T] sample values, on one CUDA device; computed in float64.
+    -> dict(out float64[B, K, T], winner int32[B, K, T] or None, status uint8[B]).  A diagram with a NaN / Inf coordinate (status 3)
+    raises RuntimeError naming it unless check=False."""
+    import torch
+    from . import engine
+    if not torch.is_tensor(ts) or ts.dim() != 1:
+        raise ValueError("landscape: ts should be a 1-D tensor, not %s" % (tuple(ts.shape) if torch.is_tensor(ts) else type(ts).__name__,))
+    if offs is None:
+        offs = torch.tensor([0, pts.shape[0]], dtype=torch.int64, device=pts.device)
+    out, win, status = engine.landscape(pts.detach().to(torch.float64).reshape(-1, 2), offs.to(torch.int64), ts.detach().to(torch.float64), K,
+                                        winners=winners, work=work)
+    if check and status.numel() and bool((status != 0).any()):
+        bad = torch.nonzero(status).flatten()
+        raise RuntimeError("landscape: diagram %d has status %d (3 = a NaN / Inf coordinate)" % (int(bad[0]), int(status[bad[0]])))
+    return dict(out=out, winner=win, status=status)
+
+
 def capture(fn, warmup=2):
     """HIP graph of a forward closure: `fn` (C-ABI launches on the current stream, outputs in caller-held or graph-pool buffers,
     no host synchronisation inside) is warmed up on a side stream, captured once, and replayed with `.replay()`.

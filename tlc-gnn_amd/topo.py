@@ -1,7 +1,7 @@
 """Topological layers on a LEARNED filtration: the exact extended persistence of a packed batch of graphs as a differentiable
 function of the node values f, composed with the imager and the Wasserstein loss of `autograd`.
 
-    f (an MLP on node features, an HKS time, ...)  ->  diagrams(f, ...)  ->  images(...) / wasserstein_to(...) /
+    f (an MLP on node features, an HKS time, ...)  ->  diagrams(f, ...)  ->  images(...) / landscapes(...) / wasserstein_to(...) /
                                                        sliced_wasserstein_to(...) / bottleneck_to(...)  ->  loss.backward()
 
 `hks_filtration(time, ...)` is the second of these filtrations: the normalised heat-kernel signature as a differentiable function of its
@@ -100,6 +100,22 @@ def images(f, node_offs, edge_offs, edges, which="ord0+ext1", res=5, pd_large="h
     check_which(which)
     pts, offs = _select(f, node_offs, edge_offs, edges, which, pd_large)
     return autograd.diagram_image(pts, offs, res, imager=imager, grad=grad)
+
+
+def landscapes(f, node_offs, edge_offs, edges, ts, K=5, which="ord0+ext1", pd_large="host"):
+    """[B, K, T] persistence landscapes of every graph's diagram `which` at the sample values ts [T] (a 1-D tensor without grad) -- the
+    K largest tent values min(t - birth, death - t) > 0 at every sample, `autograd.diagram_landscape` -- as a differentiable function
+    of f.  The sibling of `images` without a sigma or a ramp: the gradient of a cell reaches the one node value behind the birth or
+    the death of the point that attains it.  Points of zero persistence are never present."""
+    check_which(which)
+    if not torch.is_tensor(ts) or ts.dim() != 1:
+        raise ValueError("landscapes: ts should be a 1-D tensor of sample values")
+    if ts.requires_grad:
+        raise ValueError("landscapes: ts requires grad, but the samples get no gradient (detach them)")
+    if not 1 <= int(K) <= _lib.LS_KMAX or not 1 <= ts.numel() <= _lib.LS_TMAX:
+        raise ValueError("landscapes: K = %d outside 1 .. %d or %d samples outside 1 .. %d" % (int(K), _lib.LS_KMAX, ts.numel(), _lib.LS_TMAX))
+    pts, offs = _select(f, node_offs, edge_offs, edges, which, pd_large)
+    return autograd.diagram_landscape(pts, offs, ts, K=K)
 
 
 def wasserstein_to(f, node_offs, edge_offs, edges, target_pts, target_offs, which="ord0+ext1", order=2, pd_large="host", w2_large="refuse"):
