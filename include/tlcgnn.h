@@ -1040,6 +1040,75 @@ int tlc_landscape(int32_t n_dgms, const int64_t* d_offs, const double* d_pts, in
 int tlc_landscape_vjp(int32_t n_dgms, const int64_t* d_offs, const double* d_pts, int32_t T, const double* d_ts, int32_t K,
                       int64_t max_points, const int32_t* d_winner, const double* d_grad_out, double* d_grad_pts, void* stream);
 
+/* ---- Gram matrices of persistence diagram kernels and their gradient (csrc/dgm_gram.hip) --------------------------
+ * The persistence scale-space kernel (Reininghaus et al. 2015) and the persistence weighted Gaussian kernel (Kusano et al. 2016)
+ * between packed diagrams: every diagram of X against every diagram of Y (TLC_DG_ALL) or diagram i against diagram i (TLC_DG_PAIRED).
+ *
+ * THE FUNCTION.  X: nx diagrams, x_offs int64[nx + 1], x_pts float64[sum n, 2] rows (birth, death), x_w float64[sum n] or NULL (every
+ * weight 1); Y likewise.  gamma > 0, scale finite; mirror = 1 with TLC_DG_MIRROR, else 0.  For p in X_i and q in Y_j:
+ *     e1(p, q) = exp(-gamma * ((p.b - q.b)^2 + (p.d - q.d)^2))        e2(p, q) = exp(-gamma * ((p.b - q.d)^2 + (p.d - q.b)^2))
+ *     k(X_i, Y_j) = scale * sum_p sum_q w_p w_q (e1 - mirror * e2)
+ *   PSS with bandwidth sigma: gamma = 1 / (8 sigma), scale = 1 / (8 pi sigma), TLC_DG_MIRROR, no weights.  PWG: gamma = 1 / (2 s^2),
+ *   scale = 1, no mirror, w = arctan(C * pers^p) made by the caller.
+ * d_out float64[nx, ny] (ALL) or float64[nx] (PAIRED, nx == ny).  TLC_DG_SYMMETRIC (ALL only, Y the same buffers as X): only j >= i
+ *   is computed and stored to [i, j] and [j, i]; the upper triangle and the diagonal equal the general call on a copy of X bit for bit.
+ * A pair with an empty diagram gives +0.0.
+ * d_status_x uint8[nx], d_status_y uint8[ny] (written by tlc_dgm_gram): 0 ok, 3 = a NaN / Inf coordinate or weight in that diagram:
+ *   its row (column) of d_out is NaN, its gradient rows are zero, and no other entry changes.
+ *
+ * THE ORDER, operation by operation (fp64, round to nearest, no fused multiply-add, exp = the device library's).  ng = -gamma.
+ *   One summand t(p, q):  db = p.b - q.b;  dd = p.d - q.d;  e = exp(ng * (db * db + dd * dd));  with the mirror:  xb = p.b - q.d;
+ *     xd = p.d - q.b;  e = e - exp(ng * (xb * xb + xd * xd));  with weights:  t = (w_p * w_q) * e;  without:  t = e.
+ *   X_i (n points) is cut into max(1, ceil(n / TLC_DG_SLICE)) slices of TLC_DG_SLICE points and Y_j (m points) into
+ *     max(1, ceil(m / TLC_DG_GROUP)) groups of TLC_DG_GROUP points, a group into chunks of 64 points, all from the diagram's own start.
+ *   Unit (slice s, group g):  P = +0.0;  for the group's chunks ascending:  for l = 0 .. 63:  a[l] = +0.0, and if point q = chunk
+ *     start + l exists, for p of the slice ascending:  a[l] = a[l] + t(p, q);  FOLD:  for d = 32, 16, 8, 4, 2, 1:  for every l < d at
+ *     once:  a[l] = a[l] + a[l + d];  P = P + a[0].
+ *   R = +0.0;  for s ascending:  for g ascending:  R = R + P(s, g).  d_out = scale * R  (an empty diagram: +0.0; status 3: NaN).
+ *   The order is a function of (n, m) alone: d_out[i, j] is the same bits alone, in any batch, in ALL or PAIRED mode, with any
+ *   workspace from *least up, and from run to run.  No floating-point atomics.
+ *
+ * THE GRADIENT IN THE FIRST ARGUMENT (tlc_dgm_gram_vjp).  d_grad_out float64[nx, ny] or [nx]; d_grad_pts_x float64[sum n, 2] and,
+ * exactly when x_w is given, d_grad_w_x float64[sum n]: every row written.  d_status_x / d_status_y are INPUTS here, the forward's.
+ *   For point p of X_i, one owner (a lane):  gb = gd = gw = +0.0;  for j ascending (PAIRED: j = i only), skipping status 3:
+ *     ib = id = iw = +0.0;  for q of Y_j ascending:  db, dd as above;  t1 = w_q * exp(ng * (db * db + dd * dd))  (no weights: the exp);
+ *       without the mirror:  ib = ib - db * t1;  id = id - dd * t1;  iw = iw + t1;
+ *       with it:  xb, xd as above;  t2 = w_q * exp(ng * (xb * xb + xd * xd));  ib = ib + (xb * t2 - db * t1);
+ *                 id = id + (xd * t2 - dd * t1);  iw = iw + (t1 - t2).
+ *     G = d_grad_out[i, j];  gb = gb + G * ib;  gd = gd + G * id;  gw = gw + G * iw.
+ *   c = scale * w_p (no weights: scale);  grad_pts = ((c * (2 * gamma)) * gb, (c * (2 * gamma)) * gd);  grad_w = scale * gw.
+ *   A diagram of X with status 3 gets zero rows.  The order for a row is a function of the sizes of Y's diagrams alone.  The gradient
+ *   in the second argument is this entry with the roles swapped and d_grad_out transposed (|p - q~| = |q - p~|); for Y = X the caller
+ *   passes G + G^T (PAIRED: 2 G).  TLC_DG_SYMMETRIC is accepted and changes nothing here.
+ *
+ * max_nx_points / max_ny_points: upper bounds of one diagram's points.  Both entries read the offsets back once and synchronise the
+ * stream before they launch anything; an entry that uses its prefix arrays (below) uploads them in one copy and synchronises once more.
+ * tlc_dgm_gram_work_bytes (host arithmetic, one size for both entries): the d_work that runs every diagram pair in one launch, at most
+ * 1 GiB of partials; 0 when max_nx_points <= 64 and max_ny_points <= TLC_DG_GROUP; -1 for a negative size, any flag word the entries
+ * refuse, or a size beyond int64.  *least (may be NULL): the size that runs the pairs of one X diagram at a time.  An entry asks for
+ * d_work only where it uses it: tlc_dgm_gram when a pair can have more than one unit (max_nx_points > TLC_DG_SLICE or max_ny_points >
+ * TLC_DG_GROUP), tlc_dgm_gram_vjp for its chunk prefix (PAIRED with max_nx_points > 64); otherwise d_work may be NULL.
+ * TLC_ERR_INVALID_ARG, nothing launched and nothing written: null required pointers, negative sizes, gamma not finite or not > 0,
+ * scale not finite, unknown flag bits, not exactly one of ALL / PAIRED, PAIRED with nx != ny, SYMMETRIC without ALL, with different
+ * X and Y buffers or with nx != ny or max_nx_points != max_ny_points, offsets that are negative or decrease, a diagram above its
+ * max_*_points, a d_work the entry uses below *least, tlc_dgm_gram_vjp with exactly one of x_w and d_grad_w_x.
+ * nx == 0 or ny == 0: TLC_OK (the VJP with ny == 0 writes zero rows). */
+#define TLC_DG_ALL        0x1u
+#define TLC_DG_PAIRED     0x2u
+#define TLC_DG_SYMMETRIC  0x4u
+#define TLC_DG_MIRROR     0x8u
+#define TLC_DG_SLICE      1024   /* points of a slice of the first argument */
+#define TLC_DG_GROUP      1024   /* points of a group of the second argument: 16 chunks of 64 */
+int64_t tlc_dgm_gram_work_bytes(int32_t nx, int32_t ny, int64_t max_nx_points, int64_t max_ny_points, uint32_t flags, int64_t* least);
+int tlc_dgm_gram(int32_t nx, const int64_t* x_offs, const double* x_pts, const double* x_w, int32_t ny, const int64_t* y_offs,
+                 const double* y_pts, const double* y_w, double gamma, double scale, uint32_t flags, int64_t max_nx_points,
+                 int64_t max_ny_points, double* d_out, uint8_t* d_status_x, uint8_t* d_status_y, void* d_work, int64_t work_bytes,
+                 void* stream);
+int tlc_dgm_gram_vjp(int32_t nx, const int64_t* x_offs, const double* x_pts, const double* x_w, int32_t ny, const int64_t* y_offs,
+                     const double* y_pts, const double* y_w, double gamma, double scale, uint32_t flags, int64_t max_nx_points,
+                     int64_t max_ny_points, const uint8_t* d_status_x, const uint8_t* d_status_y, const double* d_grad_out,
+                     double* d_grad_pts_x, double* d_grad_w_x, void* d_work, int64_t work_bytes, void* stream);
+
 /* ---- what `loss.backward()` runs through the PDGNN layer and the edge head ---------------------------
  * (Knowledge_Distillation/train_Teacher_Model.py:55-62 through gat_conv.py:113-216 and Teacher_model.py:53-59.)
  * tlc_gat_layer_bwd: gradients of one layer, same operands as tlc_gat_layer_fwd.  Nothing of the forward is kept: the node rows,

@@ -169,7 +169,7 @@ class Teacher_Model(torch.nn.Module):
         return not (torch.is_grad_enabled() and (x0.requires_grad or any(p.requires_grad for p in self.parameters())))
 
     def forward(self, x0, edge_index0, PD, kernel='sliced', M=50, p=1, pair_diagonal=False, draw_fig=False, fig_name='',
-                compute_loss=True, grad_PI=True, graph_ptr=None, edge_ptr=None, pd_ptr=None, csr=None, w2_large='refuse'):
+                compute_loss=True, grad_PI=True, graph_ptr=None, edge_ptr=None, pd_ptr=None, csr=None, w2_large='refuse', sigma=1.0):
         """Reference signature.  compute_loss=True needs kernel='wasserstein' (p = 1 or 2) and returns
         loss0 (differentiable), loss_xy0, loss_xd0, loss_yd0 like :63-66.  pair_diagonal=False (training, :64): every target
         point is matched, loss_yd0 is 0 (wasserstein.py:330-372, num_models=1); pair_diagonal=True (evaluation, :66): the
@@ -177,6 +177,9 @@ class Teacher_Model(torch.nn.Module):
         kernel='sliced_wasserstein': the reference's 'sliced' branch (:110-124, the sliced Wasserstein distance over M directions,
         `tlc_sliced_wasserstein`) with the return repaired: loss0 differentiable, loss_xy0 / loss_xd0 / loss_yd0 zeros (the branch
         computes no parts); p and pair_diagonal have no effect there.  kernel='sliced' itself (the signature's default) keeps raising.
+        kernel='pss' (not in the reference): loss0 = the sum over the graphs of the squared persistence scale-space kernel distance with
+        bandwidth `sigma` between the predicted and the target diagram (`autograd.diagram_kernel_distance`, tlc_dgm_gram); the three
+        parts are zeros as for 'sliced_wasserstein'.  Smooth, no assignment, no cap on the points.
 
         x0 [n,1] filtration, edge_index0 [2, m+n] with the n self loops LAST (train_Teacher_Model.py:43-44).
         Block-diagonal batches: pass graph_ptr (int64 [B+1] node offsets) and edge_ptr (int64 [B+1] offsets into the
@@ -190,8 +193,8 @@ class Teacher_Model(torch.nn.Module):
         """
         if draw_fig:
             raise NotImplementedError("Teacher_Model (HIP): draw_fig=False only")
-        if compute_loss and kernel not in ('wasserstein', 'sliced_wasserstein'):
-            raise NotImplementedError("Teacher_Model (HIP): compute_loss needs kernel='wasserstein' or kernel='sliced_wasserstein' (the "
+        if compute_loss and kernel not in ('wasserstein', 'sliced_wasserstein', 'pss'):
+            raise NotImplementedError("Teacher_Model (HIP): compute_loss needs kernel='wasserstein', 'sliced_wasserstein' or 'pss' (the "
                                       "reference's 'sliced' branch cannot run: Teacher_model.py:110-123 ends in names that were never "
                                       "bound, :139; kernel='sliced_wasserstein' is that branch with the return repaired)")
         t1 = time.time()
@@ -243,6 +246,11 @@ class Teacher_Model(torch.nn.Module):
                 raise ValueError("Teacher_Model: pd_ptr needs edge_ptr with the same number of graphs")
             if kernel == 'sliced_wasserstein':                                                     # :110-124
                 loss0 = autograd.sliced_diagram_loss(x, PD.to(torch.float64), M=M, xoff=xoff, yoff=yoff).sum().reshape(1)
+                loss_xy0, loss_xd0, loss_yd0 = (torch.zeros(1, dtype=loss0.dtype, device=loss0.device) for _ in range(3))
+            elif kernel == 'pss':
+                one = torch.tensor([0, int(PD.shape[0])], dtype=torch.int64, device=x.device)
+                loss0 = autograd.diagram_kernel_distance(x, torch.tensor([0, m], dtype=torch.int64, device=x.device) if xoff is None else xoff,
+                                                         PD.to(torch.float64), one if yoff is None else yoff, kernel='pss', sigma=sigma).sum().reshape(1)
                 loss_xy0, loss_xd0, loss_yd0 = (torch.zeros(1, dtype=loss0.dtype, device=loss0.device) for _ in range(3))
             else:
                 parts = autograd.diagram_loss(x, PD.to(torch.float64), order=p, xoff=xoff, yoff=yoff, infer=bool(pair_diagonal), large=w2_large)

@@ -41,6 +41,7 @@ BN_WAVE_NMAX, BN_NMAX = 512, 4096                                   # TLC_BN_*: 
 PI_MAX_RES, PI_GRAD_WEIGHT, PI_GRAD_FULL = 128, 0, 1                # TLC_PI_*: the general imager of csrc/pi_general.hip
 PI_SLICE, PI_CHUNK, PI_GROUP = 1024, 32, 32                         # points per K-slice / per LDS chunk, K-split diagrams per launch
 LS_WAVE_NMAX, LS_LDS_NMAX, LS_KMAX, LS_TMAX = 64, 4096, 16, 4096    # TLC_LS_*: the size classes of csrc/landscape.hip by n, the most levels and samples
+DG_ALL, DG_PAIRED, DG_SYMMETRIC, DG_MIRROR, DG_SLICE, DG_GROUP = 0x1, 0x2, 0x4, 0x8, 1024, 1024   # TLC_DG_*: the layouts of csrc/dgm_gram.hip and its cuts
 DIST_WAVE_NMAX, DIST_WG_NMAX, DIST_WG_MMAX, DIST_WORK_FALLBACKS_OFF = 64, 2048, 4096, 64   # TLC_DIST_*: the size classes of csrc/dist_filt.hip
 SEG_LANE_MAX, SEG_WAVE_MAX, SEG_WG_THREADS = 16, 2048, 256           # TLC_SEG_*: the size classes of csrc/vic_grad.hip by segment length
 GNN_ACT_NONE, GNN_ACT_RELU, GNN_ACT_PRELU, GNN_ROWS = 0, 1, 2, 64      # TLC_GNN_ACT_*; GN_ROWS of csrc/gnn_layers.hip: node rows per group
@@ -67,6 +68,7 @@ SYMBOLS = [
     "tlc_bottleneck_matching",
     "tlc_pi_image_work_bytes", "tlc_pi_image", "tlc_pi_image_vjp",
     "tlc_landscape_work_bytes", "tlc_landscape", "tlc_landscape_vjp",
+    "tlc_dgm_gram_work_bytes", "tlc_dgm_gram", "tlc_dgm_gram_vjp",
     "tlc_graph_components_work_bytes", "tlc_graph_components",
     "tlc_dist_filtration_work_bytes", "tlc_dist_filtration_vjp_work_bytes", "tlc_dist_filtration", "tlc_dist_filtration_vjp",
     "tlc_packed_edge_lookup", "tlc_segment_index_work_bytes", "tlc_segment_index", "tlc_segment_sum_work_bytes", "tlc_segment_sum_f64",
@@ -264,6 +266,12 @@ def lib():
         L.tlc_landscape.argtypes = ([C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int64] + [C.c_void_p] * 4
                                     + [C.c_int64, C.c_void_p])
         L.tlc_landscape_vjp.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int64] + [C.c_void_p] * 4
+        L.tlc_dgm_gram_work_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_uint32, C.POINTER(C.c_int64)]
+        L.tlc_dgm_gram_work_bytes.restype = C.c_int64
+        L.tlc_dgm_gram.argtypes = ([C.c_int32] + [C.c_void_p] * 3 + [C.c_int32] + [C.c_void_p] * 3 + [C.c_double, C.c_double, C.c_uint32, C.c_int64,
+                                   C.c_int64] + [C.c_void_p] * 4 + [C.c_int64, C.c_void_p])
+        L.tlc_dgm_gram_vjp.argtypes = ([C.c_int32] + [C.c_void_p] * 3 + [C.c_int32] + [C.c_void_p] * 3 + [C.c_double, C.c_double, C.c_uint32, C.c_int64,
+                                       C.c_int64] + [C.c_void_p] * 6 + [C.c_int64, C.c_void_p])
         L.tlc_graph_components_work_bytes.argtypes = [C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_int64)]
         L.tlc_graph_components.argtypes = [C.c_void_p] * 3 + [C.c_int64] * 4 + [C.c_void_p] * 5 + [C.c_int64, C.c_void_p]
         # the scratch sizes of the entries that take a bare d_work (csrc/scratch_layouts.h)

@@ -4,7 +4,7 @@
 classifier of Knowledge_Distillation/ConvCurv_GIN.py: CurvConv and NcLinear (nc_curv.hip).
 
 torch.autograd only carries the graph: every forward and every backward below is one C-ABI call (`tlc_gat_layer_fwd/_bwd`,
-`tlc_msg_layer_fwd/_bwd`, `tlc_edge_head_fwd/_bwd`, `tlc_w2_partial_matching`, `tlc_sliced_wasserstein`, `tlc_bottleneck_matching`, `tlc_pi_raster` / `tlc_pi_raster_wgrad`, `tlc_pi_image` / `tlc_pi_image_vjp`, `tlc_landscape` / `tlc_landscape_vjp`, `tlc_hks_batch_dt` + `tlc_hks_large_batch_dt`) or a few (`tlc_gemm_f32` /
+`tlc_msg_layer_fwd/_bwd`, `tlc_edge_head_fwd/_bwd`, `tlc_w2_partial_matching`, `tlc_sliced_wasserstein`, `tlc_bottleneck_matching`, `tlc_pi_raster` / `tlc_pi_raster_wgrad`, `tlc_pi_image` / `tlc_pi_image_vjp`, `tlc_landscape` / `tlc_landscape_vjp`, `tlc_dgm_gram` / `tlc_dgm_gram_vjp`, `tlc_hks_batch_dt` + `tlc_hks_large_batch_dt`) or a few (`tlc_gemm_f32` /
 `tlc_spmm_csr_f32` / `tlc_gemm_tn_f32`, `tlc_lp_decode_fused_f32` / `tlc_lp_decode_bwd_f32` / `tlc_lp_decode_bwd_pi_f32`, `tlc_segment_sum_f64`); nothing is recomputed with torch ops
 and there is no CPU path.
 """
@@ -241,6 +241,46 @@ class DiagramLandscape(torch.autograd.Function):
         return g.to(ctx.dtype), None, None, None
 
 
+class DiagramGram(torch.autograd.Function):
+    """The Gram matrix of a diagram kernel (include/tlcgnn.h defines it): `tlc_dgm_gram` forward, `tlc_dgm_gram_vjp` backward -- once
+    per side that needs a gradient, the second side with the roles swapped and the upstream transposed; y None (X against itself): one
+    call with G + G^T (paired: 2 G).  Computed in float64 whatever the dtypes."""
+
+    @staticmethod
+    def forward(ctx, x, xoff, wx, y, yoff, wy, gamma, scale, mirror, paired):
+        def side(pts, offs, w):
+            return (pts.detach().to(torch.float64).reshape(-1, 2).contiguous(), offs.to(torch.int64).contiguous(),
+                    None if w is None else w.detach().to(torch.float64).reshape(-1).contiguous())
+        same = y is None
+        X = side(x, xoff, wx)
+        Y = X if same else side(y, yoff, wy)
+        out, sx, sy = engine.dgm_gram(*X, *Y, gamma, scale, mirror, paired=paired, symmetric=same and not paired)
+        ops.dgm_raise_on_status("diagram_gram", sx, None if same else sy)
+        ctx.save_for_backward(*X, *Y, sx, sy)
+        ctx.params = (gamma, scale, mirror, paired, same)
+        ctx.dtypes = tuple(None if t is None else t.dtype for t in (x, wx, y, wy))
+        return out.to(x.dtype)
+
+    @staticmethod
+    def backward(ctx, gout):
+        xp, xo, xw, yp, yo, yw, sx, sy = ctx.saved_tensors
+        gamma, scale, mirror, paired, same = ctx.params
+        g = gout.to(torch.float64).contiguous()
+        need = ctx.needs_input_grad
+        gx = gwx = gy = gwy = None
+        if same:
+            if need[0] or need[2]:
+                gx, gwx = engine.dgm_gram_vjp(xp, xo, xw, xp, xo, xw, gamma, scale, mirror, sx, sx, 2.0 * g if paired else g + g.t(), paired=paired)
+        else:
+            if need[0] or need[2]:
+                gx, gwx = engine.dgm_gram_vjp(xp, xo, xw, yp, yo, yw, gamma, scale, mirror, sx, sy, g, paired=paired)
+            if need[3] or need[5]:
+                gy, gwy = engine.dgm_gram_vjp(yp, yo, yw, xp, xo, xw, gamma, scale, mirror, sy, sx, g if paired else g.t().contiguous(),
+                                              paired=paired)
+        cast = lambda t, k, on: t.to(ctx.dtypes[k]) if (t is not None and on) else None        # noqa: E731
+        return (cast(gx, 0, need[0]), None, cast(gwx, 1, need[2]), cast(gy, 2, need[3]), None, cast(gwy, 3, need[5]), None, None, None, None)
+
+
 class ExtendedPersistence(torch.autograd.Function):
     """The exact extended persistence as a differentiable function of the filtration values: (up, down, one, ext0, counts) in the slot
     layout of `engine.pd_from_filtration`, the same values bit for bit.  Every coordinate is a copy of one f[v], so the backward is a
@@ -465,6 +505,33 @@ def diagram_landscape(pd_hat, offs=None, ts=None, K=5):
     if offs is None:
         offs = torch.tensor([0, pd_hat.shape[0]], dtype=torch.int64, device=pd_hat.device)
     return DiagramLandscape.apply(pd_hat, offs, ts, K)
+
+
+def diagram_gram(x, xoff=None, y=None, yoff=None, wx=None, wy=None, kernel="pss", sigma=1.0, paired=False):
+    """The Gram matrix of a kernel between packed persistence diagrams (`ops.diagram_gram`), [Bx, By] or with paired=True [B], in x's
+    dtype; differentiable in both point sets and both weight vectors.  y=None: X against itself (the symmetric call).  kernel 'pss' /
+    'gauss' and sigma: `ops.dgm_kernel_params`; sigma is a Python number and gets no gradient.  A NaN / Inf coordinate or weight
+    raises RuntimeError naming the diagram."""
+    gamma, scale, mirror = ops.dgm_kernel_params(kernel, sigma)
+    if y is None and (yoff is not None or wy is not None):
+        raise ValueError("diagram_gram: yoff / wy without y")
+    if xoff is None:
+        xoff = torch.tensor([0, x.shape[0]], dtype=torch.int64, device=x.device)
+    if y is not None and yoff is None:
+        yoff = torch.tensor([0, y.shape[0]], dtype=torch.int64, device=y.device)
+    return DiagramGram.apply(x, xoff, wx, y, yoff, wy, gamma, scale, mirror, bool(paired))
+
+
+def diagram_kernel_distance(x, xoff, y, yoff, wx=None, wy=None, kernel="pss", sigma=1.0):
+    """[B]: the SQUARED kernel distance k(X_i, X_i) + k(Y_i, Y_i) - 2 k(X_i, Y_i) between the diagrams of two packed batches, from three
+    paired `diagram_gram` calls; differentiable like them.  Squared because the root has no gradient at 0.  Smooth everywhere, no
+    assignment, no sort and no cap on the points -- the cheap sibling of `diagram_loss` and `sliced_diagram_loss`.  The three terms
+    are formed and subtracted in float64 (they cancel where the diagrams agree); the result is cast to x's dtype."""
+    x64, y64 = x.to(torch.float64), y.to(torch.float64)
+    kxx = diagram_gram(x64, xoff, wx=wx, kernel=kernel, sigma=sigma, paired=True)
+    kyy = diagram_gram(y64, yoff, wx=wy, kernel=kernel, sigma=sigma, paired=True)
+    kxy = diagram_gram(x64, xoff, y64, yoff, wx=wx, wy=wy, kernel=kernel, sigma=sigma, paired=True)
+    return (kxx + kyy - 2.0 * kxy).to(x.dtype)
 
 
 def gat_layer(x, wl, att, wij, bias, rowptr, src, prelu_slope=-1.0):

@@ -321,3 +321,39 @@ struct TlcHksSparseScratch {
         total = o + all_panel_bytes;
     }
 };
+
+// tlc_dgm_gram / tlc_dgm_gram_vjp (dgm_gram.hip).  In BYTES, carved by the shared carver (handed in, as for the landscape).  A diagram of
+// n points is cut into slices_of(n) slices of SLICE points as the first argument and into groups_of(n) groups of GROUP points as the
+// second; a unit is one (slice, group) of one diagram pair.  The unit-prefix arrays int64[nx + 1] | int64[ny + 1], contiguous (uploaded by the entry;
+// the VJP keeps the 64-point chunk prefix of X in the first) exist when a declared size leaves the one-unit case (max_nx_points > CHUNK
+// or max_ny_points > GROUP); the unit partials f64[slots] behind them when a pair can have more than one unit (max_nx_points > SLICE
+// or max_ny_points > GROUP).  `least` holds the partials of the rows of one X diagram (ALL: against every Y diagram; PAIRED: its one
+// pair), `total` those of every diagram, at most FULL_CAP bytes of them (but never below `least`).  Saturating: -1 sizes are the entry's.
+struct TlcDgmGramScratch {
+    static constexpr int64_t SLICE = 1024, GROUP = 1024, CHUNK = 64, SAT = INT64_MAX / 64, FULL_CAP = (int64_t)1 << 30;
+    static int64_t slices_of(int64_t n) { return n > SLICE ? (n + SLICE - 1) / SLICE : 1; }
+    static int64_t groups_of(int64_t n) { return n > GROUP ? (n + GROUP - 1) / GROUP : 1; }
+    static int64_t chunks_of(int64_t n) { return (n + CHUNK - 1) / CHUNK; }
+    static int64_t sat_mul(int64_t a, int64_t b) { return a && b > SAT / a ? SAT : std::min(SAT, a * b); }
+    int64_t xpre = 0, ypre = 0, partial = 0, head = 0, row_slots = 0, least = 0, total = 0;
+    bool prefixes = false, wide = false;
+    template <class Carver>
+    TlcDgmGramScratch(int64_t nx, int64_t ny, int64_t max_nx_points, int64_t max_ny_points, bool paired, Carver) {
+        prefixes = max_nx_points > CHUNK || max_ny_points > GROUP;
+        wide = max_nx_points > SLICE || max_ny_points > GROUP;
+        if (!prefixes || nx < 1 || ny < 1) { prefixes = wide = false; return; }
+        Carver W;
+        xpre = (int64_t)W.take(nx + ny + 1, 8);                 // (one block of nx + 1 and ny + 1 entries: one upload)
+        ypre = xpre + (nx + 1) * 8;
+        partial = (int64_t)W.bytes() - 256;
+        head = (int64_t)W.bytes();                               // (with the 256 of tlc_align256)
+        least = total = head;
+        if (!wide) return;
+        const int64_t per_pair = sat_mul(slices_of(max_nx_points), groups_of(max_ny_points));
+        row_slots = paired ? per_pair : sat_mul(per_pair, ny);
+        const int64_t all = sat_mul(row_slots, nx);
+        least = std::min(SAT, head + sat_mul(row_slots, 8));
+        total = std::max(least, head + std::min(sat_mul(all, 8), FULL_CAP));
+    }
+    int64_t slots_in(int64_t work_bytes) const { return wide ? (work_bytes - head) / 8 : 0; }
+};

@@ -990,6 +990,112 @@ def landscape_vjp(pts, offs, ts, K, winner, grad_out):
     return out[:pts.shape[0]]
 
 
+def dgm_gram_flags(mirror, paired, symmetric=False):
+    """The TLC_DG_* flag word of `dgm_gram` / `dgm_gram_vjp`."""
+    return ((_lib.DG_PAIRED if paired else _lib.DG_ALL) | (_lib.DG_SYMMETRIC if symmetric else 0) | (_lib.DG_MIRROR if mirror else 0))
+
+
+def dgm_gram_work_bytes(nx, ny, max_nx_points, max_ny_points, flags):
+    """(full, least) bytes of the workspace of `dgm_gram` and `dgm_gram_vjp` (tlc_dgm_gram_work_bytes): 0 while no diagram of X has more
+    than 64 points and none of Y more than _lib.DG_GROUP; any size from `least` up gives the same bits."""
+    least = C.c_int64(0)
+    full = _lib.lib().tlc_dgm_gram_work_bytes(C.c_int32(int(nx)), C.c_int32(int(ny)), C.c_int64(int(max_nx_points)), C.c_int64(int(max_ny_points)),
+                                              C.c_uint32(int(flags)), C.byref(least))
+    if full < 0:
+        _lib.check(1, "tlc_dgm_gram_work_bytes")
+    return int(full), int(least.value)
+
+
+def _dgm_gram_side(what, name, pts, offs, w):
+    """The checks of one side -> (B, max_points); the offsets are read once (offsets beyond the points would be read out of bounds)."""
+    import torch
+    assert pts.dtype == torch.float64 and offs.dtype == torch.int64 and pts.dim() == 2 and pts.shape[1] == 2
+    assert pts.is_contiguous() and offs.is_contiguous() and (w is None or (w.dtype == torch.float64 and w.is_contiguous()))
+    B = offs.numel() - 1
+    if B < 0:
+        raise ValueError("%s: %soff is empty" % (what, name))
+    if w is not None and w.shape != (pts.shape[0],):
+        raise ValueError("%s: w%s should hold one weight per point (%d), not shape %s" % (what, name, pts.shape[0], tuple(w.shape)))
+    max_points = 0
+    if B > 0:
+        end, max_points = torch.stack([offs[-1], (offs[1:] - offs[:-1]).max()]).tolist()
+        if end > pts.shape[0]:
+            raise ValueError("%s: the offsets of %s end at %d but there are %d points" % (what, name, end, pts.shape[0]))
+    return B, max(int(max_points), 0)
+
+
+def _dgm_gram_call(what, x, xoff, wx, y, yoff, wy, flags, work):
+    torch = _lib.require_gpu()
+    nx, max_nx = _dgm_gram_side(what, "x", x, xoff, wx)
+    if flags & _lib.DG_SYMMETRIC:
+        ny, max_ny = nx, max_nx
+    else:
+        ny, max_ny = _dgm_gram_side(what, "y", y, yoff, wy)
+    if (flags & _lib.DG_PAIRED) and nx != ny:
+        raise ValueError("%s: paired, but x holds %d diagrams and y %d" % (what, nx, ny))
+    nbytes = 0
+    full, _ = dgm_gram_work_bytes(nx, ny, max_nx, max_ny, flags)
+    if full > 0:
+        if work is None:
+            work = torch.empty(full, dtype=torch.uint8, device=xoff.device)
+        nbytes = work.numel()
+    sizes = (C.c_int64(max_nx), C.c_int64(max_ny))
+    # (the workspace travels with its pointer: it has to outlive the call that is made with it)
+    return nx, ny, sizes, work, (_lib.ptr(work) if nbytes else None, C.c_int64(nbytes), _lib.stream_ptr())
+
+
+def _dgm_gram_operands(x, xoff, wx, y, yoff, wy, nx, ny):
+    p = lambda t: _lib.ptr(t) if t is not None and t.numel() else None                    # noqa: E731
+    return (C.c_int32(nx), _lib.ptr(xoff), p(x), p(wx), C.c_int32(ny), _lib.ptr(yoff), p(y), p(wy))
+
+
+@_lib.on_device_of
+def dgm_gram(x, xoff, wx, y, yoff, wy, gamma, scale, mirror, paired=False, symmetric=False, work=None):
+    """k(X_i, Y_j) = scale * sum_p sum_q w_p w_q (e1 - mirror * e2) between packed diagrams (tlc_dgm_gram; csrc/dgm_gram.hip;
+    include/tlcgnn.h defines it and its summation order).
+
+    x float64[sum n, 2], xoff int64[Bx + 1], wx float64[sum n] or None (every weight 1), y / yoff / wy likewise (CUDA tensors);
+    symmetric=True: y, yoff and wy are not read, Y is X and only j >= i is computed.  work: an optional uint8 CUDA workspace.
+    -> (out float64[Bx, By], or [B] with paired=True; status_x uint8[Bx], status_y uint8[By]: 3 = a NaN / Inf coordinate or weight, the
+    diagram's row / column of out is NaN).  The offsets are read back once."""
+    torch = _lib.require_gpu()
+    if symmetric:
+        y, yoff, wy = x, xoff, wx
+    flags = dgm_gram_flags(mirror, paired, symmetric)
+    nx, ny, sizes, work, tail = _dgm_gram_call("dgm_gram", x, xoff, wx, y, yoff, wy, flags, work)
+    dev = xoff.device
+    out = torch.empty((max(nx, 1),) if paired else (max(nx, 1), max(ny, 1)), dtype=torch.float64, device=dev)
+    sx = torch.zeros(max(nx, 1), dtype=torch.uint8, device=dev)
+    sy = torch.zeros(max(ny, 1), dtype=torch.uint8, device=dev)
+    rc = _lib.lib().tlc_dgm_gram(*_dgm_gram_operands(x, xoff, wx, y, yoff, wy, nx, ny), C.c_double(float(gamma)), C.c_double(float(scale)),
+                                 C.c_uint32(flags), *sizes, _lib.ptr(out), _lib.ptr(sx), _lib.ptr(sy), *tail)
+    _lib.check(rc, "tlc_dgm_gram")
+    return (out[:nx] if paired else out[:nx, :ny]), sx[:nx], sy[:ny]
+
+
+@_lib.on_device_of
+def dgm_gram_vjp(x, xoff, wx, y, yoff, wy, gamma, scale, mirror, status_x, status_y, grad_out, paired=False, work=None):
+    """d (sum grad_out * gram) / d (x, wx) with Y held fixed (tlc_dgm_gram_vjp) -> (float64[sum n, 2], float64[sum n] or None without wx).
+    status_x / status_y: `dgm_gram`'s; grad_out float64[Bx, By] or [B].  The gradient in (y, wy) is this call with the roles swapped and
+    grad_out transposed."""
+    torch = _lib.require_gpu()
+    flags = dgm_gram_flags(mirror, paired, False)
+    nx, ny, sizes, work, tail = _dgm_gram_call("dgm_gram_vjp", x, xoff, wx, y, yoff, wy, flags, work)
+    grad_out, status_x, status_y = grad_out.contiguous(), status_x.contiguous(), status_y.contiguous()
+    assert grad_out.dtype == torch.float64 and grad_out.numel() == (nx if paired else nx * ny)
+    assert status_x.dtype == torch.uint8 and status_x.numel() == nx and status_y.dtype == torch.uint8 and status_y.numel() == ny
+    rows = x.shape[0]
+    gx = torch.zeros((max(rows, 1), 2), dtype=torch.float64, device=xoff.device)
+    gw = None if wx is None else torch.zeros(max(rows, 1), dtype=torch.float64, device=xoff.device)
+    if rows == 0:
+        return gx[:0], (None if gw is None else gw[:0])
+    p = lambda t: _lib.ptr(t) if t.numel() else None                                      # noqa: E731
+    rc = _lib.lib().tlc_dgm_gram_vjp(*_dgm_gram_operands(x, xoff, wx, y, yoff, wy, nx, ny), C.c_double(float(gamma)), C.c_double(float(scale)),
+                                     C.c_uint32(flags), *sizes, p(status_x), p(status_y), p(grad_out), _lib.ptr(gx), _lib.ptr(gw), *tail)
+    _lib.check(rc, "tlc_dgm_gram_vjp")
+    return gx[:rows], (None if gw is None else gw[:rows])
+
+
 # size tiers of the PD kernel (csrc/tlc_kernels.h) and what the library's timing slots bracket
 TIER_LIMITS = [("pd_tier_small", 64, 128), ("pd_tier_mid", 128, 256), ("pd_tier_medium", 512, 1024), ("pd_tier_large", 2048, 4096)]
 TINY_LIMITS = (16, 24)          # TLC_T_NMAX / TLC_T_MMAX: lane-per-subgraph kernel (plain image batches at resolution 5)

@@ -1154,6 +1154,67 @@ def landscape(pts, offs, ts, K=5, winners=True, work=None, check=True):
     return dict(out=out, winner=win, status=status)
 
 
+DGM_KERNELS = ("pss", "gauss")
+
+
+def dgm_kernel_params(kernel, sigma):
+    """-> (gamma, scale, mirror) of include/tlcgnn.h's function for a named kernel between diagrams: 'pss', the persistence scale-space
+    kernel with bandwidth sigma (gamma = 1 / (8 sigma), scale = 1 / (8 pi sigma), the mirror term); 'gauss', the plain Gaussian of the
+    persistence weighted Gaussian kernel (gamma = 1 / (2 sigma^2), scale = 1, no mirror; its weights are `pwg_weights`)."""
+    import math
+    sigma = float(sigma)
+    if not (math.isfinite(sigma) and sigma > 0.0):
+        raise ValueError("diagram kernel: sigma should be finite and > 0, not %r" % (sigma,))
+    if kernel == "pss":
+        return 1.0 / (8.0 * sigma), 1.0 / (8.0 * math.pi * sigma), True
+    if kernel == "gauss":
+        return 1.0 / (2.0 * sigma * sigma), 1.0, False
+    raise ValueError("diagram kernel: kernel should be one of %s, not %r" % (DGM_KERNELS, kernel))
+
+
+def pwg_weights(pts, C=1.0, p=1.0):
+    """arctan(C * persistence^p) per point of pts [n, 2], the weights of the persistence weighted Gaussian kernel (Kusano et al. 2016):
+    plain torch ops, so C and p may be tensors that require grad."""
+    import torch
+    return torch.atan(C * (pts[:, 1] - pts[:, 0]) ** p)
+
+
+def dgm_raise_on_status(what, status_x, status_y):
+    """RuntimeError naming the first diagram whose status is not 0 (3 = a NaN / Inf coordinate or weight)."""
+    import torch
+    for name, st in (("x", status_x), ("y", status_y)):
+        if st is not None and st.numel() and bool((st != 0).any()):
+            bad = int(torch.nonzero(st).flatten()[0])
+            raise RuntimeError("%s: diagram %d of %s has status %d (3 = a NaN / Inf coordinate or weight)" % (what, bad, name, int(st[bad])))
+
+
+def diagram_gram(x, xoff, y=None, yoff=None, wx=None, wy=None, kernel="pss", sigma=1.0, paired=False, work=None, check=True):
+    """The Gram matrix of a kernel between packed persistence diagrams (`engine.dgm_gram`; include/tlcgnn.h defines the function):
+    x [sum n, 2] of any float dtype with xoff int64[Bx + 1] (None: one diagram) against y / yoff, every pair ([Bx, By]) or, with
+    paired=True, diagram i against diagram i ([B]); computed in float64.  y=None: X against itself -- symmetric, only j >= i computed
+    (paired: k(X_i, X_i)).  kernel / sigma: `dgm_kernel_params`; wx / wy: optional weights per point (`pwg_weights`).
+    -> dict(out, status_x, status_y).  A diagram with a NaN / Inf coordinate or weight (status 3) raises RuntimeError naming it unless
+    check=False (its row / column is NaN then)."""
+    import torch
+    from . import engine
+    gamma, scale, mirror = dgm_kernel_params(kernel, sigma)
+    if y is None and (yoff is not None or wy is not None):
+        raise ValueError("diagram_gram: yoff / wy without y")
+
+    def side(pts, offs, w):
+        pts = pts.detach().to(torch.float64).reshape(-1, 2).contiguous()
+        if offs is None:
+            offs = torch.tensor([0, pts.shape[0]], dtype=torch.int64, device=pts.device)
+        return pts, offs.to(torch.int64).contiguous(), None if w is None else w.detach().to(torch.float64).reshape(-1).contiguous()
+
+    X = side(x, xoff, wx)
+    Y = X if y is None else side(y, yoff, wy)
+    out, sx, sy = engine.dgm_gram(*X, *Y, gamma, scale, mirror, paired=paired, symmetric=(y is None and not paired), work=work)
+    if check:
+        dgm_raise_on_status("diagram_gram", sx, None if y is None else sy)
+    return dict(out=out, status_x=sx, status_y=sy)
+
+
 def capture(fn, warmup=2):
     """HIP graph of a forward closure: `fn` (C-ABI launches on the current stream, outputs in caller-held or graph-pool buffers,
     no host synchronisation inside) is warmed up on a side stream, captured once, and replayed with `.replay()`.

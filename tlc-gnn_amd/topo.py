@@ -2,7 +2,8 @@
 function of the node values f, composed with the imager and the Wasserstein loss of `autograd`.
 
     f (an MLP on node features, an HKS time, ...)  ->  diagrams(f, ...)  ->  images(...) / landscapes(...) / wasserstein_to(...) /
-                                                       sliced_wasserstein_to(...) / bottleneck_to(...)  ->  loss.backward()
+                                                       sliced_wasserstein_to(...) / bottleneck_to(...) / kernel_distance_to(...) /
+                                                       gram(...)  ->  loss.backward()
 
 `hks_filtration(time, ...)` is the second of these filtrations: the normalised heat-kernel signature as a differentiable function of its
 diffusion time (`autograd.hks_signature`: values and d / d t from tlc_hks_batch_dt and tlc_hks_large_batch_dt), so a time can be learned
@@ -135,6 +136,24 @@ def sliced_wasserstein_to(f, node_offs, edge_offs, edges, target_pts, target_off
     check_which(which)
     pts, offs = _select(f, node_offs, edge_offs, edges, which, pd_large)
     return autograd.sliced_diagram_loss(pts, target_pts.to(pts.dtype), M=M, xoff=offs, yoff=target_offs)
+
+
+def kernel_distance_to(f, node_offs, edge_offs, edges, target_pts, target_offs, which="ord0+ext1", sigma=1.0, kernel="pss", pd_large="host"):
+    """[B] SQUARED kernel distances k(F, F) + k(G, G) - 2 k(F, G) (`autograd.diagram_kernel_distance`; 'pss': the persistence
+    scale-space kernel with bandwidth sigma, 'gauss': the plain Gaussian) between every graph's diagram `which` and the target diagrams
+    target_pts [sum k, 2] / target_offs int64[B + 1]; differentiable in f (and in target_pts when it requires grad).  The smooth sibling
+    of `sliced_wasserstein_to`: a double sum of Gaussians, no assignment, no sort, no cap on the points."""
+    check_which(which)
+    pts, offs = _select(f, node_offs, edge_offs, edges, which, pd_large)
+    return autograd.diagram_kernel_distance(pts, offs, target_pts.to(pts.dtype), target_offs, kernel=kernel, sigma=sigma)
+
+
+def gram(f, node_offs, edge_offs, edges, which="ord0+ext1", sigma=1.0, kernel="pss", pd_large="host"):
+    """[B, B] Gram matrix of the kernel between every two graphs' diagrams `which` (`autograd.diagram_gram`, the symmetric call) as a
+    differentiable function of f: what a kernel SVM on the exact diagrams takes, and the only B x B operation of this module."""
+    check_which(which)
+    pts, offs = _select(f, node_offs, edge_offs, edges, which, pd_large)
+    return autograd.diagram_gram(pts, offs, kernel=kernel, sigma=sigma)
 
 
 def bottleneck_to(f, node_offs, edge_offs, edges, target_pts, target_offs, which="ord0+ext1", pd_large="host"):
